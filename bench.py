@@ -1,13 +1,21 @@
 #!/usr/bin/env python3
 """Headline benchmark: CGNR iterations/sec @ 4096x2048 ComplexF32 (BASELINE.json `metric`).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 N = 1: a step is ONE CGNR iteration (src/CGNR.jl:143-178) of the matrix-free normal operator on a dense
 column-major ComplexF32 4096x2048 A that is already resident in HBM (lambda = 0, relTol = 0, SURVEY.md 8d
-"headline metric run").  The timed region is EXACTLY K iterations between barrier + synchronize on both sides;
-when that region is shorter than 10 ms it is repeated (>= 50 times, every repetition bracketed the same way) and
-`value` = K / median(elapsed), with the spread reported beside it.
+"headline metric run").  The timed region is ONE region of EXACTLY K iterations between barrier + synchronize on
+both sides, after W warm-up iterations; `value` = K / elapsed and `ms_per_step` = elapsed / K.
+
+A plain run does only that: set-up, warm-up, the timed region, the line.  `--full` adds everything else the line
+used to carry -- the solution check against a float64 CGNR on the host, the per-kernel timings and the rooflines
+(grid-exchange micro-benchmark, live `rocprofv3 --pmc` passes), the other paths of SURVEY 8 (`other_paths`), the CPU
+baselines and, at N > 1, the same-workload N = 1 rate and the config-4 / config-5 legs.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step -- the x (N = 1: `x.npy`; N > 1: one
+`x_rank<r>.npy` per rank; `--workload config4`: the batched X) -- as float32 (real, imaginary) pairs.  The inputs are
+generated from fixed seeds, so two builds run with the same arguments can be compared output for output.
 
 N > 1: one process per GPU.  `python bench.py --gpus N` from a plain shell starts `python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...` itself, as a CHILD process, before anything has
@@ -15,12 +23,12 @@ touched torch or HIP, relays its output and exit code (`--dry-launch` prints tha
 torchrun (RANK / WORLD_SIZE set) it runs as a rank.  The SAME workload and unit on every GPU -- one
 independent headline solve per GPU (the path shards by independent problems, src/MultiThreading.jl:30-79: no data-path
 collective, weak scaling), `value` = iterations/s summed over the GPUs, so value(N) / (N * value(1)) is an efficiency.
-Every N > 1 line also carries `n1_same_workload_value` (rank 0 running the same steps alone while the other ranks wait)
+With `--full` every N > 1 line also carries `n1_same_workload_value` (rank 0 running the same steps alone while the other ranks wait)
 and the quotient, plus `config4_batched`: BASELINE configs[3]'s shared-A flavour (8 right-hand sides per GPU advancing
 together on the matrix cores, solve-iterations/s) measured the same way.  `--workload config4` makes that the line's
 workload; `--workload rowsharded` runs BASELINE configs[4] (one tall A row-partitioned, one all-reduce per iteration).
 
-Prints ONE JSON line on rank 0 with `roofline` and (N = 1) `cpu_baseline` objects.
+Prints ONE JSON line on rank 0; with `--full` it carries `roofline` and (N = 1) `cpu_baseline` objects.
 """
 import argparse
 import ctypes as C
@@ -115,11 +123,15 @@ def float64_cgnr(A, b, n):
     return x
 
 
-def spread(xs):
-    xs = sorted(xs)
-    n = len(xs)
-    return {"n": n, "median": statistics.median(xs), "min": xs[0], "max": xs[-1], "p10": xs[int(0.1 * (n - 1))],
-            "p90": xs[int(math.ceil(0.9 * (n - 1)))]}
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy; complex values become (real, imaginary) pairs in a trailing axis of the
+    matching real type (complex64 -> float32)"""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype.kind == "c":
+            a = np.stack([a.real, a.imag], axis=-1)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 # ---- CPU baselines (rank 0, N = 1 only): the oracle's NumPy restatement and its C++/OpenMP restatement -----------
@@ -807,7 +819,14 @@ def main():
                          "register-resident kernels are switched off (N processes cannot all own the chip).  The line says `rehearsal`: "
                          "its numbers are not a scaling measurement")
     ap.add_argument("--c5-rows", type=int, default=65536, help="total rows of the config-5 matrix (rehearsals shrink it)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what it does not need: the solution check, the per-kernel timings and rooflines, "
+                         "other_paths, the CPU baselines and (N > 1) the same-workload N = 1 rate and the config-4 / config-5 legs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last step (the solution x) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload == "rowsharded":
+        ap.error("--dump-outputs is not available for --workload rowsharded")
     # (the pool's host driver supports dmabuf IPC only: without this RCCL's and our communicator's cross-process buffers fail with
     #  hipIpcGetMemHandle: invalid argument.  The image exports it already; a launcher that builds its own environment may not.)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -935,34 +954,23 @@ def main():
         ctx.sync()
         torch.cuda.synchronize()
 
-    def timed_regions(prepare, run, est_s):
-        """the contract's timed region -- barrier + synchronize, EXACTLY K steps, synchronize + barrier -- repeated
-        when it is short.  Returns wall-clock seconds (max over ranks) and hipEvent seconds of every repetition."""
+    def timed_region(prepare, run):
+        """the contract's timed region -- barrier + synchronize, EXACTLY K steps, synchronize + barrier -- once.  Returns its
+        wall-clock seconds (max over ranks) and its hipEvent seconds."""
+        prepare()
+        barrier()
+        ctx.timer_start()
+        t0 = time.perf_counter()
+        run()
+        ev_ms = ctx.timer_stop_ms()  # hipEvents on the stream the kernels run on; synchronises that stream
+        torch.cuda.synchronize()
+        el = time.perf_counter() - t0
         if dist is not None:
-            # every rank must run the SAME number of repetitions (each one holds a barrier and an all-reduce): the estimate is a
-            # per-rank measurement, so agree on the largest (found by the one-GPU rehearsal: rank 0 waited for ever)
-            tt = torch.tensor([est_s], dtype=torch.float64, device="cuda")
+            dist.barrier()
+            tt = torch.tensor([el], dtype=torch.float64, device="cuda")
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            est_s = float(tt.item())
-        reps = 5 if est_s >= 0.010 else int(min(400, max(50, math.ceil(0.4 / max(est_s, 1e-5)))))
-        walls, evs = [], []
-        for _ in range(reps):
-            prepare()
-            barrier()
-            ctx.timer_start()
-            t0 = time.perf_counter()
-            run()
-            ev_ms = ctx.timer_stop_ms()  # hipEvents on the stream the kernels run on; synchronises that stream
-            torch.cuda.synchronize()
-            el = time.perf_counter() - t0
-            if dist is not None:
-                dist.barrier()
-                tt = torch.tensor([el], dtype=torch.float64, device="cuda")
-                dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-                el = float(tt.item())
-            walls.append(el)
-            evs.append(ev_ms * 1e-3)
-        return walls, evs
+            el = float(tt.item())
+        return el, ev_ms * 1e-3
 
     def solo_rate(prepare, run, units):
         """units / wall time of `run` on rank 0 ALONE (the other ranks wait at the barrier): the N = 1 figure of the same
@@ -1034,10 +1042,9 @@ def main():
 
         step(20 * SEGMENT); ctx.sync()
         step(W)
-        t0 = time.perf_counter(); init(); step(min(K, 4 * SEGMENT), True); ctx.sync()
-        est = (time.perf_counter() - t0) * K / min(K, 4 * SEGMENT)
-        walls, evs = timed_regions(init, lambda: step(K, True), est)
-        elapsed, ev = statistics.median(walls), statistics.median(evs)
+        elapsed, ev = timed_region(init, lambda: step(K, True))
+        if args.dump_outputs and not leg_name:
+            dump_outputs(args.dump_outputs, {"X" if world == 1 else f"X_rank{rank}": st.X.to_host()})
         stat = st.status()
         assert all(math.isfinite(s_.residual) for s_ in stat), "batched CGNR residual is not finite"
         rate = R * K / elapsed
@@ -1057,8 +1064,7 @@ def main():
             "config": {"workload": f"BASELINE configs[3]: CGNR {M}x{N} ComplexF32, shared A, {R} right-hand sides per GPU advancing together "
                                    f"(BatchedState: per-column scalars and done flags), lambda=0, relTol=0, back-to-back solves of {SEGMENT} "
                                    f"iterations, no data-path collective", "M": M, "N": N, "rhs_per_gpu": R, "step": "one batched iteration"},
-            "timed_region": {"repetitions": len(walls), "wall_s": spread(walls), "hip_events_s": spread(evs),
-                             "value_is": "n_gpus * rhs_per_gpu * steps / median(wall, max over ranks)"},
+            "timed_region": {"wall_s": elapsed, "hip_events_s": ev, "value_is": "n_gpus * rhs_per_gpu * steps / wall (max over ranks)"},
             "per_rank_solve_iterations_per_s_hip_events": rates,
         }
         # which roof binds a batched iteration: the two passes over the shared A (2*M*N*s bytes, whatever the
@@ -1086,7 +1092,7 @@ def main():
                                      "hbm basis: A streamed twice per batched iteration (2*M*N*s bytes, shared by the right-hand sides; it "
                                      "comes out of the Infinity Cache, so the memory-side counters see less); mfma basis: 16*M*N flops per "
                                      "solve-iteration (complex MAC = 8 flops, two products), padding columns not counted"))
-        n1 = solo_rate(init, lambda: step(K, True), R * K)
+        n1 = solo_rate(init, lambda: step(K, True), R * K) if args.full else None
         if n1 is not None:
             out["n1_same_workload_value"] = n1
             out["efficiency_vs_n1_same_workload"] = out["value"] / (world * n1)
@@ -1128,19 +1134,50 @@ def main():
     ctx.sync()
     step(W)
     ctx.sync()
-    t0 = time.perf_counter(); rls.init_(solver, bd); step(min(K, 4 * SEGMENT), True); ctx.sync()
-    est = (time.perf_counter() - t0) * K / min(K, 4 * SEGMENT)
     trace("headline: warm-up done")
-    walls, evs = timed_regions(lambda: rls.init_(solver, bd), lambda: step(K, True), est)
-    trace("headline: timed regions done")
-    elapsed, ev = statistics.median(walls), statistics.median(evs)
+    elapsed, ev = timed_region(lambda: rls.init_(solver, bd), lambda: step(K, True))
+    trace("headline: timed region done")
     st._refresh(lib)
     assert st.iteration == ((K - 1) % SEGMENT) + 1, (st.iteration, K)
     assert math.isfinite(st._residual), "CGNR residual is not finite"
-    # the line proves its own work: the x the timed region left behind (st.iteration iterations into its last solve) against a
-    # float64 CGNR of the same count on the host, and against the planted solution (CG converges geometrically on this matrix)
     sol_iter = int(st.iteration)
-    x_dev = st.x.to_host().astype(np.complex128)
+    x_host = st.x.to_host()  # what the caller of the timed path receives: the x of its last solve, st.iteration iterations in
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x" if world == 1 else f"x_rank{rank}": x_host})
+
+    out = {
+        "metric": "CGNR iterations/sec @4096x2048 CF32; achieved HBM GB/s vs roofline",
+        "value": world * K / elapsed,
+        "unit": "iterations/s",
+        "n_gpus": world,
+        "steps": K,
+        "warmup": W,
+        "ms_per_step": 1e3 * elapsed / K,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "c64 (ComplexF32 storage and arithmetic; scalar reductions accumulated in f64)",
+        "data": "synthetic",
+        **({"rehearsal": "every rank on device 0, gloo control plane, resident kernels off: the N > 1 CODE PATH on one GPU -- not a "
+                         "scaling measurement"} if args.rehearse else {}),
+        "config": {"workload": f"CGNR matrix-free normal operator, dense column-major ComplexF32 {M}x{N}, lambda=0, relTol=0, back-to-back "
+                               f"solves of {SEGMENT} iterations (BASELINE configs[1] shape, headline metric run of SURVEY 8d)" +
+                               ("" if world == 1 else "; one independent solve per GPU, no collectives"),
+                   "M": M, "N": N, "problems_per_gpu": 1, "kernel_path": PATH_NAMES.get(path.value, str(path.value)),
+                   # which regime `value` is in: a resident launch pays its slab load once per step call, and the first solve's init!
+                   # lies outside the timed region when the region is a single launch
+                   "iterations_per_launch": (min(K, SEGMENT) if path.value in (4, 5) else 1), "init_inside_region": bool(K > SEGMENT)},
+        "timed_region": {"wall_s": elapsed, "hip_events_s": ev, "iterations_per_s_hip_events": K / ev,
+                         "value_is": "n_gpus * steps / wall (max over ranks); the region is exactly `steps` iterations between "
+                                     "barrier + synchronize on both sides"},
+    }
+    if not args.full:
+        return finish(out if rank == 0 else None)
+
+    # ---- --full: everything the headline does not need -------------------------------------------------------------
+    # the line proves its own work: the x the timed region left behind against a float64 CGNR of the same iteration count on the
+    # host, and against the planted solution (CG converges geometrically on this matrix)
+    x_dev = x_host.astype(np.complex128)
     x_f64 = float64_cgnr(A, b, sol_iter)
     sol_err = float(np.linalg.norm(x_dev - x_f64) / np.linalg.norm(x_f64))
     sol_err_true = float(np.linalg.norm(x_dev - x_true) / np.linalg.norm(x_true))
@@ -1326,35 +1363,10 @@ def main():
     frac_alg = iter_gbs / HBM_PEAK_GBS
 
     if rank == 0:
-        out = {
-            "metric": "CGNR iterations/sec @4096x2048 CF32; achieved HBM GB/s vs roofline",
-            "value": world * K / elapsed,
-            "unit": "iterations/s",
-            "n_gpus": world,
-            "steps": K,
-            "warmup": W,
-            "ms_per_step": 1e3 * elapsed / K,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "c64 (ComplexF32 storage and arithmetic; scalar reductions accumulated in f64)",
-            "data": "synthetic",
-            **({"rehearsal": "every rank on device 0, gloo control plane, resident kernels off: the N > 1 CODE PATH on one GPU -- not a "
-                             "scaling measurement"} if args.rehearse else {}),
-            "config": {"workload": f"CGNR matrix-free normal operator, dense column-major ComplexF32 {M}x{N}, lambda=0, relTol=0, back-to-back "
-                                   f"solves of {SEGMENT} iterations (BASELINE configs[1] shape, headline metric run of SURVEY 8d)" +
-                                   ("" if world == 1 else "; one independent solve per GPU, no collectives"),
-                       "M": M, "N": N, "problems_per_gpu": 1, "kernel_path": PATH_NAMES.get(path.value, str(path.value))},
-            "timed_region": {"repetitions": len(walls), "wall_s": spread(walls), "hip_events_s": spread(evs),
-                             "value_is": "n_gpus * steps / median(wall); every repetition is exactly `steps` iterations between "
-                                         "barrier + synchronize on both sides",
-                             "iterations_per_s_hip_events": K / ev},
-            "solution_check": {"rel_err_vs_float64_cgnr_same_iteration": sol_err, "tolerance": 1e-5, "iteration": sol_iter,
-                               "rel_err_vs_planted_x_true": sol_err_true,
-                               "what": "x left by the LAST solve of the timed region (max over ranks) against a complex128 CGNR of the same "
-                                       "iteration count run on the host by bench.py itself; asserted before the line is printed"},
-            "roofline": {},
-        }
+        out["solution_check"] = {"rel_err_vs_float64_cgnr_same_iteration": sol_err, "tolerance": 1e-5, "iteration": sol_iter,
+                                 "rel_err_vs_planted_x_true": sol_err_true,
+                                 "what": "x left by the LAST solve of the timed region (max over ranks) against a complex128 CGNR of the same "
+                                         "iteration count run on the host by bench.py itself; asserted before the line is printed"}
         hbm_view = {
             # algorithmic basis, the ITERATION as the unit (SURVEY 8d bytes per iteration x iterations / device time of the timed region)
             "peak_GBps": HBM_PEAK_GBS, "algorithmic_GBps": iter_gbs, "frac_algorithmic": frac_alg,
@@ -1384,10 +1396,6 @@ def main():
                                "hbm_streaming": hbm_streaming, "hbm_bytes_per_launch_used": hbm_bytes, "note": hbm_view["note"]}
         out["roofline"]["per_kernel"] = kern
         out["roofline"]["iteration"] = {"bytes": bytes_iter, "us_hip_events": 1e6 * ev / K, "roofline_us_at_peak": bytes_iter / HBM_PEAK_GBS / 1e3}
-        # which regime `value` is in: a resident launch pays its slab load once per step call, and the first solve's init! lies
-        # outside the timed region when the region is a single launch
-        out["config"]["iterations_per_launch"] = (min(K, SEGMENT) if path.value in (4, 5) else 1)
-        out["config"]["init_inside_region"] = bool(K > SEGMENT)
         if n1_value is not None:
             out["n1_same_workload_value"] = n1_value
             out["efficiency_vs_n1_same_workload"] = out["value"] / (world * n1_value)

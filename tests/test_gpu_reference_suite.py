@@ -217,6 +217,39 @@ def test_fista_tv_plan_reused_with_other_parameters(rls, ctx):
     assert np.array_equal(rls.solve_(s, bd).to_host(), x1)
 
 
+# ---- bench.py's plain line: the headline alone, and the x its last timed step left behind --------------------------------
+def test_bench_plain_line_times_exactly_the_steps_and_dumps_its_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: ONE line with the headline fields and nothing that takes a
+    run of its own (those are `--full`'s), and DIR/x.npy = the x of the last timed solve, ((K - 1) % 32) + 1 iterations in, as float32
+    (real, imaginary) pairs -- checked against a complex128 CGNR of the same count on the same seeded problem"""
+    import json
+    import subprocess
+    import sys
+
+    import bench
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "8", "--dump-outputs",
+                        str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 40 and d["warmup"] == 8 and d["unit"] == "iterations/s" and d["higher_is_better"] is True
+    assert d["value"] > 0 and abs(d["ms_per_step"] - 1e3 / d["value"]) <= 1e-9 * d["ms_per_step"]
+    assert not {"roofline", "cpu_baseline", "other_paths", "solution_check"} & set(d)
+    x = np.load(out / "x.npy")
+    assert x.dtype == np.float32 and x.shape == (2048, 2)
+    A = bench.make_A(4096, 2048, seed=2)
+    rng = np.random.default_rng(1000)
+    x_true = ((rng.standard_normal(2048) + 1j * rng.standard_normal(2048)) / np.sqrt(2)).astype(np.complex64)
+    b = (A @ x_true).astype(np.complex64)
+    want = bench.float64_cgnr(A, b, (40 - 1) % 32 + 1)
+    got = x[:, 0].astype(np.float64) + 1j * x[:, 1]
+    assert np.linalg.norm(got - want) / np.linalg.norm(want) <= 1e-5
+
+
 # ---- the N > 1 path of bench.py, rehearsed on the one GPU of this box ---------------------------------------------------
 @pytest.mark.parametrize("n", [2, 8])
 def test_bench_multi_gpu_path_rehearsed_on_one_gpu(n):
@@ -231,8 +264,8 @@ def test_bench_multi_gpu_path_rehearsed_on_one_gpu(n):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--rehearse", "--steps", "64", "--warmup", "32",
-                        "--c5-rows", "8192"], env=env, capture_output=True, text=True, timeout=1500)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--rehearse", "--full", "--steps", "64",
+                        "--warmup", "32", "--c5-rows", "8192"], env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, lines
@@ -269,8 +302,8 @@ def test_bench_multi_gpu_leg_failure_on_one_rank_keeps_the_line(where):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(RLS_BENCH_FAIL=where, RLS_BENCH_DIST_TIMEOUT_S="60")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse", "--steps", "64", "--warmup", "32",
-                        "--c5-rows", "8192"], env=env, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse", "--full", "--steps", "64",
+                        "--warmup", "32", "--c5-rows", "8192"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, lines
@@ -460,8 +493,8 @@ def test_bench_other_multi_gpu_workloads_rehearsed(workload):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse", "--workload", workload, "--steps", "64",
-                        "--warmup", "32", "--c5-rows", "8192"], env=env, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse", "--full", "--workload", workload,
+                        "--steps", "64", "--warmup", "32", "--c5-rows", "8192"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, lines

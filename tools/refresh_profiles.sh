@@ -5,8 +5,9 @@ R=${1:-r02}
 cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-timeout 600 python3 bench.py > gpurun_out/${R}_bench_n1.json 2> gpurun_out/${R}_bench_n1.err
-tail -c 400 gpurun_out/${R}_bench_n1.json
+# the full bench line (solution check, rooflines, other paths, CPU baselines), kept under TMPDIR beside the rocprofv3 trees
+timeout 600 python3 bench.py --full > "$TMPDIR/${R}_bench_n1.json" 2> "$TMPDIR/${R}_bench_n1.err"
+tail -c 400 "$TMPDIR/${R}_bench_n1.json"
 rm -rf /tmp/prof_bench /tmp/prof_pipe /tmp/pmc_fetch /tmp/pmc_write /tmp/prof_cfg /tmp/prof_batched
 # headline run (resident kernel) and the same run on the two-launch pipeline
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -o bench -- python3 "$GRAFT_REPO_ROOT/bench.py" --no-extras --no-cpu-baseline --steps 1600 --warmup 160 > /dev/null 2>&1)
