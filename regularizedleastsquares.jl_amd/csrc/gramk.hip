@@ -890,53 +890,13 @@ __global__ __launch_bounds__(GK_NT) void fista_gramk_resident_kernel(rls_fgramk 
 static size_t gk_lds_bytes(int64_t N) { return gk_panel_bytes(N) + sizeof(gk_lds_tail); }
 static size_t fk_lds_bytes(int64_t N) { return gk_panel_bytes(N) + sizeof(fk_lds_tail); }
 
-// KIND 0: CGNR, 1: FISTA
-template <int KIND, int NE, bool FULL>
-static const void* gk_kernel() {
-  if constexpr (KIND == 0) return reinterpret_cast<const void*>(&cgnr_gramk_resident_kernel<NE, FULL>);
-  else return reinterpret_cast<const void*>(&fista_gramk_resident_kernel<NE, FULL>);
-}
-template <int KIND>
-static size_t gk_kind_lds(int64_t N) { return KIND == 0 ? gk_lds_bytes(N) : fk_lds_bytes(N); }
-
-template <int KIND, int NE>
-static void gk_allow_lds() {
-  (void)hipFuncSetAttribute(gk_kernel<KIND, NE, true>(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gk_kind_lds<KIND>(256 * NE));
-  (void)hipFuncSetAttribute(gk_kernel<KIND, NE, false>(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gk_kind_lds<KIND>(256 * NE));
-}
-template <int KIND, int NE>
-static hipError_t gk_occupancy(int* blocks, bool full) {
-  if constexpr (KIND == 0)
-    return full ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, cgnr_gramk_resident_kernel<NE, true>, GK_NT, gk_lds_bytes(256 * NE))
-                : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, cgnr_gramk_resident_kernel<NE, false>, GK_NT, gk_lds_bytes(256 * NE));
-  else
-    return full ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, fista_gramk_resident_kernel<NE, true>, GK_NT, fk_lds_bytes(256 * NE))
-                : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, fista_gramk_resident_kernel<NE, false>, GK_NT, fk_lds_bytes(256 * NE));
-}
-template <int NE>
-static void gk_launch(rls_ctx* ctx, const rls_gramk& D, void* sync, int n_steps, unsigned spin_limit) {
-  const int nwg = (int)(D.N / GK_ROWS);
-  const size_t lds = gk_lds_bytes(D.N);
-  if (D.N == 256 * NE)
-    hipLaunchKernelGGL((cgnr_gramk_resident_kernel<NE, true>), dim3(nwg), dim3(GK_NT), lds, ctx->stream, D, (resident_sync*)sync, n_steps,
-                       spin_limit);
-  else
-    hipLaunchKernelGGL((cgnr_gramk_resident_kernel<NE, false>), dim3(nwg), dim3(GK_NT), lds, ctx->stream, D, (resident_sync*)sync, n_steps,
-                       spin_limit);
-}
-template <int NE>
-static void fk_launch(rls_ctx* ctx, const rls_fgramk& D, void* sync, int n_steps, unsigned spin_limit) {
-  const int nwg = (int)(D.N / GK_ROWS);
-  const size_t lds = fk_lds_bytes(D.N);
-  if (D.N == 256 * NE)
-    hipLaunchKernelGGL((fista_gramk_resident_kernel<NE, true>), dim3(nwg), dim3(GK_NT), lds, ctx->stream, D, (resident_sync*)sync, n_steps,
-                       spin_limit);
-  else
-    hipLaunchKernelGGL((fista_gramk_resident_kernel<NE, false>), dim3(nwg), dim3(GK_NT), lds, ctx->stream, D, (resident_sync*)sync, n_steps,
-                       spin_limit);
+// f(NE, FULL) for the instantiation that runs N rows (its LDS image depends on NE alone: gk_panel_bytes)
+template <typename F>
+static auto with_gk_shape(int64_t N, F&& f) {
+  return rls_with<1, 2, 4, 8>(gk_ne(N), [&](auto NE) { return with_bool(N == 256 * NE, [&](auto FULL) { return f(NE, FULL); }); });
 }
 
-// shapes both kernels take, and whether one workgroup of kernel KIND fits a CU
+// shapes both kernels take, and whether one workgroup of kernel KIND (0: CGNR, 1: FISTA) fits a CU
 template <int KIND>
 static bool gk_resident_ok(rls_ctx* ctx, int32_t dtype, int64_t N, int nrhs, const void* G, int64_t ldg) {
   if (dtype != RLS_C32 || !G || nrhs < 1 || nrhs > GK_KB || N < 16 || N % 16 || N > GK_NMAX) return false;
@@ -945,20 +905,12 @@ static bool gk_resident_ok(rls_ctx* ctx, int32_t dtype, int64_t N, int nrhs, con
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess) return false;
   if (!(nwg <= cus && nwg <= 256)) return false;
-  static rls_device_once attr_once;
-  if (auto once_ = attr_once.first(ctx->device)) {
-    gk_allow_lds<KIND, 1>();
-    gk_allow_lds<KIND, 2>();
-    gk_allow_lds<KIND, 4>();
-    gk_allow_lds<KIND, 8>();
-  }
-  int blocks = 0;
-  const int ne = gk_ne(N);
-  const bool full = N == 256 * ne;
-  const hipError_t e = ne == 1 ? gk_occupancy<KIND, 1>(&blocks, full) : ne == 2 ? gk_occupancy<KIND, 2>(&blocks, full)
-                       : ne == 4 ? gk_occupancy<KIND, 4>(&blocks, full) : gk_occupancy<KIND, 8>(&blocks, full);
-  (void)hipGetLastError();
-  return e == hipSuccess && blocks >= 1;
+  return with_gk_shape(N, [&](auto NE, auto FULL) {
+    if constexpr (KIND == 0)
+      return rls_occupancy<cgnr_gramk_resident_kernel<NE, FULL>>(ctx->device, GK_NT, gk_lds_bytes(N)) >= 1;
+    else
+      return rls_occupancy<fista_gramk_resident_kernel<NE, FULL>>(ctx->device, GK_NT, fk_lds_bytes(N)) >= 1;
+  });
 }
 
 }  // namespace
@@ -976,14 +928,10 @@ bool rls_gramk_resident_ok(rls_ctx* ctx, int32_t dtype, int64_t N, int nrhs, con
 }
 
 int32_t rls_gramk_resident_launch(rls_ctx* ctx, const rls_gramk& D, void* sync, int n_steps, unsigned spin_limit) {
-  const int ne = gk_ne(D.N);
-  if (ne == 1) gk_launch<1>(ctx, D, sync, n_steps, spin_limit);
-  else if (ne == 2) gk_launch<2>(ctx, D, sync, n_steps, spin_limit);
-  else if (ne == 4) gk_launch<4>(ctx, D, sync, n_steps, spin_limit);
-  else gk_launch<8>(ctx, D, sync, n_steps, spin_limit);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rls_fail(ctx, (int32_t)e, hipGetErrorString(e));
-  return 0;
+  return with_gk_shape(D.N, [&](auto NE, auto FULL) {
+    return rls_launch<cgnr_gramk_resident_kernel<NE, FULL>>(ctx, dim3((int)(D.N / GK_ROWS)), dim3(GK_NT), gk_lds_bytes(D.N), D,
+                                                           (resident_sync*)sync, n_steps, spin_limit);
+  });
 }
 
 // FISTA: exchanged rows of y [2 parities][re | im][2 column halves][rows][16 bytes], gathered x / xold / res [3][N][8] complex,
@@ -999,12 +947,8 @@ bool rls_fgramk_resident_ok(rls_ctx* ctx, int32_t dtype, int64_t N, int nrhs, co
 }
 
 int32_t rls_fgramk_resident_launch(rls_ctx* ctx, const rls_fgramk& D, void* sync, int n_steps, unsigned spin_limit) {
-  const int ne = gk_ne(D.N);
-  if (ne == 1) fk_launch<1>(ctx, D, sync, n_steps, spin_limit);
-  else if (ne == 2) fk_launch<2>(ctx, D, sync, n_steps, spin_limit);
-  else if (ne == 4) fk_launch<4>(ctx, D, sync, n_steps, spin_limit);
-  else fk_launch<8>(ctx, D, sync, n_steps, spin_limit);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rls_fail(ctx, (int32_t)e, hipGetErrorString(e));
-  return 0;
+  return with_gk_shape(D.N, [&](auto NE, auto FULL) {
+    return rls_launch<fista_gramk_resident_kernel<NE, FULL>>(ctx, dim3((int)(D.N / GK_ROWS)), dim3(GK_NT), fk_lds_bytes(D.N), D,
+                                                            (resident_sync*)sync, n_steps, spin_limit);
+  });
 }

@@ -3784,47 +3784,55 @@ static int64_t fused_nwg(const rls_tuning& T, int64_t M, int64_t N) {
   return (Mc + c.G - 1) / c.G;
 }
 
-template <typename KernelT>
-static void allow_big_lds(KernelT* k, size_t lds) {
-  hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+// the shapes of kCfgs as template constants: f(slab_shape<G, K, WV>{})
+template <int G_, int K_, int WV_>
+struct slab_shape {
+  static constexpr int G = G_, K = K_, WV = WV_;
+};
+template <typename F>
+static auto with_cfg(const fused_cfg& c, F&& f) {
+  if (c.G == 8 && c.K == 8 && c.WV == 8) return f(slab_shape<8, 8, 8>{});
+  if (c.G == 8 && c.K == 16 && c.WV == 8) return f(slab_shape<8, 16, 8>{});
+  if (c.G == 8 && c.K == 32 && c.WV == 8) return f(slab_shape<8, 32, 8>{});
+  return f(slab_shape<4, 32, 8>{});  // (pick_cfg returns an entry of kCfgs)
 }
 
+// the full-size instantiation (no clamps at all): N columns fill the slab and the nwg blocks of G row pieces cover the M rows exactly
 template <typename E, int G, int K, int WV>
-static int launch_slab(rls_ctx* ctx, const E* A, int64_t lda, const E* p, E* slab, int64_t M, int64_t N, int nwg,
-                       const int* skip) {
+static bool slab_full(int64_t M, int64_t N, int nwg) {
+  using C = slab_cfg<E, G, K, WV>;
+  return N == C::NMAX && (int64_t)nwg * G == M / C::NV;
+}
+
+// finish kernels: f(EPT) for the elements per thread that N needs, 1, 2 or 4
+template <typename F>
+static auto with_ept(int64_t N, F&& f) {
+  const int ept = (int)((N + FIN_THREADS - 1) / FIN_THREADS);
+  return rls_with<1, 2, 4>(ept <= 1 ? 1 : ept <= 2 ? 2 : 4, f);
+}
+
+// a combination the launcher's runtime choice never reaches
+static int32_t not_instantiated(rls_ctx* ctx) { return rls_fail(ctx, RLS_E_UNSUPPORTED, "kernel variant not instantiated"); }
+
+// `grid` < nwg: the MULTI instantiation (K = 32 only), `grid` workgroups walking the nwg row blocks (`grid` partial rows)
+template <typename E, int G, int K, int WV>
+static int32_t launch_slab(rls_ctx* ctx, const E* A, int64_t lda, const E* p, E* slab, int64_t M, int64_t N, int nwg, int grid,
+                           const int* skip) {
   using C = slab_cfg<E, G, K, WV>;
   const int64_t Mc = M / C::NV;
   const int pair = slab_pairing(G, nwg);
   constexpr size_t lds = sizeof(slab_lds<E, G, K, WV>);
-  static rls_device_once attr_once;  // per template instantiation and device
-  if (auto once_ = attr_once.first(ctx->device)) {
-    allow_big_lds(&normal_slab_kernel<E, G, K, WV, true>, lds);
-    allow_big_lds(&normal_slab_kernel<E, G, K, WV, false>, lds);
-    if constexpr (K == 32) {
-      allow_big_lds(&normal_slab_multi_kernel<E, G, K, WV, true>, lds);
-      allow_big_lds(&normal_slab_multi_kernel<E, G, K, WV, false>, lds);
-    }
-  }
-  const bool full = N == C::NMAX && (int64_t)nwg * G == Mc;
-  const int grid = slab_grid(ctx, K, nwg);
-  if constexpr (K == 32) {
-    if (grid < nwg) {  // several row blocks per workgroup: `grid` partial rows
-      if (full)
-        hipLaunchKernelGGL((normal_slab_multi_kernel<E, G, K, WV, true>), dim3(grid), dim3(C::NT), lds, ctx->stream, A, lda, p,
-                           slab, Mc, N, pair, nwg, skip);
+  return with_bool(slab_full<E, G, K, WV>(M, N, nwg), [&](auto FULL) {
+    return with_bool(K == 32 && grid < nwg, [&](auto MULTI) {
+      if constexpr (!MULTI)
+        return rls_launch<normal_slab_kernel<E, G, K, WV, FULL>>(ctx, dim3(nwg), dim3(C::NT), lds, A, lda, p, slab, Mc, N, pair, skip);
+      else if constexpr (K == 32)
+        return rls_launch<normal_slab_multi_kernel<E, G, K, WV, FULL>>(ctx, dim3(grid), dim3(C::NT), lds, A, lda, p, slab, Mc, N, pair,
+                                                                       nwg, skip);
       else
-        hipLaunchKernelGGL((normal_slab_multi_kernel<E, G, K, WV, false>), dim3(grid), dim3(C::NT), lds, ctx->stream, A, lda, p,
-                           slab, Mc, N, pair, nwg, skip);
-      return grid;
-    }
-  }
-  if (full)
-    hipLaunchKernelGGL((normal_slab_kernel<E, G, K, WV, true>), dim3(nwg), dim3(C::NT), lds, ctx->stream, A, lda, p,
-                       slab, Mc, N, pair, skip);
-  else
-    hipLaunchKernelGGL((normal_slab_kernel<E, G, K, WV, false>), dim3(nwg), dim3(C::NT), lds, ctx->stream, A, lda, p,
-                       slab, Mc, N, pair, skip);
-  return nwg;
+        return not_instantiated(ctx);
+    });
+  });
 }
 
 // rows: the workgroups of K_A (= its partial rows); rows < nwg is the MULTI instantiation, which keeps <p, v>
@@ -3841,7 +3849,7 @@ static pipe_rhs_ptrs rhs_of(const rls_cgnr_pipe& P, int nwg, int rows = 0) {
 
 // `grid` < nwg: the MULTI instantiation (K = 32 only), `grid` workgroups walking the nwg row blocks
 template <typename E, int G, int K, int WV>
-static void launch_pipe_a(rls_ctx* ctx, const rls_cgnr_pipe& P, int nwg, int grid) {
+static int32_t launch_pipe_a(rls_ctx* ctx, const rls_cgnr_pipe& P, int nwg, int grid) {
   using C = slab_cfg<E, G, K, WV>;
   const int64_t Mc = P.M / C::NV;
   const int pair = slab_pairing(G, nwg);
@@ -3851,68 +3859,28 @@ static void launch_pipe_a(rls_ctx* ctx, const rls_cgnr_pipe& P, int nwg, int gri
   // does not know which pair is current (the first node of a graph chunk) runs the hinted kernel on a guess -- that kernel
   // checks the hint on the device and re-loads the right pair, late, when it was wrong.
   constexpr bool ALWAYS_HINTED = elem<E>::cplx && G == 4 && K == 32;
-  static rls_device_once attr_once;
-  if (auto once_ = attr_once.first(ctx->device)) {
-    if constexpr (!ALWAYS_HINTED) {
-      allow_big_lds(&cgnr_pipe_a_kernel<E, G, K, WV, true, false, false>, lds);
-      allow_big_lds(&cgnr_pipe_a_kernel<E, G, K, WV, false, false, false>, lds);
-    }
-    allow_big_lds(&cgnr_pipe_a_kernel<E, G, K, WV, true, false, true>, lds);
-    allow_big_lds(&cgnr_pipe_a_kernel<E, G, K, WV, false, false, true>, lds);
-    if constexpr (K == 32) {
-      if constexpr (!ALWAYS_HINTED) {
-        allow_big_lds(&cgnr_pipe_a_kernel<E, G, K, WV, true, false, false, true>, lds);
-        allow_big_lds(&cgnr_pipe_a_kernel<E, G, K, WV, false, false, false, true>, lds);
-      }
-      allow_big_lds(&cgnr_pipe_a_kernel<E, G, K, WV, true, false, true, true>, lds);
-      allow_big_lds(&cgnr_pipe_a_kernel<E, G, K, WV, false, false, true, true>, lds);
-    }
-  }
-  const bool full = P.N == C::NMAX && (int64_t)nwg * G == Mc;
-  const bool batched = P.nrhs > 1;
+  const bool full = slab_full<E, G, K, WV>(P.M, P.N, nwg);
   auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   // single right-hand side: the hinted instantiation (its full-size form loads the vectors in 16-byte pieces)
   const bool aligned = al16(P.r0) && al16(P.p0) && al16(P.r1) && al16(P.p1) && al16(P.v);
-  const bool hinted = !batched && P.cur_hint >= 0 && aligned;
+  const bool hinted = P.nrhs <= 1 && P.cur_hint >= 0 && aligned;
   pipe_rhs_ptrs R = rhs_of(P, nwg, grid);
-#define RLS_LAUNCH_A2(FULLV, BATCHV, HINTV, MULTIV)                                                                     \
-  hipLaunchKernelGGL((cgnr_pipe_a_kernel<E, G, K, WV, FULLV, BATCHV, HINTV, MULTIV>), dim3(MULTIV ? grid : nwg), dim3(C::NT),  \
-                     lds, ctx->stream, (const E*)P.A, P.lda, (E*)P.x, (E*)P.r0, (E*)P.p0, (E*)P.r1, (E*)P.p1, (const E*)P.v, \
-                     (E*)P.slab, P.dots, P.ndots, P.sc, P.scn, Mc, P.N, pair, ctx->tune.slab_order, R, nwg)
-#define RLS_LAUNCH_A(FULLV, BATCHV, HINTV)                      \
-  do {                                                          \
-    if constexpr (K == 32) {                                    \
-      if (grid < nwg) {                                         \
-        RLS_LAUNCH_A2(FULLV, BATCHV, HINTV, true);              \
-        break;                                                  \
-      }                                                         \
-    }                                                           \
-    RLS_LAUNCH_A2(FULLV, BATCHV, HINTV, false);                 \
-  } while (0)
+  if (ALWAYS_HINTED && R.hint < 0) R.hint = 0;
   // (a BATCHED = true instantiation -- the slab kernel looping over several right-hand sides on the VALU -- existed until
   //  round 3 as the fallback of the matrix-core batched path; it spilled up to 528 bytes per lane and was four times slower
   //  per solve-iteration than the skinny kernels: shapes those do not cover now run one plan per column)
-  (void)batched;
-  if constexpr (ALWAYS_HINTED) {
-    if (R.hint < 0) R.hint = 0;
-    if (full && aligned) RLS_LAUNCH_A(true, false, true);   // (the full-size hinted form loads 16-byte pieces)
-    else RLS_LAUNCH_A(false, false, true);
-  } else {
-    if (full && hinted) RLS_LAUNCH_A(true, false, true);
-    else if (hinted) RLS_LAUNCH_A(false, false, true);
-    else if (full) RLS_LAUNCH_A(true, false, false);
-    else RLS_LAUNCH_A(false, false, false);
-  }
-#undef RLS_LAUNCH_A
-#undef RLS_LAUNCH_A2
-}
-
-#define RLS_FOR_EACH_CFG(X) X(8, 8, 8) X(8, 16, 8) X(8, 32, 8) X(4, 32, 8)
-
-static int32_t launch_status(rls_ctx* ctx) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rls_fail(ctx, (int32_t)e, hipGetErrorString(e));
-  return 0;
+  return with_bool(ALWAYS_HINTED ? full && aligned : full, [&](auto FULL) {
+    return with_bool(ALWAYS_HINTED || hinted, [&](auto HINT) {
+      return with_bool(K == 32 && grid < nwg, [&](auto MULTI) {
+        if constexpr ((ALWAYS_HINTED && !HINT) || (MULTI && K != 32))
+          return not_instantiated(ctx);
+        else
+          return rls_launch<cgnr_pipe_a_kernel<E, G, K, WV, FULL, false, HINT, MULTI>>(
+              ctx, dim3(MULTI ? grid : nwg), dim3(C::NT), lds, (const E*)P.A, P.lda, (E*)P.x, (E*)P.r0, (E*)P.p0, (E*)P.r1,
+              (E*)P.p1, (const E*)P.v, (E*)P.slab, P.dots, P.ndots, P.sc, P.scn, Mc, P.N, pair, ctx->tune.slab_order, R, nwg);
+      });
+    });
+  });
 }
 
 template <typename E>
@@ -3921,11 +3889,8 @@ static int32_t normal_typed(rls_ctx* ctx, int64_t M, int64_t N, const E* A, int6
   fused_cfg c;
   if (!pick_cfg<E>(ctx->tune, N, &c)) return rls_fail(ctx, RLS_E_UNSUPPORTED, "normal_fused: N too large for a register slab");
   const int nwg = (int)fused_nwg<E>(ctx->tune, M, N);
-  int rows = nwg;  // partial rows the slab launch leaves
-#define RLS_SLAB_CASE(GG, KK, WW) \
-  if (c.G == GG && c.K == KK && c.WV == WW) rows = launch_slab<E, GG, KK, WW>(ctx, A, lda, p, slab, M, N, nwg, skip);
-  RLS_FOR_EACH_CFG(RLS_SLAB_CASE)
-#undef RLS_SLAB_CASE
+  const int rows = slab_grid(ctx, c.K, nwg);  // partial rows the slab launch leaves = its workgroups
+  RLS_TRY(with_cfg(c, [&](auto S) { return launch_slab<E, S.G, S.K, S.WV>(ctx, A, lda, p, slab, M, N, nwg, rows, skip); }));
   hipLaunchKernelGGL(slab_reduce_kernel<E>, dim3((unsigned)((N + 15) / 16)), dim3(ctx->tune.red_threads), 0, ctx->stream, slab, rows, N,
                      v, skip);
   return launch_status(ctx);
@@ -3937,12 +3902,7 @@ static int32_t pipe_iteration_typed(rls_ctx* ctx, const rls_cgnr_pipe& P, int wh
   if (!pick_cfg<E>(ctx->tune, P.N, &c)) return rls_fail(ctx, RLS_E_UNSUPPORTED, "cgnr pipeline: N too large");
   const int nwg = (int)fused_nwg<E>(ctx->tune, P.M, P.N);
   const int rows = slab_grid(ctx, c.K, nwg);  // partial rows K_A leaves = its workgroups
-#define RLS_PIPE_CASE(GG, KK, WW) \
-  if (c.G == GG && c.K == KK && c.WV == WW) launch_pipe_a<E, GG, KK, WW>(ctx, P, nwg, rows);
-  if (which & 1) {
-    RLS_FOR_EACH_CFG(RLS_PIPE_CASE)
-  }
-#undef RLS_PIPE_CASE
+  if (which & 1) RLS_TRY(with_cfg(c, [&](auto S) { return launch_pipe_a<E, S.G, S.K, S.WV>(ctx, P, nwg, rows); }));
   if (which & 2)
     hipLaunchKernelGGL(cgnr_pipe_r_kernel<E>, dim3((unsigned)P.ndots, (unsigned)(P.nrhs > 0 ? P.nrhs : 1)),
                        dim3(ctx->tune.red_threads), 0, ctx->stream, (const E*)P.slab, rows, P.N, (E*)P.v, (const E*)P.p0,
@@ -3952,58 +3912,31 @@ static int32_t pipe_iteration_typed(rls_ctx* ctx, const rls_cgnr_pipe& P, int wh
 
 template <typename E>
 static int32_t pipe_finish_typed(rls_ctx* ctx, const rls_cgnr_pipe& P) {
-  const int ept = (int)((P.N + FIN_THREADS - 1) / FIN_THREADS);
-#define RLS_FIN_CASE(EE)                                                                                         \
-  hipLaunchKernelGGL((cgnr_pipe_f_kernel<E, EE>), dim3((unsigned)(P.nrhs > 0 ? P.nrhs : 1)), dim3(FIN_THREADS), 0, \
-                     ctx->stream, (E*)P.x, (E*)P.r0, (E*)P.p0, (E*)P.r1, (E*)P.p1, (const E*)P.v, P.dots, P.ndots, P.sc, \
-                     P.N, rhs_of(P, 0), P.mb)
-  if (ept <= 1) RLS_FIN_CASE(1);
-  else if (ept <= 2) RLS_FIN_CASE(2);
-  else RLS_FIN_CASE(4);
-#undef RLS_FIN_CASE
-  return launch_status(ctx);
+  return with_ept(P.N, [&](auto EPT) {
+    return rls_launch<cgnr_pipe_f_kernel<E, EPT>>(ctx, dim3((unsigned)(P.nrhs > 0 ? P.nrhs : 1)), dim3(FIN_THREADS), 0, (E*)P.x,
+                                                  (E*)P.r0, (E*)P.p0, (E*)P.r1, (E*)P.p1, (const E*)P.v, P.dots, P.ndots, P.sc, P.N,
+                                                  rhs_of(P, 0), P.mb);
+  });
 }
 
 template <typename E, int G, int K, int WV>
-static void launch_fista_a(rls_ctx* ctx, const rls_fista_pipe& P, int nwg, int grid) {
+static int32_t launch_fista_a(rls_ctx* ctx, const rls_fista_pipe& P, int nwg, int grid) {
   using C = slab_cfg<E, G, K, WV>;
   const int64_t Mc = P.M / C::NV;
   const int pair = slab_pairing(G, nwg);
   constexpr size_t lds = sizeof(slab_lds<E, G, K, WV>);
-  static rls_device_once attr_once;
-  if (auto once_ = attr_once.first(ctx->device)) {
-    allow_big_lds(&fista_pipe_a_kernel<E, G, K, WV, true, false>, lds);
-    allow_big_lds(&fista_pipe_a_kernel<E, G, K, WV, false, false>, lds);
-    allow_big_lds(&fista_pipe_a_kernel<E, G, K, WV, true, true>, lds);
-    allow_big_lds(&fista_pipe_a_kernel<E, G, K, WV, false, true>, lds);
-    if constexpr (K == 32) {
-      allow_big_lds(&fista_pipe_a_kernel<E, G, K, WV, true, false, true>, lds);
-      allow_big_lds(&fista_pipe_a_kernel<E, G, K, WV, false, false, true>, lds);
-      allow_big_lds(&fista_pipe_a_kernel<E, G, K, WV, true, true, true>, lds);
-      allow_big_lds(&fista_pipe_a_kernel<E, G, K, WV, false, true, true>, lds);
-    }
-  }
-  const bool full = P.N == C::NMAX && (int64_t)nwg * G == Mc;
-#define RLS_LAUNCH_FA2(FULLV, HINTV, MULTIV)                                                                              \
-  hipLaunchKernelGGL((fista_pipe_a_kernel<E, G, K, WV, FULLV, HINTV, MULTIV>), dim3(MULTIV ? grid : nwg), dim3(C::NT), lds,   \
-                     ctx->stream, (const E*)P.A, P.lda, (E*)P.b0, (E*)P.b1, (const E*)P.x0, (E*)P.res, (E*)P.y0, (E*)P.y1, \
-                     (const E*)P.res_raw, (E*)P.slab, P.sc, P.scn, Mc, P.N, pair, P.par_hint, nwg)
-#define RLS_LAUNCH_FA(FULLV, HINTV)                 \
-  do {                                              \
-    if constexpr (K == 32) {                        \
-      if (grid < nwg) {                             \
-        RLS_LAUNCH_FA2(FULLV, HINTV, true);         \
-        break;                                      \
-      }                                             \
-    }                                               \
-    RLS_LAUNCH_FA2(FULLV, HINTV, false);            \
-  } while (0)
-  if (full && P.par_hint >= 0) RLS_LAUNCH_FA(true, true);
-  else if (P.par_hint >= 0) RLS_LAUNCH_FA(false, true);
-  else if (full) RLS_LAUNCH_FA(true, false);
-  else RLS_LAUNCH_FA(false, false);
-#undef RLS_LAUNCH_FA
-#undef RLS_LAUNCH_FA2
+  return with_bool(slab_full<E, G, K, WV>(P.M, P.N, nwg), [&](auto FULL) {
+    return with_bool(P.par_hint >= 0, [&](auto HINT) {
+      return with_bool(K == 32 && grid < nwg, [&](auto MULTI) {
+        if constexpr (MULTI && K != 32)
+          return not_instantiated(ctx);
+        else
+          return rls_launch<fista_pipe_a_kernel<E, G, K, WV, FULL, HINT, MULTI>>(
+              ctx, dim3(MULTI ? grid : nwg), dim3(C::NT), lds, (const E*)P.A, P.lda, (E*)P.b0, (E*)P.b1, (const E*)P.x0, (E*)P.res,
+              (E*)P.y0, (E*)P.y1, (const E*)P.res_raw, (E*)P.slab, P.sc, P.scn, Mc, P.N, pair, P.par_hint, nwg);
+      });
+    });
+  });
 }
 
 template <typename E>
@@ -4012,10 +3945,7 @@ static int32_t fista_iteration_typed(rls_ctx* ctx, const rls_fista_pipe& P) {
   if (!pick_cfg<E>(ctx->tune, P.N, &c)) return rls_fail(ctx, RLS_E_UNSUPPORTED, "fista pipeline: N too large");
   const int nwg = (int)fused_nwg<E>(ctx->tune, P.M, P.N);
   const int rows = slab_grid(ctx, c.K, nwg);
-#define RLS_FISTA_CASE(GG, KK, WW) \
-  if (c.G == GG && c.K == KK && c.WV == WW) launch_fista_a<E, GG, KK, WW>(ctx, P, nwg, rows);
-  RLS_FOR_EACH_CFG(RLS_FISTA_CASE)
-#undef RLS_FISTA_CASE
+  RLS_TRY(with_cfg(c, [&](auto S) { return launch_fista_a<E, S.G, S.K, S.WV>(ctx, P, nwg, rows); }));
   hipLaunchKernelGGL(fista_pipe_r_kernel<E>, dim3((unsigned)((P.N + 15) / 16)), dim3(ctx->tune.red_threads), 0, ctx->stream,
                      (const E*)P.slab, rows, P.N, (E*)P.res_raw, P.sc, P.scn);
   return launch_status(ctx);
@@ -4023,15 +3953,10 @@ static int32_t fista_iteration_typed(rls_ctx* ctx, const rls_fista_pipe& P) {
 
 template <typename E>
 static int32_t fista_finish_typed(rls_ctx* ctx, const rls_fista_pipe& P) {
-  const int ept = (int)((P.N + FIN_THREADS - 1) / FIN_THREADS);
-#define RLS_FFIN_CASE(EE)                                                                                        \
-  hipLaunchKernelGGL((fista_pipe_f_kernel<E, EE>), dim3(1), dim3(FIN_THREADS), 0, ctx->stream, (E*)P.b0, (E*)P.b1, \
-                     (const E*)P.x0, (E*)P.res, (E*)P.y0, (E*)P.y1, (const E*)P.res_raw, P.sc, P.N, P.mb)
-  if (ept <= 1) RLS_FFIN_CASE(1);
-  else if (ept <= 2) RLS_FFIN_CASE(2);
-  else RLS_FFIN_CASE(4);
-#undef RLS_FFIN_CASE
-  return launch_status(ctx);
+  return with_ept(P.N, [&](auto EPT) {
+    return rls_launch<fista_pipe_f_kernel<E, EPT>>(ctx, dim3(1), dim3(FIN_THREADS), 0, (E*)P.b0, (E*)P.b1, (const E*)P.x0,
+                                                   (E*)P.res, (E*)P.y0, (E*)P.y1, (const E*)P.res_raw, P.sc, P.N, P.mb);
+  });
 }
 
 // ---- Gram pipeline host side -------------------------------------------------------------------
@@ -4053,33 +3978,30 @@ static int gram_grid(rls_ctx* ctx, int K, int nwg) {
   return elem<E>::cplx ? slab_grid(ctx, K, nwg) : nwg;
 }
 
+// the Gram pipeline's MULTI instantiations: ComplexF32 K = 32 only (Float32: N <= 4096 is at most 256 blocks of 16 rows --
+// nothing to walk, the instantiations would be dead code)
 template <typename E, int K>
-static void launch_gram(rls_ctx* ctx, const rls_gram_pipe& P, int q, int nwg) {
+constexpr bool gram_walks() {
+  return K == 32 && elem<E>::cplx;
+}
+
+template <typename E, int K>
+static int32_t launch_gram(rls_ctx* ctx, const rls_gram_pipe& P, int q, int nwg) {
   using C = slab_cfg<E, 4, K, 8>;
   const int64_t Mc = P.N / C::NV;
   const int pair = slab_pairing(4, nwg);
-  const bool full = P.N == C::NMAX && (int64_t)nwg * 4 == Mc;
   const int grid = gram_grid<E>(ctx, K, nwg);
-#define RLS_LAUNCH_G2(FULLV, MULTIV)                                                                                         \
-  hipLaunchKernelGGL((cgnr_gram_kernel<E, 4, K, 8, FULLV, MULTIV>), dim3(MULTIV ? grid : nwg), dim3(C::NT), 0, ctx->stream,   \
-                     (const E*)P.G, P.ldg, (E*)P.x, (const E*)P.r[q], (const E*)P.p[q], (E*)P.r[q ^ 1], (E*)P.p[q ^ 1],        \
-                     (const E*)P.v[q], (E*)P.v[q ^ 1], P.dots + (size_t)q * 4 * nwg, P.dots + (size_t)(q ^ 1) * 4 * nwg,       \
-                     MULTIV ? grid : nwg, P.sc[q], P.sc[q ^ 1], Mc, P.N, pair, ctx->tune.slab_order, nwg)
-  // (Float32: N <= 4096 is at most 256 blocks of 16 rows -- nothing to walk, the instantiations would be dead code)
-#define RLS_LAUNCH_G(FULLV)               \
-  do {                                    \
-    if constexpr (K == 32 && elem<E>::cplx) { \
-      if (grid < nwg) {                   \
-        RLS_LAUNCH_G2(FULLV, true);       \
-        break;                            \
-      }                                   \
-    }                                     \
-    RLS_LAUNCH_G2(FULLV, false);          \
-  } while (0)
-  if (full) RLS_LAUNCH_G(true);
-  else RLS_LAUNCH_G(false);
-#undef RLS_LAUNCH_G
-#undef RLS_LAUNCH_G2
+  return with_bool(slab_full<E, 4, K, 8>(P.N, P.N, nwg), [&](auto FULL) {
+    return with_bool(gram_walks<E, K>() && grid < nwg, [&](auto MULTI) {
+      if constexpr (MULTI && !gram_walks<E, K>())
+        return not_instantiated(ctx);
+      else
+        return rls_launch<cgnr_gram_kernel<E, 4, K, 8, FULL, MULTI>>(
+            ctx, dim3(MULTI ? grid : nwg), dim3(C::NT), 0, (const E*)P.G, P.ldg, (E*)P.x, (const E*)P.r[q], (const E*)P.p[q],
+            (E*)P.r[q ^ 1], (E*)P.p[q ^ 1], (const E*)P.v[q], (E*)P.v[q ^ 1], P.dots + (size_t)q * 4 * nwg,
+            P.dots + (size_t)(q ^ 1) * 4 * nwg, MULTI ? grid : nwg, P.sc[q], P.sc[q ^ 1], Mc, P.N, pair, ctx->tune.slab_order, nwg);
+    });
+  });
 }
 
 template <typename E>
@@ -4087,10 +4009,7 @@ static int32_t gram_iteration_typed(rls_ctx* ctx, const rls_gram_pipe& P, int q)
   int K = 0;
   if (!gram_pick<E>(P.N, &K)) return rls_fail(ctx, RLS_E_UNSUPPORTED, "gram pipeline: N too large");
   const int nwg = rls_gram_pipe_nwg(elem<E>::cplx ? RLS_C32 : RLS_F32, P.N);
-  if (K == 8) launch_gram<E, 8>(ctx, P, q, nwg);
-  else if (K == 16) launch_gram<E, 16>(ctx, P, q, nwg);
-  else launch_gram<E, 32>(ctx, P, q, nwg);
-  return launch_status(ctx);
+  return rls_with<8, 16, 32>(K, [&](auto KC) { return launch_gram<E, KC>(ctx, P, q, nwg); });
 }
 
 template <typename E>
@@ -4099,45 +4018,31 @@ static int32_t gram_finish_typed(rls_ctx* ctx, const rls_gram_pipe& P, int q) {
   int Kp = 0;
   gram_pick<E>(P.N, &Kp);
   const int ndots = gram_grid<E>(ctx, Kp, nwg);  // what the last iteration's launch left (launch_gram)
-  const int ept = (int)((P.N + FIN_THREADS - 1) / FIN_THREADS);
-#define RLS_GFIN_CASE(EE)                                                                                           \
-  hipLaunchKernelGGL((cgnr_gram_f_kernel<E, EE>), dim3(1), dim3(FIN_THREADS), 0, ctx->stream, (E*)P.x,               \
-                     (const E*)P.r[q], (const E*)P.p[q], (E*)P.r[0], (E*)P.p[0], (const E*)P.v[q], (E*)P.v[0],       \
-                     P.dots + (size_t)q * 4 * nwg, ndots, P.sc[q], P.sc[0], P.sc[1], P.N)
-  if (ept <= 1) RLS_GFIN_CASE(1);
-  else if (ept <= 2) RLS_GFIN_CASE(2);
-  else RLS_GFIN_CASE(4);
-#undef RLS_GFIN_CASE
-  return launch_status(ctx);
+  return with_ept(P.N, [&](auto EPT) {
+    return rls_launch<cgnr_gram_f_kernel<E, EPT>>(ctx, dim3(1), dim3(FIN_THREADS), 0, (E*)P.x, (const E*)P.r[q], (const E*)P.p[q],
+                                                  (E*)P.r[0], (E*)P.p[0], (const E*)P.v[q], (E*)P.v[0], P.dots + (size_t)q * 4 * nwg,
+                                                  ndots, P.sc[q], P.sc[0], P.sc[1], P.N);
+  });
 }
 
 template <typename E, int K>
-static void launch_fista_gram(rls_ctx* ctx, const rls_fista_gram& P, int q, int nwg) {
+static int32_t launch_fista_gram(rls_ctx* ctx, const rls_fista_gram& P, int q, int nwg) {
   using C = slab_cfg<E, 4, K, 8>;
   const int64_t Mc = P.N / C::NV;
   const int pair = slab_pairing(4, nwg);
-  const bool full = P.N == C::NMAX && (int64_t)nwg * 4 == Mc;
   const int grid = gram_grid<E>(ctx, K, nwg);
-#define RLS_LAUNCH_FG2(FULLV, HINTV, MULTIV)                                                                                  \
-  hipLaunchKernelGGL((fista_gram_kernel<E, 4, K, 8, FULLV, HINTV, MULTIV>), dim3(MULTIV ? grid : nwg), dim3(C::NT), 0,         \
-                     ctx->stream, (const E*)P.G, P.ldg, (E*)P.b0, (E*)P.b1, (const E*)P.x0, (E*)P.res, (E*)P.y0, (E*)P.y1,    \
-                     (const E*)P.rr[q], (E*)P.rr[q ^ 1], P.sc[q], P.sc[q ^ 1], Mc, P.N, pair, P.par_hint, nwg)
-#define RLS_LAUNCH_FG(FULLV, HINTV)             \
-  do {                                          \
-    if constexpr (K == 32 && elem<E>::cplx) {   \
-      if (grid < nwg) {                         \
-        RLS_LAUNCH_FG2(FULLV, HINTV, true);     \
-        break;                                  \
-      }                                         \
-    }                                           \
-    RLS_LAUNCH_FG2(FULLV, HINTV, false);        \
-  } while (0)
-  if (full && P.par_hint >= 0) RLS_LAUNCH_FG(true, true);
-  else if (P.par_hint >= 0) RLS_LAUNCH_FG(false, true);
-  else if (full) RLS_LAUNCH_FG(true, false);
-  else RLS_LAUNCH_FG(false, false);
-#undef RLS_LAUNCH_FG
-#undef RLS_LAUNCH_FG2
+  return with_bool(slab_full<E, 4, K, 8>(P.N, P.N, nwg), [&](auto FULL) {
+    return with_bool(P.par_hint >= 0, [&](auto HINT) {
+      return with_bool(gram_walks<E, K>() && grid < nwg, [&](auto MULTI) {
+        if constexpr (MULTI && !gram_walks<E, K>())
+          return not_instantiated(ctx);
+        else
+          return rls_launch<fista_gram_kernel<E, 4, K, 8, FULL, HINT, MULTI>>(
+              ctx, dim3(MULTI ? grid : nwg), dim3(C::NT), 0, (const E*)P.G, P.ldg, (E*)P.b0, (E*)P.b1, (const E*)P.x0, (E*)P.res,
+              (E*)P.y0, (E*)P.y1, (const E*)P.rr[q], (E*)P.rr[q ^ 1], P.sc[q], P.sc[q ^ 1], Mc, P.N, pair, P.par_hint, nwg);
+      });
+    });
+  });
 }
 
 template <typename E>
@@ -4145,23 +4050,15 @@ static int32_t fista_gram_iteration_typed(rls_ctx* ctx, const rls_fista_gram& P,
   int K = 0;
   if (!gram_pick<E>(P.N, &K)) return rls_fail(ctx, RLS_E_UNSUPPORTED, "gram pipeline: N too large");
   const int nwg = rls_gram_pipe_nwg(elem<E>::cplx ? RLS_C32 : RLS_F32, P.N);
-  if (K == 8) launch_fista_gram<E, 8>(ctx, P, q, nwg);
-  else if (K == 16) launch_fista_gram<E, 16>(ctx, P, q, nwg);
-  else launch_fista_gram<E, 32>(ctx, P, q, nwg);
-  return launch_status(ctx);
+  return rls_with<8, 16, 32>(K, [&](auto KC) { return launch_fista_gram<E, KC>(ctx, P, q, nwg); });
 }
 
 template <typename E>
 static int32_t fista_gram_finish_typed(rls_ctx* ctx, const rls_fista_gram& P, int q) {
-  const int ept = (int)((P.N + FIN_THREADS - 1) / FIN_THREADS);
-#define RLS_FGFIN_CASE(EE)                                                                                         \
-  hipLaunchKernelGGL((fista_gram_f_kernel<E, EE>), dim3(1), dim3(FIN_THREADS), 0, ctx->stream, (E*)P.b0, (E*)P.b1,  \
-                     (const E*)P.x0, (E*)P.res, (E*)P.y0, (E*)P.y1, (const E*)P.rr[q], P.sc[q], P.sc[0], P.sc[1], P.N)
-  if (ept <= 1) RLS_FGFIN_CASE(1);
-  else if (ept <= 2) RLS_FGFIN_CASE(2);
-  else RLS_FGFIN_CASE(4);
-#undef RLS_FGFIN_CASE
-  return launch_status(ctx);
+  return with_ept(P.N, [&](auto EPT) {
+    return rls_launch<fista_gram_f_kernel<E, EPT>>(ctx, dim3(1), dim3(FIN_THREADS), 0, (E*)P.b0, (E*)P.b1, (const E*)P.x0,
+                                                   (E*)P.res, (E*)P.y0, (E*)P.y1, (const E*)P.rr[q], P.sc[q], P.sc[0], P.sc[1], P.N);
+  });
 }
 
 
@@ -4177,54 +4074,42 @@ static bool resident_two_level_ok(const rls_tuning& T, int nwg, int64_t N, int n
   return q >= 1 && q <= nt && (q & (q - 1)) == 0;
 }
 
+// slab shapes with a resident CGNR / FISTA instantiation: 16 or 32 columns per row piece, 8 waves, 16-byte ownership pieces
+// (EPT % V == 0); complex with 64-byte row pieces would hold 8 owned elements of x, r, p, v per thread on top of the slab: spills
+template <typename E, int G, int K, int WV>
+constexpr bool resident_shape() {
+  return (K == 32 || K == 16) && WV == 8 && slab_cfg<E, G, K, WV>::EPT % elem<E>::vec == 0 && !(elem<E>::cplx && G == 4);
+}
+// ... and with a resident OptISTA / POGM instantiation: the slab must also re-arrange into the column-owner layout
+template <typename E, int G, int K, int WV>
+constexpr bool pgm_resident_shape() {
+  return resident_shape<E, G, K, WV>() && owner_cfg_ok<E, G, K, WV>();
+}
+
+// the resident kernels pair whole groups of 16 blocks only (slab_pairing also pairs the leading groups of a ragged grid)
+static int resident_pairing(int G, int nwg) { return (G == 4 && nwg % 16 == 0) ? 1 : 0; }
+
 template <typename E, int G, int K, int WV>
 static int32_t launch_resident(rls_ctx* ctx, const rls_cgnr_pipe& P, double* dout, void* sync, int nwg, int n_steps,
                                unsigned spin_limit, const rls_cg_start& St) {
-  using C = slab_cfg<E, G, K, WV>;
-  // (complex with 64-byte row pieces holds 8 owned elements of x, r, p, v per thread on top of the slab: spills)
-  if constexpr ((K == 32 || K == 16) && WV == 8 && C::EPT % C::NV == 0 && !(elem<E>::cplx && G == 4)) {
+  if constexpr (!resident_shape<E, G, K, WV>()) {
+    return rls_fail(ctx, RLS_E_UNSUPPORTED, "resident CGNR: slab shape not instantiated");
+  } else {
+    using C = slab_cfg<E, G, K, WV>;
     const int64_t Mc = P.M / C::NV;
-    const int pair = (G == 4 && nwg % 16 == 0) ? 1 : 0;
-    const bool full = P.N == C::NMAX && (int64_t)nwg * G == Mc;
+    const int pair = resident_pairing(G, nwg);
     constexpr size_t lds = resident_lds_bytes<E, G, K, WV>();
-    static rls_device_once attr_once;
-    if (auto once_ = attr_once.first(ctx->device)) {
-      allow_big_lds(&cgnr_resident_kernel<E, G, K, WV, 1, true>, lds);
-      allow_big_lds(&cgnr_resident_kernel<E, G, K, WV, 2, true>, lds);
-      allow_big_lds(&cgnr_resident_kernel<E, G, K, WV, 1, false>, lds);
-      allow_big_lds(&cgnr_resident_kernel<E, G, K, WV, 2, false>, lds);
-      allow_big_lds(&cgnr_resident_kernel<E, G, K, WV, 1, true, true>, lds);
-      allow_big_lds(&cgnr_resident_kernel<E, G, K, WV, 2, true, true>, lds);
-      allow_big_lds(&cgnr_resident_kernel<E, G, K, WV, 1, false, true>, lds);
-      allow_big_lds(&cgnr_resident_kernel<E, G, K, WV, 2, false, true>, lds);
-      }
-#define RLS_LAUNCH_RES(BB, FF, SS)                                                                                      \
-  hipLaunchKernelGGL((cgnr_resident_kernel<E, G, K, WV, BB, FF, SS>), dim3(nwg), dim3(C::NT), lds, ctx->stream, (const E*)P.A, \
-                     P.lda, (E*)P.x, (E*)P.r1, (E*)P.r0, (E*)P.p0, (E*)P.v, (E*)P.slab, dout, P.sc, (resident_sync*)sync, Mc, P.N,  \
-                     pair, n_steps, spin_limit, St)
     // a kernel that stays and listens runs one iteration ahead of its commands (SPEC) unless the context says otherwise
     const bool spec = St.srv_ctl != nullptr && ctx->tune.resident_ahead != 0;
-    if (resident_two_level_ok<E>(ctx->tune, nwg, P.N, C::NT)) {
-      if (spec) {
-        if (full) RLS_LAUNCH_RES(2, true, true);
-        else RLS_LAUNCH_RES(2, false, true);
-      } else {
-        if (full) RLS_LAUNCH_RES(2, true, false);
-        else RLS_LAUNCH_RES(2, false, false);
-      }
-    } else {
-      if (spec) {
-        if (full) RLS_LAUNCH_RES(1, true, true);
-        else RLS_LAUNCH_RES(1, false, true);
-      } else {
-        if (full) RLS_LAUNCH_RES(1, true, false);
-        else RLS_LAUNCH_RES(1, false, false);
-      }
-    }
-#undef RLS_LAUNCH_RES
-    return launch_status(ctx);
-  } else {
-    return rls_fail(ctx, RLS_E_UNSUPPORTED, "resident CGNR: slab shape not instantiated");
+    return with_bool(resident_two_level_ok<E>(ctx->tune, nwg, P.N, C::NT), [&](auto TWO) {
+      return with_bool(slab_full<E, G, K, WV>(P.M, P.N, nwg), [&](auto FULL) {
+        return with_bool(spec, [&](auto SPEC) {
+          return rls_launch<cgnr_resident_kernel<E, G, K, WV, TWO ? 2 : 1, FULL, SPEC>>(
+              ctx, dim3(nwg), dim3(C::NT), lds, (const E*)P.A, P.lda, (E*)P.x, (E*)P.r1, (E*)P.r0, (E*)P.p0, (E*)P.v, (E*)P.slab,
+              dout, P.sc, (resident_sync*)sync, Mc, P.N, pair, n_steps, spin_limit, St);
+        });
+      });
+    });
   }
 }
 
@@ -4232,34 +4117,26 @@ template <typename E>
 static bool resident_ok_typed(const rls_tuning& T, int device, int64_t M, int64_t N, const void* A, int64_t lda) {
   if (!fused_ok<E>(T, M, N, A, lda)) return false;
   fused_cfg c;
-  if (!pick_cfg<E>(T, N, &c) || (c.K != 32 && c.K != 16) || c.WV != 8 || (elem<E>::cplx && c.G == 4)) return false;
-  if (((int64_t)c.K * c.WV * (64 / c.G) / (c.WV * 64)) % elem<E>::vec) return false;  // 16-byte ownership pieces: EPT % V == 0
-  // the K = 32 slab shapes: N in (NMAX / 2, NMAX], N a multiple of the 16-byte piece; ragged M and N run the masked
-  // instantiation (the full-size one has no clamps at all)
-  const int64_t nwg = fused_nwg<E>(T, M, N);
-  if (N % elem<E>::vec) return false;
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return false;
-  // one 512-thread workgroup (256 VGPRs per lane, ~148 KiB of LDS) per CU: the grid is resident iff it fits the CUs;
-  // the arrival words of the barrier (resident_sync::cnt, per-workgroup flags in mode 0) hold 256 workgroups
-  if (!(nwg <= cus && nwg <= 256 && nwg * N * (int64_t)sizeof(E) < (int64_t)0xffffffffll)) return false;
-  // ... and the runtime must agree that a workgroup of this instantiation fits a CU at all (the occupancy query is
-  // advisory upwards -- it can over-report by one -- but "0" is a firm no: e.g. a device with less LDS per CU)
-  int blocks = 0;
-#define RLS_OCC_CASE(GG, KK, WW)                                                                                        \
-  if (c.G == GG && c.K == KK && c.WV == WW) {                                                                            \
-    if constexpr ((KK == 32 || KK == 16) && WW == 8 && slab_cfg<E, GG, KK, WW>::EPT % elem<E>::vec == 0 &&               \
-                  !(elem<E>::cplx && GG == 4)) {                                                                         \
-      allow_big_lds(&cgnr_resident_kernel<E, GG, KK, WW, 1, false>, resident_lds_bytes<E, GG, KK, WW>());                \
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, cgnr_resident_kernel<E, GG, KK, WW, 1, false>, WW * 64,  \
-                                                       resident_lds_bytes<E, GG, KK, WW>()) != hipSuccess)               \
-        blocks = 0;                                                                                                      \
-    }                                                                                                                    \
-  }
-  RLS_FOR_EACH_CFG(RLS_OCC_CASE)
-#undef RLS_OCC_CASE
-  (void)hipGetLastError();
-  return blocks >= 1;
+  if (!pick_cfg<E>(T, N, &c)) return false;
+  return with_cfg(c, [&](auto S) {
+    if constexpr (!resident_shape<E, S.G, S.K, S.WV>()) {
+      return false;
+    } else {
+      // the K = 32 slab shapes: N in (NMAX / 2, NMAX], N a multiple of the 16-byte piece; ragged M and N run the masked
+      // instantiation (the full-size one has no clamps at all)
+      const int64_t nwg = fused_nwg<E>(T, M, N);
+      if (N % elem<E>::vec) return false;
+      int cus = 0;
+      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return false;
+      // one 512-thread workgroup (256 VGPRs per lane, ~148 KiB of LDS) per CU: the grid is resident iff it fits the CUs;
+      // the arrival words of the barrier (resident_sync::cnt, per-workgroup flags in mode 0) hold 256 workgroups
+      if (!(nwg <= cus && nwg <= 256 && nwg * N * (int64_t)sizeof(E) < (int64_t)0xffffffffll)) return false;
+      // ... and the runtime must agree that a workgroup of this instantiation fits a CU at all (the occupancy query is
+      // advisory upwards -- it can over-report by one -- but "0" is a firm no: e.g. a device with less LDS per CU)
+      return rls_occupancy<cgnr_resident_kernel<E, S.G, S.K, S.WV, 1, false>>(device, S.WV * 64,
+                                                                              resident_lds_bytes<E, S.G, S.K, S.WV>()) >= 1;
+    }
+  });
 }
 
 template <typename E>
@@ -4268,60 +4145,32 @@ static int32_t resident_typed(rls_ctx* ctx, const rls_cgnr_pipe& P, double* dout
   fused_cfg c;
   if (!pick_cfg<E>(ctx->tune, P.N, &c)) return rls_fail(ctx, RLS_E_UNSUPPORTED, "resident CGNR: N too large");
   const int nwg = (int)fused_nwg<E>(ctx->tune, P.M, P.N);
-  int32_t st = RLS_E_UNSUPPORTED;
-#define RLS_RES_CASE(GG, KK, WW) \
-  if (c.G == GG && c.K == KK && c.WV == WW) st = launch_resident<E, GG, KK, WW>(ctx, P, dout, sync, nwg, n_steps, spin_limit, St);
-  RLS_FOR_EACH_CFG(RLS_RES_CASE)
-#undef RLS_RES_CASE
-  return st;
+  return with_cfg(c, [&](auto S) {
+    return launch_resident<E, S.G, S.K, S.WV>(ctx, P, dout, sync, nwg, n_steps, spin_limit, St);
+  });
 }
 
 template <typename E, int G, int K, int WV>
 static int32_t launch_fista_resident(rls_ctx* ctx, const rls_fista_pipe& P, void* sync, int nwg, int n_steps,
                                      unsigned spin_limit, const rls_srv_args& Sv) {
-  using C = slab_cfg<E, G, K, WV>;
-  if constexpr ((K == 32 || K == 16) && WV == 8 && C::EPT % C::NV == 0 && !(elem<E>::cplx && G == 4)) {
-    const int64_t Mc = P.M / C::NV;
-    const int pair = (G == 4 && nwg % 16 == 0) ? 1 : 0;
-    const bool full = P.N == C::NMAX && (int64_t)nwg * G == Mc;
-    constexpr size_t lds = resident_lds_bytes<E, G, K, WV>();
-    static rls_device_once attr_once;
-    if (auto once_ = attr_once.first(ctx->device)) {
-      allow_big_lds(&fista_resident_kernel<E, G, K, WV, 1, true>, lds);
-      allow_big_lds(&fista_resident_kernel<E, G, K, WV, 2, true>, lds);
-      allow_big_lds(&fista_resident_kernel<E, G, K, WV, 1, false>, lds);
-      allow_big_lds(&fista_resident_kernel<E, G, K, WV, 2, false>, lds);
-      allow_big_lds(&fista_resident_kernel<E, G, K, WV, 1, true, true>, lds);
-      allow_big_lds(&fista_resident_kernel<E, G, K, WV, 2, true, true>, lds);
-      allow_big_lds(&fista_resident_kernel<E, G, K, WV, 1, false, true>, lds);
-      allow_big_lds(&fista_resident_kernel<E, G, K, WV, 2, false, true>, lds);
-      }
-#define RLS_LAUNCH_FRES(BB, FF, SS)                                                                                      \
-  hipLaunchKernelGGL((fista_resident_kernel<E, G, K, WV, BB, FF, SS>), dim3(nwg), dim3(C::NT), lds, ctx->stream, (const E*)P.A, \
-                     P.lda, (E*)P.b0, (E*)P.b1, (const E*)P.x0, (E*)P.res, (E*)P.y0, (E*)P.y1, (E*)P.res_raw, (E*)P.slab,  \
-                     P.sc, (resident_sync*)sync, Mc, P.N, pair | (ctx->tune.fista_defer ? 0 : 2), n_steps, spin_limit, Sv)
-    const bool spec = Sv.ctl != nullptr && ctx->tune.resident_ahead != 0;  // a kernel that stays and listens runs one iteration ahead of its commands
-    if (resident_two_level_ok<E>(ctx->tune, nwg, P.N, C::NT)) {
-      if (spec) {
-        if (full) RLS_LAUNCH_FRES(2, true, true);
-        else RLS_LAUNCH_FRES(2, false, true);
-      } else {
-        if (full) RLS_LAUNCH_FRES(2, true, false);
-        else RLS_LAUNCH_FRES(2, false, false);
-      }
-    } else {
-      if (spec) {
-        if (full) RLS_LAUNCH_FRES(1, true, true);
-        else RLS_LAUNCH_FRES(1, false, true);
-      } else {
-        if (full) RLS_LAUNCH_FRES(1, true, false);
-        else RLS_LAUNCH_FRES(1, false, false);
-      }
-    }
-#undef RLS_LAUNCH_FRES
-    return launch_status(ctx);
-  } else {
+  if constexpr (!resident_shape<E, G, K, WV>()) {
     return rls_fail(ctx, RLS_E_UNSUPPORTED, "resident FISTA: slab shape not instantiated");
+  } else {
+    using C = slab_cfg<E, G, K, WV>;
+    const int64_t Mc = P.M / C::NV;
+    const int pair = resident_pairing(G, nwg);
+    constexpr size_t lds = resident_lds_bytes<E, G, K, WV>();
+    const bool spec = Sv.ctl != nullptr && ctx->tune.resident_ahead != 0;  // a kernel that stays and listens runs one iteration ahead of its commands
+    return with_bool(resident_two_level_ok<E>(ctx->tune, nwg, P.N, C::NT), [&](auto TWO) {
+      return with_bool(slab_full<E, G, K, WV>(P.M, P.N, nwg), [&](auto FULL) {
+        return with_bool(spec, [&](auto SPEC) {
+          return rls_launch<fista_resident_kernel<E, G, K, WV, TWO ? 2 : 1, FULL, SPEC>>(
+              ctx, dim3(nwg), dim3(C::NT), lds, (const E*)P.A, P.lda, (E*)P.b0, (E*)P.b1, (const E*)P.x0, (E*)P.res, (E*)P.y0,
+              (E*)P.y1, (E*)P.res_raw, (E*)P.slab, P.sc, (resident_sync*)sync, Mc, P.N, pair | (ctx->tune.fista_defer ? 0 : 2),
+              n_steps, spin_limit, Sv);
+        });
+      });
+    });
   }
 }
 
@@ -4331,47 +4180,30 @@ static int32_t fista_resident_typed(rls_ctx* ctx, const rls_fista_pipe& P, void*
   fused_cfg c;
   if (!pick_cfg<E>(ctx->tune, P.N, &c)) return rls_fail(ctx, RLS_E_UNSUPPORTED, "resident FISTA: N too large");
   const int nwg = (int)fused_nwg<E>(ctx->tune, P.M, P.N);
-  int32_t st = RLS_E_UNSUPPORTED;
-#define RLS_FRES_CASE(GG, KK, WW) \
-  if (c.G == GG && c.K == KK && c.WV == WW) st = launch_fista_resident<E, GG, KK, WW>(ctx, P, sync, nwg, n_steps, spin_limit, Sv);
-  RLS_FOR_EACH_CFG(RLS_FRES_CASE)
-#undef RLS_FRES_CASE
-  return st;
+  return with_cfg(c, [&](auto S) {
+    return launch_fista_resident<E, S.G, S.K, S.WV>(ctx, P, sync, nwg, n_steps, spin_limit, Sv);
+  });
 }
+
+// SRV of the resident Gram kernels: 0 one pass, 1 stays and listens, 2 ... and runs one iteration ahead of its commands
+static int gram_srv_mode(const rls_ctx* ctx, bool listens) { return !listens ? 0 : ctx->tune.resident_ahead ? 2 : 1; }
+
 template <typename E, int K>
 static int32_t launch_gram_resident(rls_ctx* ctx, const rls_gram_pipe& P, void* sync, int nwg, int n_steps,
                                     unsigned spin_limit, const rls_cg_start& St) {
   using C = slab_cfg<E, 4, K, 8>;
   const int64_t Mc = P.N / C::NV;
-  const int pair = (nwg % 16 == 0) ? 1 : 0;
-  const bool full = P.N == C::NMAX && (int64_t)nwg * 4 == Mc;
-#define RLS_LAUNCH_GR(BB, FF)                                                                                          \
-  hipLaunchKernelGGL((cgnr_gram_resident_kernel<E, K, BB, FF>), dim3(nwg), dim3(C::NT), 0, ctx->stream, (const E*)P.G,  \
-                     P.ldg, (E*)P.x, (E*)P.r[0], (E*)P.p[0], (E*)P.v[0], (E*)P.v[1], P.dots, P.sc[0], P.sc[1],         \
-                     (resident_sync*)sync, Mc, P.N, pair, n_steps, spin_limit, St)
-  if constexpr (K != 32) {
-    if (St.srv_ctl) {  // the instantiation that can stay and listen
-#define RLS_LAUNCH_GRS(FF, SS)                                                                                            \
-  hipLaunchKernelGGL((cgnr_gram_resident_kernel<E, K, 1, FF, SS>), dim3(nwg), dim3(C::NT), 0, ctx->stream, (const E*)P.G, \
-                     P.ldg, (E*)P.x, (E*)P.r[0], (E*)P.p[0], (E*)P.v[0], (E*)P.v[1], P.dots, P.sc[0], P.sc[1],            \
-                     (resident_sync*)sync, Mc, P.N, pair, n_steps, spin_limit, St)
-      if (ctx->tune.resident_ahead) {  // one iteration ahead of its commands
-        if (full) RLS_LAUNCH_GRS(true, 2);
-        else RLS_LAUNCH_GRS(false, 2);
-      } else {
-        if (full) RLS_LAUNCH_GRS(true, 1);
-        else RLS_LAUNCH_GRS(false, 1);
-      }
-#undef RLS_LAUNCH_GRS
-      return launch_status(ctx);
-    }
-  } else if (St.srv_ctl) {
-    return rls_fail(ctx, RLS_E_UNSUPPORTED, "resident Gram CGNR: no listening instantiation for this shape");
-  }
-  if (full) RLS_LAUNCH_GR(1, true);
-  else RLS_LAUNCH_GR(1, false);
-#undef RLS_LAUNCH_GR
-  return launch_status(ctx);
+  const int pair = resident_pairing(4, nwg);
+  return with_bool(slab_full<E, 4, K, 8>(P.N, P.N, nwg), [&](auto FULL) {
+    return rls_with<0, 1, 2>(gram_srv_mode(ctx, St.srv_ctl != nullptr), [&](auto SRV) {
+      if constexpr (K == 32 && SRV != 0)
+        return rls_fail(ctx, RLS_E_UNSUPPORTED, "resident Gram CGNR: no listening instantiation for this shape");
+      else
+        return rls_launch<cgnr_gram_resident_kernel<E, K, 1, FULL, SRV>>(
+            ctx, dim3(nwg), dim3(C::NT), 0, (const E*)P.G, P.ldg, (E*)P.x, (E*)P.r[0], (E*)P.p[0], (E*)P.v[0], (E*)P.v[1], P.dots,
+            P.sc[0], P.sc[1], (resident_sync*)sync, Mc, P.N, pair, n_steps, spin_limit, St);
+    });
+  });
 }
 
 // every Gram-pipeline shape whose workgroups (8 / 16 rows of AHA each) fit the CUs at one per CU: N <= 2048 CF32,
@@ -4384,14 +4216,12 @@ static bool gram_resident_ok_typed(int device, int64_t N) {
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return false;
   if (!(nwg <= cus && nwg <= 256)) return false;
-  int blocks = 0;
-  hipError_t e = hipSuccess;
-  if (K == 8) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, cgnr_gram_resident_kernel<E, 8, 1, false>, 512, 0);
-  else if (K == 16) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, cgnr_gram_resident_kernel<E, 16, 1, false>, 512, 0);
-  else if constexpr (!elem<E>::cplx)  // complex K = 32 would be N > 2048: more than 256 workgroups, never resident
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, cgnr_gram_resident_kernel<E, 32, 1, false>, 512, 0);
-  (void)hipGetLastError();
-  return e == hipSuccess && blocks >= 1;
+  return rls_with<8, 16, 32>(K, [&](auto KC) {
+    if constexpr (elem<E>::cplx && KC == 32)  // complex K = 32 would be N > 2048: more than 256 workgroups, never resident
+      return false;
+    else
+      return rls_occupancy<cgnr_gram_resident_kernel<E, KC, 1, false>>(device, 512, 0) >= 1;
+  });
 }
 
 template <typename E>
@@ -4400,40 +4230,31 @@ static int32_t gram_resident_typed(rls_ctx* ctx, const rls_gram_pipe& P, void* s
   int K = 0;
   if (!gram_pick<E>(P.N, &K)) return rls_fail(ctx, RLS_E_UNSUPPORTED, "resident Gram CGNR: N too large");
   const int nwg = rls_gram_pipe_nwg(elem<E>::cplx ? RLS_C32 : RLS_F32, P.N);
-  if (K == 8) return launch_gram_resident<E, 8>(ctx, P, sync, nwg, n_steps, spin_limit, St);
-  if (K == 16) return launch_gram_resident<E, 16>(ctx, P, sync, nwg, n_steps, spin_limit, St);
-  if constexpr (!elem<E>::cplx) return launch_gram_resident<E, 32>(ctx, P, sync, nwg, n_steps, spin_limit, St);
-  return rls_fail(ctx, RLS_E_UNSUPPORTED, "resident Gram CGNR: shape not resident");
+  return rls_with<8, 16, 32>(K, [&](auto KC) {
+    if constexpr (elem<E>::cplx && KC == 32)
+      return rls_fail(ctx, RLS_E_UNSUPPORTED, "resident Gram CGNR: shape not resident");
+    else
+      return launch_gram_resident<E, KC>(ctx, P, sync, nwg, n_steps, spin_limit, St);
+  });
 }
+
 template <typename E, int K>
 static int32_t launch_fista_gram_resident(rls_ctx* ctx, const rls_fista_gram& P, void* sync, int nwg, int n_steps,
                                           unsigned spin_limit, const rls_srv_args& Sv) {
   using C = slab_cfg<E, 4, K, 8>;
   const int64_t Mc = P.N / C::NV;
-  const int pair = (nwg % 16 == 0) ? 1 : 0;
-  const bool full = P.N == C::NMAX && (int64_t)nwg * 4 == Mc;
-#define RLS_LAUNCH_FGR(BB, FF, SS)                                                                                         \
-  hipLaunchKernelGGL((fista_gram_resident_kernel<E, K, BB, FF, SS>), dim3(nwg), dim3(C::NT), 0, ctx->stream, (const E*)P.G, \
-                     P.ldg, (E*)P.b0, (E*)P.b1, (const E*)P.x0, (E*)P.res, (E*)P.y0, (E*)P.y1, (E*)P.rr[0], (E*)P.rr[1], \
-                     P.sc[0], P.sc[1], (resident_sync*)sync, Mc, P.N, pair, n_steps, spin_limit, Sv)
-  if constexpr (K != 32) {
-    if (Sv.ctl) {  // the listening instantiation (the host asks rls_gram_resident_server_ok first)
-      if (ctx->tune.resident_ahead) {  // one iteration ahead of its commands
-        if (full) RLS_LAUNCH_FGR(1, true, 2);
-        else RLS_LAUNCH_FGR(1, false, 2);
-      } else {
-        if (full) RLS_LAUNCH_FGR(1, true, 1);
-        else RLS_LAUNCH_FGR(1, false, 1);
-      }
-      return launch_status(ctx);
-    }
-  } else if (Sv.ctl) {
-    return rls_fail(ctx, RLS_E_UNSUPPORTED, "resident Gram FISTA: no listening instantiation for this shape");
-  }
-  if (full) RLS_LAUNCH_FGR(1, true, 0);
-  else RLS_LAUNCH_FGR(1, false, 0);
-#undef RLS_LAUNCH_FGR
-  return launch_status(ctx);
+  const int pair = resident_pairing(4, nwg);
+  // (the host asks rls_gram_resident_server_ok before it starts a listening kernel)
+  return with_bool(slab_full<E, 4, K, 8>(P.N, P.N, nwg), [&](auto FULL) {
+    return rls_with<0, 1, 2>(gram_srv_mode(ctx, Sv.ctl != nullptr), [&](auto SRV) {
+      if constexpr (K == 32 && SRV != 0)
+        return rls_fail(ctx, RLS_E_UNSUPPORTED, "resident Gram FISTA: no listening instantiation for this shape");
+      else
+        return rls_launch<fista_gram_resident_kernel<E, K, 1, FULL, SRV>>(
+            ctx, dim3(nwg), dim3(C::NT), 0, (const E*)P.G, P.ldg, (E*)P.b0, (E*)P.b1, (const E*)P.x0, (E*)P.res, (E*)P.y0,
+            (E*)P.y1, (E*)P.rr[0], (E*)P.rr[1], P.sc[0], P.sc[1], (resident_sync*)sync, Mc, P.N, pair, n_steps, spin_limit, Sv);
+    });
+  });
 }
 
 template <typename E>
@@ -4442,47 +4263,34 @@ static int32_t fista_gram_resident_typed(rls_ctx* ctx, const rls_fista_gram& P, 
   int K = 0;
   if (!gram_pick<E>(P.N, &K)) return rls_fail(ctx, RLS_E_UNSUPPORTED, "resident Gram FISTA: N too large");
   const int nwg = rls_gram_pipe_nwg(elem<E>::cplx ? RLS_C32 : RLS_F32, P.N);
-  if (K == 8) return launch_fista_gram_resident<E, 8>(ctx, P, sync, nwg, n_steps, spin_limit, Sv);
-  if (K == 16) return launch_fista_gram_resident<E, 16>(ctx, P, sync, nwg, n_steps, spin_limit, Sv);
-  if constexpr (!elem<E>::cplx) return launch_fista_gram_resident<E, 32>(ctx, P, sync, nwg, n_steps, spin_limit, Sv);
-  return rls_fail(ctx, RLS_E_UNSUPPORTED, "resident Gram FISTA: shape not resident");
+  return rls_with<8, 16, 32>(K, [&](auto KC) {
+    if constexpr (elem<E>::cplx && KC == 32)
+      return rls_fail(ctx, RLS_E_UNSUPPORTED, "resident Gram FISTA: shape not resident");
+    else
+      return launch_fista_gram_resident<E, KC>(ctx, P, sync, nwg, n_steps, spin_limit, Sv);
+  });
 }
+
 template <typename E, int G, int K, int WV>
 static int32_t launch_pgm_resident(rls_ctx* ctx, const rls_pgm_desc& D, const rls_pgm_coefs& CF, void* sync, int nwg, int n_steps,
                                    unsigned spin_limit) {
-  using C = slab_cfg<E, G, K, WV>;
-  if constexpr ((K == 32 || K == 16) && WV == 8 && owner_cfg_ok<E, G, K, WV>() && !(elem<E>::cplx && G == 4)) {
-    const int64_t Mc = D.M / C::NV;
-    const int pair = (G == 4 && nwg % 16 == 0) ? 1 : 0;
-    const bool full = D.N == C::NMAX && (int64_t)nwg * G == Mc;
-    constexpr size_t lds = resident_lds_bytes<E, G, K, WV>();
-    static rls_device_once attr_once;
-    if (auto once_ = attr_once.first(ctx->device)) {
-#define RLS_PGM_ATTR(BB, FF, KK2) allow_big_lds(&pgm_resident_kernel<E, G, K, WV, BB, FF, KK2>, lds);
-      RLS_PGM_ATTR(1, true, 0) RLS_PGM_ATTR(2, true, 0) RLS_PGM_ATTR(1, false, 0) RLS_PGM_ATTR(2, false, 0)
-      RLS_PGM_ATTR(1, true, 1) RLS_PGM_ATTR(2, true, 1) RLS_PGM_ATTR(1, false, 1) RLS_PGM_ATTR(2, false, 1)
-      RLS_PGM_ATTR(1, true, 2) RLS_PGM_ATTR(2, true, 2) RLS_PGM_ATTR(1, false, 2) RLS_PGM_ATTR(2, false, 2)
-#undef RLS_PGM_ATTR
-    }
-#define RLS_LAUNCH_PGM(BB, FF, KK2)                                                                                              \
-  hipLaunchKernelGGL((pgm_resident_kernel<E, G, K, WV, BB, FF, KK2>), dim3(nwg), dim3(C::NT), lds, ctx->stream, (const E*)D.A,    \
-                     D.lda, (E*)D.v0, (E*)D.v1, (E*)D.v2, (E*)D.v3, (E*)D.o0, (E*)D.res, (const E*)D.x0, (E*)D.raw, (E*)D.slab, D.st, CF,  \
-                     D.norm_x0, D.rel_tol, D.reg_kind, D.proj_kind, (resident_sync*)sync, Mc, D.N, pair | (ctx->tune.fista_defer ? 0 : 2), n_steps, D.first_it, spin_limit)
-    const bool two = resident_two_level_ok<E>(ctx->tune, nwg, D.N, C::NT);
-    if (D.kind == 0) {
-      if (two) { if (full) RLS_LAUNCH_PGM(2, true, 0); else RLS_LAUNCH_PGM(2, false, 0); }
-      else { if (full) RLS_LAUNCH_PGM(1, true, 0); else RLS_LAUNCH_PGM(1, false, 0); }
-    } else if (D.kind == 1) {
-      if (two) { if (full) RLS_LAUNCH_PGM(2, true, 1); else RLS_LAUNCH_PGM(2, false, 1); }
-      else { if (full) RLS_LAUNCH_PGM(1, true, 1); else RLS_LAUNCH_PGM(1, false, 1); }
-    } else {
-      if (two) { if (full) RLS_LAUNCH_PGM(2, true, 2); else RLS_LAUNCH_PGM(2, false, 2); }
-      else { if (full) RLS_LAUNCH_PGM(1, true, 2); else RLS_LAUNCH_PGM(1, false, 2); }
-    }
-#undef RLS_LAUNCH_PGM
-    return launch_status(ctx);
-  } else {
+  if constexpr (!pgm_resident_shape<E, G, K, WV>()) {
     return rls_fail(ctx, RLS_E_UNSUPPORTED, "resident OptISTA / POGM: slab shape not instantiated");
+  } else {
+    using C = slab_cfg<E, G, K, WV>;
+    const int64_t Mc = D.M / C::NV;
+    const int pair = resident_pairing(G, nwg);
+    constexpr size_t lds = resident_lds_bytes<E, G, K, WV>();
+    return with_bool(resident_two_level_ok<E>(ctx->tune, nwg, D.N, C::NT), [&](auto TWO) {
+      return with_bool(slab_full<E, G, K, WV>(D.M, D.N, nwg), [&](auto FULL) {
+        return rls_with<0, 1, 2>(D.kind, [&](auto KIND) {
+          return rls_launch<pgm_resident_kernel<E, G, K, WV, TWO ? 2 : 1, FULL, KIND>>(
+              ctx, dim3(nwg), dim3(C::NT), lds, (const E*)D.A, D.lda, (E*)D.v0, (E*)D.v1, (E*)D.v2, (E*)D.v3, (E*)D.o0, (E*)D.res,
+              (const E*)D.x0, (E*)D.raw, (E*)D.slab, D.st, CF, D.norm_x0, D.rel_tol, D.reg_kind, D.proj_kind, (resident_sync*)sync,
+              Mc, D.N, pair | (ctx->tune.fista_defer ? 0 : 2), n_steps, D.first_it, spin_limit);
+        });
+      });
+    });
   }
 }
 
@@ -4492,12 +4300,7 @@ static int32_t pgm_resident_typed(rls_ctx* ctx, const rls_pgm_desc& D, const rls
   fused_cfg c;
   if (!pick_cfg<E>(ctx->tune, D.N, &c)) return rls_fail(ctx, RLS_E_UNSUPPORTED, "resident OptISTA / POGM: N too large");
   const int nwg = (int)fused_nwg<E>(ctx->tune, D.M, D.N);
-  int32_t st = RLS_E_UNSUPPORTED;
-#define RLS_PGM_CASE(GG, KK, WW) \
-  if (c.G == GG && c.K == KK && c.WV == WW) st = launch_pgm_resident<E, GG, KK, WW>(ctx, D, CF, sync, nwg, n_steps, spin_limit);
-  RLS_FOR_EACH_CFG(RLS_PGM_CASE)
-#undef RLS_PGM_CASE
-  return st;
+  return with_cfg(c, [&](auto S) { return launch_pgm_resident<E, S.G, S.K, S.WV>(ctx, D, CF, sync, nwg, n_steps, spin_limit); });
 }
 
 template <typename E>
@@ -4505,12 +4308,7 @@ static bool pgm_resident_ok_typed(const rls_tuning& T, int device, int64_t M, in
   if (!resident_ok_typed<E>(T, device, M, N, A, lda)) return false;
   fused_cfg c;
   if (!pick_cfg<E>(T, N, &c)) return false;
-  bool ok = false;
-#define RLS_PGM_OK(GG, KK, WW) \
-  if (c.G == GG && c.K == KK && c.WV == WW) ok = owner_cfg_ok<E, GG, KK, WW>() && (KK == 16 || KK == 32) && WW == 8 && !(elem<E>::cplx && GG == 4);
-  RLS_FOR_EACH_CFG(RLS_PGM_OK)
-#undef RLS_PGM_OK
-  return ok;
+  return with_cfg(c, [](auto S) { return pgm_resident_shape<E, S.G, S.K, S.WV>(); });
 }
 }  // namespace
 

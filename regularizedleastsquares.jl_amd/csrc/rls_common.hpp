@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #include "../../include/rls_mi355x.h"
 
@@ -221,7 +222,8 @@ inline std::mutex& rls_capture_mutex() {
 // threads entering their first solves at the same time (src/MultiThreading.jl:71) used to race here -- the second saw "seen" while
 // the first was still setting attributes and launched a kernel whose LDS size was not allowed yet (a cold-process failure of
 // tests/test_gpu_contexts.py, one run in a few).  Usage: `if (auto once = attr_once.first(device)) { ...work... }` -- the guard
-// lives through the body, publishes "done" behind it and only then lets the waiting threads go.
+// lives through the body, publishes "done" behind it and only then lets the waiting threads go.  A body whose work failed calls
+// once.failed(): the device stays "not done" and the next caller runs the body again.
 struct rls_device_once {
   std::atomic<uint64_t> done{0};
   std::mutex mu;
@@ -229,16 +231,18 @@ struct rls_device_once {
     rls_device_once* o;
     uint64_t bit;
     bool run;
+    bool ok = true;
     guard(rls_device_once* o_, uint64_t bit_, bool run_) : o(o_), bit(bit_), run(run_) {}
     guard(const guard&) = delete;
-    guard(guard&& g) : o(g.o), bit(g.bit), run(g.run) { g.run = false; }
+    guard(guard&& g) : o(g.o), bit(g.bit), run(g.run), ok(g.ok) { g.run = false; }
     ~guard() {
       if (run) {
-        o->done.fetch_or(bit, std::memory_order_release);
+        if (ok) o->done.fetch_or(bit, std::memory_order_release);
         o->mu.unlock();
       }
     }
     explicit operator bool() const { return run; }
+    void failed() { ok = false; }
   };
   guard first(int device) {  // true for exactly one caller per device; the others return once that caller's body has finished
     const uint64_t bit = 1ull << (device & 63);
@@ -281,6 +285,64 @@ static inline int32_t rls_fail(rls_ctx* ctx, int32_t code, const char* what) {
     int32_t _s = (expr);         \
     if (_s != 0) return _s;      \
   } while (0)
+
+static inline int32_t launch_status(rls_ctx* ctx) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return rls_fail(ctx, (int32_t)e, hipGetErrorString(e));
+  return 0;
+}
+
+// Allows kernel Kern `bytes` of dynamic LDS (hipFuncAttributeMaxDynamicSharedMemorySize; needed above 64 KiB) on `device`, the
+// current device.  Set once per instantiation and device, complete before any thread launches it (rls_device_once); a failed call
+// is returned and retried by the next caller.  So every launch of one instantiation must ask for the same `bytes`.
+template <auto Kern>
+static inline hipError_t rls_allow_lds(int device, size_t bytes) {
+  static rls_device_once once;
+  hipError_t e = hipSuccess;
+  if (auto g = once.first(device)) {
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) g.failed();
+  }
+  return e;
+}
+
+// The one launch of the dispatched kernels: `lds` bytes of dynamic LDS (0: static LDS only, no attribute) on the context's stream
+template <auto Kern, typename... A>
+static inline int32_t rls_launch(rls_ctx* ctx, dim3 grid, dim3 block, size_t lds, A... args) {
+  if (lds > 0) {
+    const hipError_t e = rls_allow_lds<Kern>(ctx->device, lds);
+    if (e != hipSuccess) return rls_fail(ctx, (int32_t)e, "hipFuncSetAttribute (dynamic LDS) failed");
+  }
+  hipLaunchKernelGGL(Kern, grid, block, lds, ctx->stream, args...);
+  return launch_status(ctx);
+}
+
+// Blocks of Kern one CU holds with `block` threads and `lds` bytes of dynamic LDS (0 when the query fails); leaves no error behind
+template <auto Kern>
+static inline int rls_occupancy(int device, int block, size_t lds) {
+  int blocks = 0;
+  if ((lds > 0 && rls_allow_lds<Kern>(device, lds) != hipSuccess) ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, Kern, block, lds) != hipSuccess)
+    blocks = 0;
+  (void)hipGetLastError();
+  return blocks;
+}
+
+// Compile-time dispatch: calls f(std::integral_constant<T, V>{}) for the first V of V0, Vs... equal to v, the last one when none
+// is.  Every V instantiates f's body: `if constexpr` in it keeps out the combinations that are not built.
+template <auto V0, auto... Vs, typename F>
+static inline auto rls_with(decltype(V0) v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) {
+    return f(std::integral_constant<decltype(V0), V0>{});
+  } else {
+    if (v == V0) return f(std::integral_constant<decltype(V0), V0>{});
+    return rls_with<Vs...>(v, static_cast<F&&>(f));
+  }
+}
+template <typename F>
+static inline auto with_bool(bool b, F&& f) {
+  return rls_with<false, true>(b, static_cast<F&&>(f));
+}
 
 static inline size_t rls_elem_size(int32_t dtype) { return dtype == RLS_C32 ? 8 : 4; }
 static inline bool rls_dtype_ok(int32_t dtype) { return dtype == RLS_F32 || dtype == RLS_C32; }

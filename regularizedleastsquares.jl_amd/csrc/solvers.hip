@@ -582,12 +582,6 @@ static void cgnr_launch_update(rls_cgnr* s) {
 #undef RLS_UPD_REG
 }
 
-static int32_t launch_status(rls_ctx* ctx) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rls_fail(ctx, (int32_t)e, hipGetErrorString(e));
-  return 0;
-}
-
 static int32_t cgnr_enqueue_update(rls_cgnr* s) {
   if (s->op->dtype == RLS_F32)
     cgnr_launch_update<float>(s);
