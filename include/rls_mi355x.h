@@ -338,7 +338,11 @@ typedef struct rls_cgnr_status {
 
 int32_t rls_cgnr_create(rls_operator* op, void* x, void* r, void* p, void* v, rls_cgnr** out);
 int32_t rls_cgnr_destroy(rls_cgnr* s);
-/* b: length M (or length N when the operator has only a Gram matrix: b must then be A^H b) */
+/* b: length M (or length N when the operator has only a Gram matrix: b must then be A^H b).
+ * Queue mode (resident plans, rls_cgnr_path 4, full-size shapes): once back-to-back solves have a resident kernel listening,
+ * rls_cgnr_init + rls_cgnr_step post ONE command to it and return -- init! runs inside the kernel when its turn comes, so b must
+ * be final on the device when rls_cgnr_init is called (work put on the stream by other means is not ordered before it).  Every
+ * other entry point tells the kernel to leave behind the commands posted.  rls_tune_set(ctx, "resident_queue", 0) switches it off. */
 int32_t rls_cgnr_init(rls_cgnr* s, const void* b, float lambda, float rel_tol, int32_t iterations);
 /* enqueue n_steps iterations (no-ops once done); asynchronous, graph-replayed */
 int32_t rls_cgnr_step(rls_cgnr* s, int32_t n_steps);

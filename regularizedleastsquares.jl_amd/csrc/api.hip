@@ -259,6 +259,7 @@ int32_t rls_ctx_sync(rls_ctx* ctx) {
   RLS_CHECK_CTX(ctx);
   RLS_HIP(ctx, rls_enter(ctx));
   RLS_HIP(ctx, rls_stream_wait(ctx->stream));
+  ++ctx->syncs;
   return 0;
 }
 
@@ -290,6 +291,7 @@ int32_t rls_tune_set(rls_ctx* ctx, const char* key, int32_t value) {
   else if (!strcmp(key, "small")) ctx->tune.small = value;
   else if (!strcmp(key, "resident_server")) ctx->tune.resident_server = value;
   else if (!strcmp(key, "resident_ahead")) ctx->tune.resident_ahead = value ? 1 : 0;
+  else if (!strcmp(key, "resident_queue")) ctx->tune.resident_queue = value ? 1 : 0;
   else if (!strcmp(key, "resident_l2_rows")) ctx->tune.resident_l2_rows = value;
   else if (!strcmp(key, "fista_defer")) ctx->tune.fista_defer = value;
   else if (!strcmp(key, "resident_server_idle_us")) {
@@ -400,6 +402,7 @@ int32_t rls_timer_stop_ms(rls_ctx* ctx, float* ms_out) {
   RLS_HIP(ctx, rls_enter(ctx));
   RLS_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   RLS_HIP(ctx, rls_event_wait(ctx->ev1));
+  ++ctx->syncs;
   RLS_HIP(ctx, hipEventElapsedTime(ms_out, ctx->ev0, ctx->ev1));
   return 0;
 }

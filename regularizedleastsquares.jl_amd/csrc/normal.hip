@@ -2199,6 +2199,35 @@ __device__ static inline void owner_products(const chunk<E, elem<E>::vec> (&a)[K
   }
 }
 
+// the second product of owner_products alone, for a given t_w (tr: the G * NV rows of this workgroup): partial row of A_w^H t_w ->
+// slab[blockIdx] at the scope owner_products uses.  Queue mode's init! (r = A^H b with t_w = b_w).
+template <typename E, int G, int K, int WV, bool FULL>
+__device__ static inline void owner_adjoint(const chunk<E, elem<E>::vec> (&a)[K], const E (&tr)[G * elem<E>::vec],
+                                            __amdgpu_buffer_rsrc_t slab_rs, int64_t N, bool l2rows) {
+  using C = slab_cfg<E, G, K, WV>;
+  constexpr int NV = C::NV, EPT = C::EPT, NT = C::NT;
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int q = 0; q < EPT / NV; ++q) {
+    chunk<E, NV> out;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      E sum = elem<E>::zero();
+#pragma unroll
+      for (int i = 0; i < G; ++i)
+#pragma unroll
+        for (int r = 0; r < NV; ++r) sum = elem<E>::fmac_pk(a[16 * q + j * G + i].e[r], tr[i * NV + r], sum);
+      out.e[j] = sum;
+    }
+    const int o = q * NT * NV + tid * NV;
+    if (FULL || o < N) {
+      const uint32_t off = (uint32_t)blockIdx.x * (uint32_t)(N * sizeof(E)) + (uint32_t)(o * sizeof(E));
+      if (l2rows) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, out), slab_rs, off, 0, 1);
+      else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, out), slab_rs, off, 0, 16);
+    }
+  }
+}
+
 // The two-level exchange's FIRST hop stays inside a group (the workgroups with equal blockIdx % RES_GROUPS), and under the
 // dispatcher's round-robin placement a group is the set of workgroups on ONE XCD: they share its L2.  So the partial rows a
 // workgroup hands to its group need not be written through to the memory side: stored with sc0 they stop in the L2 (the store's
@@ -2390,6 +2419,10 @@ __device__ static inline bool resident_allreduce(resident_lds<E, G, K, WV>& R, r
 // first iteration done (nothing of it published or written back before the command is there).  Told to leave instead, the kernel
 // leaves WITHOUT a write-back: memory holds the state of command k, which is what the host was told.  A separate instantiation: the
 // plain kernel's code is the SPEC = false text, token for token.
+// Queue mode (the SPEC instantiations of the full-size owner-layout shapes, launched with RLS_SRV_QUEUE in St.srv_idle_us: rls_cgnr_init +
+// rls_cgnr_step on a listening plan): the kernel stays across SOLVES and never runs ahead.  It listens on the command ring
+// (resident_listen_q) instead of the control block, and an INIT command runs init! from the registers: r = A^H b through the second
+// product with t_w = b_w and one exchange, then x = 0, p = r and the scalars, in every workgroup.  The plain kernel compiles it out.
 template <typename E, int G, int K, int WV, int BAR, bool FULL, bool SPEC = false>
 __global__ __launch_bounds__(WV * 64) void cgnr_resident_kernel(const E* __restrict__ A, int64_t lda, E* x, E* xw, E* r, E* p,
                                                                  E* v, E* slab, double* dout, cgnr_scalars* sc,
@@ -2435,7 +2468,20 @@ __global__ __launch_bounds__(WV * 64) void cgnr_resident_kernel(const E* __restr
   chunk<E, NV> a[K];
   slab_load<E, G, K, WV, FULL>(a, A, lda, Mc, N, pair);
   __builtin_amdgcn_sched_barrier(0);
-  if (!St.enabled && (S.done || n_steps <= 0)) return;  // uniform
+  constexpr bool QOK = SPEC && FULL && owner_cfg<E, G, K, WV>::ok;  // (queue mode: full-size owner layout; the masked ones spilled with it)
+  if constexpr (!QOK) {
+    if (!St.enabled && (S.done || n_steps <= 0)) return;  // uniform
+  }
+  const bool queue = QOK && (St.srv_idle_us & RLS_SRV_QUEUE);  // uniform
+  if constexpr (QOK) {
+    // (a launch that takes over the commands left in the ring starts with n_steps = 0; a done state may be followed by an INIT)
+    if (!queue && !St.enabled && (S.done || n_steps <= 0)) return;  // uniform
+    if (queue && blockIdx.x == 0 && tid == 0) {
+      const unsigned long long t = wall_clock64();
+      sync->q_t0[0] = (unsigned)t;
+      sync->q_t0[1] = (unsigned)(t >> 32);
+    }
+  }
   constexpr bool OWN = owner_cfg<E, G, K, WV>::ok;  // the slab re-arranged once so that a thread holds whole columns
   if constexpr (OWN) owner_transpose<E, G, K, WV, FULL>(a, smem_raw, Mc, N, pair);
   STAMP(1);
@@ -2685,11 +2731,65 @@ __global__ __launch_bounds__(WV * 64) void cgnr_resident_kernel(const E* __restr
   if (!St.srv_ctl) break;  // uniform
   if constexpr (SPEC) {
     credit = 0;
-    if (!S.done) {  // uniform: one iteration ahead of the next command
+    if (!S.done && !queue) {  // uniform: one iteration ahead of the next command
       ahead = true;
       n_steps = 1;
       continue;
     }
+  }
+  if constexpr (QOK) {
+  if (queue) {
+    // ---- queue mode: the next command of the ring (resident_listen_q, resident_sync.hpp) ------------------------------------
+    const rls_q_cmd qc = resident_listen_q(St.srv_ctl, srv_seq, St.srv_idle_us & ~RLS_SRV_QUEUE, sync, epoch, (unsigned)nwg, spin_limit, &R.flag);
+    if (qc.cmd == RLS_SRV_EXIT) return;  // uniform (told to leave, left idle or old, or a wait ran out: the control block says which)
+    n_steps = (int)(qc.cmd & RLS_Q_STEPS);
+    if (qc.cmd & RLS_Q_INIT) {  // uniform: init!  r = A^H b, x = 0, p = r (cgnr_init_kernel of solvers.hip)
+      const E* bq = reinterpret_cast<const E*>((uintptr_t)qc.b_lo | ((uintptr_t)qc.b_hi << 32));
+      E tb[G * NV];  // t_w = b_w: this workgroup's G * NV rows of b
+      const int64_t rb = row_block_of(blockIdx.x, pair) * G;
+#pragma unroll
+      for (int i = 0; i < G; ++i) {
+        const chunk<E, NV> c = load_chunk<E, NV>(bq + (rb + i) * NV);
+#pragma unroll
+        for (int r = 0; r < NV; ++r) tb[i * NV + r] = c.e[r];
+      }
+      owner_adjoint<E, G, K, WV, FULL>(a, tb, slab_rs, N, l2rows);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (!resident_allreduce<E, G, K, WV, BAR, FULL>(R, sync, slab_rs, v, nwg, N, epoch, xchg, spin_limit, rv, [](int, E) {}, []() {})) {
+        resident_give_up(sync, nullptr);
+        if (blockIdx.x == 0 && tid == 0) __hip_atomic_store(St.srv_ctl + 17, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        return;
+      }
+      if (!placed) {
+        l2rows = resident_rows_at_l2(sync);
+        placed = true;
+      }
+      double rr = 0.0;
+#pragma unroll
+      for (int e = 0; e < EPT; ++e) {
+        pv[e] = rv[e];
+        xv[e] = elem<E>::zero();
+        rr += (double)elem<E>::re(rv[e]) * (double)elem<E>::re(rv[e]) + (double)elem<E>::im(rv[e]) * (double)elem<E>::im(rv[e]);
+      }
+      if (blockIdx.x == 0) store_owned(xw, xv);
+      rr = block_sum_n<NT / 64>(rr, L.red);
+      S.rr = rr;
+      S.z0 = sqrt(rr);
+      S.zeta = 0.0;
+      S.alpha_re = S.alpha_im = S.beta_re = S.beta_im = 0.0;
+      S.lambda = __builtin_bit_cast(float, qc.lambda);
+      S.rel_tol = __builtin_bit_cast(float, qc.reltol);
+      S.iteration = 0;
+      S.max_iter = (int)qc.maxiter;
+      S.pending = 0;
+      S.cur = 0;
+      S.fresh = 0;
+      const float ratio = (float)(sqrt(rr) / sqrt(rr));  // NaN when r == 0, as in the reference
+      S.done = (ratio <= S.rel_tol) || (0 >= S.max_iter);
+    }
+    continue;
+  }
   }
   // ---- server mode: listen for the next command (resident_listen, resident_sync.hpp) ----------------------------------------
   const unsigned cmd = resident_listen(St.srv_ctl, srv_seq, St.srv_idle_us, sync, epoch, (unsigned)nwg, spin_limit, &R.flag, srv_mb, srv_seq - St.srv_seq0 + 1u);
@@ -2697,7 +2797,6 @@ __global__ __launch_bounds__(WV * 64) void cgnr_resident_kernel(const E* __restr
   n_steps = (int)cmd;
   }
 }
-
 
 // ---- resident Gram-mode CGNR: a whole rls_cgnr_step call (or a whole cg! solve) in ONE launch, AHA in registers --------
 // With AHA explicit a workgroup's rows of v = AHA p are complete (no partial rows), so an iteration needs ONE grid-wide
@@ -4099,6 +4198,18 @@ static int32_t launch_resident(rls_ctx* ctx, const rls_cgnr_pipe& P, double* dou
     const int64_t Mc = P.M / C::NV;
     const int pair = resident_pairing(G, nwg);
     constexpr size_t lds = resident_lds_bytes<E, G, K, WV>();
+    if (St.srv_ctl && (St.srv_idle_us & RLS_SRV_QUEUE)) {  // queue mode: the SPEC instantiation of a full-size owner-layout shape
+      if constexpr (!owner_cfg<E, G, K, WV>::ok) {
+        return rls_fail(ctx, RLS_E_UNSUPPORTED, "resident CGNR: no queue mode for this shape");
+      } else {
+        if (!slab_full<E, G, K, WV>(P.M, P.N, nwg)) return rls_fail(ctx, RLS_E_UNSUPPORTED, "resident CGNR: no queue mode for a ragged shape");
+        return with_bool(resident_two_level_ok<E>(ctx->tune, nwg, P.N, C::NT), [&](auto TWO) {
+          return rls_launch<cgnr_resident_kernel<E, G, K, WV, TWO ? 2 : 1, true, true>>(
+              ctx, dim3(nwg), dim3(C::NT), lds, (const E*)P.A, P.lda, (E*)P.x, (E*)P.r1, (E*)P.r0, (E*)P.p0, (E*)P.v, (E*)P.slab,
+              dout, P.sc, (resident_sync*)sync, Mc, P.N, pair, n_steps, spin_limit, St);
+        });
+      }
+    }
     // a kernel that stays and listens runs one iteration ahead of its commands (SPEC) unless the context says otherwise
     const bool spec = St.srv_ctl != nullptr && ctx->tune.resident_ahead != 0;
     return with_bool(resident_two_level_ok<E>(ctx->tune, nwg, P.N, C::NT), [&](auto TWO) {
@@ -4433,6 +4544,22 @@ int32_t rls_cgnr_resident_launch(rls_ctx* ctx, int32_t dtype, const rls_cgnr_pip
                                  int n_steps, unsigned spin_limit, const rls_cg_start& St) {
   if (dtype == RLS_F32) return resident_typed<float>(ctx, P, dout, sync, n_steps, spin_limit, St);
   return resident_typed<float2>(ctx, P, dout, sync, n_steps, spin_limit, St);
+}
+
+bool rls_cgnr_resident_queue_ok(const rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N) {
+  auto ok = [&](auto tag) {
+    using E = decltype(tag);
+    if (M % elem<E>::vec) return false;  // (init! reads b in whole 16-byte row pieces)
+    fused_cfg c;
+    if (!pick_cfg<E>(ctx->tune, N, &c)) return false;
+    return with_cfg(c, [&](auto S) {
+      return resident_shape<E, S.G, S.K, S.WV>() && owner_cfg<E, S.G, S.K, S.WV>::ok &&
+             slab_full<E, S.G, S.K, S.WV>(M, N, fused_nwg<E>(ctx->tune, M, N));
+    });
+  };
+  if (dtype == RLS_F32) return ok(float());
+  if (dtype == RLS_C32) return ok(float2());
+  return false;
 }
 
 int32_t rls_fista_resident_launch(rls_ctx* ctx, int32_t dtype, const rls_fista_pipe& P, void* sync, int n_steps,

@@ -47,7 +47,9 @@ struct resident_sync {
                          // solve is missing and retires the plan from the resident kernels); init! does NOT clear it, so a loss
                          // nobody asked about is still reported -- by the next status call, of whichever solve.
   unsigned srv_n, srv_mb;  // server mode: the command workgroup 0 relays to the grid (n_steps or RLS_SRV_EXIT, mailbox sequence)
-  unsigned pad[27];
+  unsigned q_w[6];         // queue mode: the payload of the command workgroup 0 relays to the grid (rls_q_cmd)
+  unsigned q_t0[2];        // queue mode: the launch's start on the wall clock (the life cap)
+  unsigned pad[19];
 };
 static_assert(sizeof(resident_sync) == (2 * 8 * 32 + 32) * sizeof(unsigned), "resident_sync layout");
 // behind the sync block (same allocation): the group-partial vectors of the two-level exchange, [2 parities][8 groups][N]
@@ -191,4 +193,84 @@ __device__ static inline unsigned resident_listen(unsigned* ctl, unsigned& srv_s
   mb.seq = __hip_atomic_load(&sync->srv_mb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   srv_seq += 1;
   return cmd;
+}
+
+// ---- queue mode (rls_cgnr plans: rls_cgnr_init + rls_cgnr_step post, nothing is launched) -------------------------------------------
+// A kernel that stays with A in its registers across SOLVES: the host appends commands {INIT b, lambda, relTol, maxiter; STEP n} to a
+// ring of RLS_Q_RING slots behind the control block (ctl + RLS_Q_RING_OFF) and returns at once; the kernel serves them in sequence
+// order.  A slot is six 8-byte pairs {payload word, sequence number}, each written by ONE 64-bit host store: a read of the slot is
+// taken only when all six halves carry the expected sequence number, so a 16-byte read that the link splits into halves sampled at
+// different times can not pair a new sequence with an old payload.  Behind the write-back of every command workgroup 0 publishes its
+// sequence number in ctl[RLS_Q_DONE]: the host re-uses a slot once its command is done there, and when the kernel has left (idle,
+// life cap) it launches again from that number -- the commands still in the ring are served in order by the new life.
+struct rls_q_cmd {
+  unsigned cmd, maxiter, b_lo, b_hi, lambda, reltol;  // cmd: n_steps | RLS_Q_INIT, or RLS_SRV_EXIT
+};
+__device__ static inline bool srv_read_slot(const unsigned* slot, unsigned seq, rls_q_cmd& c) {
+  typedef unsigned u4h __attribute__((ext_vector_type(4)));
+  u4h w0, w1, w2;  // three 16-byte reads in flight together: one round trip over the link
+  asm volatile("global_load_dwordx4 %0, %3, off sc0 sc1\n\tglobal_load_dwordx4 %1, %3, off offset:16 sc0 sc1\n\t"
+               "global_load_dwordx4 %2, %3, off offset:32 sc0 sc1\n\ts_waitcnt vmcnt(0)"
+               : "=&v"(w0), "=&v"(w1), "=&v"(w2) : "v"(slot) : "memory");
+  c = rls_q_cmd{w0.x, w0.z, w1.x, w1.z, w2.x, w2.z};
+  return w0.y == seq && w0.w == seq && w1.y == seq && w1.w == seq && w2.y == seq && w2.w == seq;
+}
+// The queue-mode listen: workgroup 0 publishes that the command srv_seq is done (its write-back lies before this call), then polls
+// the ring slot of srv_seq + 1 and relays the command to the grid.  It leaves (RLS_SRV_EXIT; ctl[17] = 1) on an EXIT command, when
+// nothing arrives for idle_us (with the leaving handshake of resident_listen), or once the life is older than RLS_Q_LIFE_TICKS --
+// then without looking at the ring at all: "leaving" goes out and the host finds the commands it posted in the ring, not done.
+// Every wait is bounded (the grid barrier by spin_limit).  Called by every thread of every workgroup.
+__device__ static inline rls_q_cmd resident_listen_q(unsigned* ctl, unsigned& srv_seq, unsigned idle_us, resident_sync* sync,
+                                                    unsigned& epoch, unsigned nwg, unsigned spin_limit, int* lds_flag) {
+  const int tid = threadIdx.x;
+  if (blockIdx.x == 0 && tid == 0) {
+    __hip_atomic_store(ctl + RLS_Q_DONE, srv_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    const unsigned long long t0 = wall_clock64(), idle = (unsigned long long)idle_us * 100ull;  // 100 MHz
+    const unsigned long long born = (unsigned long long)sync->q_t0[0] | ((unsigned long long)sync->q_t0[1] << 32);
+    const unsigned want = srv_seq + 1u;
+    const unsigned* slot = ctl + RLS_Q_RING_OFF + (want % RLS_Q_RING) * RLS_Q_SLOT_WORDS;
+    rls_q_cmd c{RLS_SRV_EXIT, 0u, 0u, 0u, 0u, 0u};
+    if (t0 - born > RLS_Q_LIFE_TICKS) {
+      __hip_atomic_store(ctl + 16, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    } else {
+      for (;;) {
+        rls_q_cmd r;
+        if (srv_read_slot(slot, want, r)) {
+          c = r;
+          break;
+        }
+        if (wall_clock64() - t0 > idle) {
+          __hip_atomic_store(ctl + 16, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          if (srv_read_slot(slot, want, r)) {
+            __hip_atomic_store(ctl + 16, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            c = r;
+          }
+          break;
+        }
+        __builtin_amdgcn_s_sleep(8);
+      }
+    }
+    const unsigned w[6] = {c.cmd, c.maxiter, c.b_lo, c.b_hi, c.lambda, c.reltol};
+#pragma unroll
+    for (int i = 0; i < 6; ++i) __hip_atomic_store(&sync->q_w[i], w[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  __syncthreads();
+  rls_q_cmd c{RLS_SRV_EXIT, 0u, 0u, 0u, 0u, 0u};
+  if (!grid_arrive_wait(sync->cnt, ++epoch, nwg, spin_limit, lds_flag)) {
+    resident_give_up(sync, nullptr);
+    if (blockIdx.x == 0 && tid == 0) __hip_atomic_store(ctl + 17, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    return c;
+  }
+  unsigned w[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) w[i] = __hip_atomic_load(&sync->q_w[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  c = rls_q_cmd{w[0], w[1], w[2], w[3], w[4], w[5]};
+  if (c.cmd == RLS_SRV_EXIT) {  // uniform
+    if (blockIdx.x == 0 && tid == 0) __hip_atomic_store(ctl + 17, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    return c;
+  }
+  srv_seq += 1;
+  return c;
 }

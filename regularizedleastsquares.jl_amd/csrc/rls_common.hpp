@@ -35,6 +35,7 @@ struct rls_tuning {
   int resident_preclear = 1; // 1: the init kernels zero the resident kernels' arrival counters (no memset launch ahead of the first step)
   int resident_server = 1;     // 1: rls_cgnr_step_status leaves the resident kernel listening for the next call (rls_cg_start::srv_ctl)
   int resident_server_idle_us = 300;  // ... for this long
+  int resident_queue = 1;      // 1: back-to-back rls_cgnr_init + rls_cgnr_step calls on a resident plan post to one kernel that stays (queue mode)
   int resident_ahead = 1;      // 1: a listening kernel computes one iteration ahead of the next command (the SPEC instantiations, normal.hip)
   int fista_defer = 1;         // 1: fista_resident_kernel sums ||res||^2 off the critical path where it can (normal.hip, DEFER); 0: measurement
   int resident_l2_rows = 1;    // 1: the matrix-free resident kernels keep their partial rows in the XCD's L2 when the placement allows (normal.hip,
@@ -76,6 +77,8 @@ struct rls_ctx {
   float* res_d = nullptr;   // small float result block on device
   float* res_h = nullptr;   // pinned host mirror
   rls_tuning tune;
+  uint64_t syncs = 0;         // host waits for the stream (rls_ctx_sync, rls_timer_stop_ms): queue mode starts on a plan's second
+                              // resident step call between two of them (solvers.hip, cgnr_use_queue)
   uint64_t tune_epoch = 0;    // bumped by every rls_tune_set: a cached hipGraph captured under other settings is dropped (solvers.hip, run_steps)
   int cus = 0;                // compute units of `device` (looked up once, by whoever asks first on this context)
   int resident_failures = 0;  // resident launches of this context that timed out; at 2 the context stops using them
@@ -109,7 +112,18 @@ struct rls_mailbox_slot {
 rls_mailbox_slot rls_mailbox_arm(rls_ctx* ctx, void* dst_pinned);
 // server mode of the resident kernels (see rls_cg_start::srv_ctl for the protocol): what a launch that is to stay and LISTEN gets
 constexpr unsigned RLS_SRV_EXIT = 0xffffffffu;
+constexpr unsigned RLS_SRV_QUEUE = 0x40000000u;  // bit 30 of rls_cg_start::srv_idle_us: the launch serves a command ring (queue mode, rls_cgnr)
 constexpr unsigned RLS_SRV_AHEAD = 0x80000000u;  // bit 31 of rls_srv_args::idle_us, read by the single-workgroup kernels (small.hip): one iteration ahead
+// queue mode's command ring (resident_listen_q, resident_sync.hpp; host side cgnr_queue_post, solvers.hip)
+constexpr unsigned RLS_Q_RING = 16;            // slots
+constexpr unsigned RLS_Q_SLOT_WORDS = 16;      // 64 bytes per slot, words 0..11 used
+constexpr unsigned RLS_Q_RING_OFF = 64;        // the ring starts 256 bytes behind the control block
+constexpr unsigned RLS_Q_CTL_WORDS = RLS_Q_RING_OFF + RLS_Q_RING * RLS_Q_SLOT_WORDS;
+constexpr unsigned RLS_Q_DONE = 18;            // ctl word: sequence number of the last command served and written back
+constexpr unsigned RLS_Q_INIT = 0x40000000u;   // command word: a new solve (init! with the payload's b) ahead of its n steps
+constexpr unsigned RLS_Q_STEPS = 0x3fffffffu;  // command word: n_steps
+constexpr unsigned long long RLS_Q_LIFE_TICKS = 2000000ull;  // life cap, 20 ms of the 100 MHz wall clock: a life leaves at the
+                                                             // first command boundary behind it (one 32-iteration command: ~0.25 ms)
 struct rls_srv_args {
   unsigned* ctl = nullptr;  // control block in pinned host memory (null: an ordinary launch)
   unsigned seq0 = 0, idle_us = 0;
@@ -890,6 +904,8 @@ struct rls_cg_start {
 
 int32_t rls_cgnr_resident_launch(rls_ctx* ctx, int32_t dtype, const rls_cgnr_pipe& P, double* dout, void* sync,
                                  int n_steps, unsigned spin_limit, const rls_cg_start& start = rls_cg_start());
+// the resident CGNR instantiation of this shape can serve a command ring (queue mode: the owner layout)
+bool rls_cgnr_resident_queue_ok(const rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N);
 
 // ---- OptISTA / POGM as resident launches (normal.hip, pgm_resident_kernel; host side pgm.hip) ----------------------------
 // the 4-word device record of the deferred OptISTA / POGM sequences (rls_*_update_async): iteration count, `done`, ||res||

@@ -141,6 +141,12 @@ struct srv_state {
   int served = 0, short_lives = 0;  // iterates: a listening kernel only stands in its way): per-iteration pipeline until init!
   unsigned seq = 0;
   bool* resident_used = nullptr;  // the plan's flag: "a status call must read the sync block's flags" (set when a life ends)
+  // queue mode (rls_cgnr plans, cgnr_queue_post): the life alive serves the command ring behind ctl
+  bool queue = false;
+  bool q_pending = false;  // an init! of rls_cgnr_init waits for the rls_cgnr_step that posts it
+  unsigned q_pay[5] = {};  // ... its payload {maxiter, b low, b high, lambda, relTol}
+  unsigned q_last = 0;     // the sequence number of the last command other than EXIT posted to the ring
+  void* q_plan = nullptr;  // the rls_cgnr the ring belongs to
 };
 
 struct rls_cgnr {
@@ -197,6 +203,9 @@ struct rls_cgnr {
   void* q_b = nullptr;
   void* q_bh = nullptr;
   void* q_xh = nullptr;
+  // queue mode (cgnr_use_queue): the control block has room for the command ring; ctx->syncs at the plan's last resident step call
+  bool q_ok = false;
+  uint64_t q_mark = ~0ull;
 };
 
 static bool cgnr_use_gram_pipeline(const rls_cgnr* s) {
@@ -2116,9 +2125,14 @@ static int32_t cgnr_create_impl(rls_operator* op, int32_t nrhs, void* x, void* r
     e = resident_alloc(ctx, op, &s->rsync, &s->rsync_h);
     if (e == hipSuccess) e = dmalloc(&s->rdots, db);
     if (e == hipSuccess) e = hipMemsetAsync(s->rdots, 0, db, ctx->stream);
-    if (e == hipSuccess && !s->srv.ctl) e = hmalloc(&s->srv.ctl, 32 * sizeof(unsigned));
+    if (e == hipSuccess && !s->srv.ctl) {
+      e = hmalloc(&s->srv.ctl, RLS_Q_CTL_WORDS * sizeof(unsigned));  // (the control block and the command ring of queue mode)
+      if (e == hipSuccess) memset(s->srv.ctl, 0, RLS_Q_CTL_WORDS * sizeof(unsigned));
+      s->q_ok = e == hipSuccess && rls_cgnr_resident_queue_ok(ctx, op->dtype, op->M, op->N);
+    }
     if (e == hipSuccess) memset(s->srv.ctl, 0, 32 * sizeof(unsigned));
     s->srv.resident_used = &s->resident_used;
+    s->srv.q_plan = s;
   }
   if (e == hipSuccess && nrhs == 1 && op->G && rls_gram_pipe_ok(op->dtype, op->N, op->G, op->ldg)) {
     const size_t vb = (size_t)op->N * rls_elem_size(op->dtype);
@@ -2250,7 +2264,17 @@ int32_t rls_cgnr_init_local_b(rls_cgnr* s) {
 
 static int32_t cgnr_group(rls_cgnr* const* plans, const void* const* b, int32_t count, float lambda, float rel_tol, int32_t iterations,
                           int32_t n_steps);
+extern "C++" {
+static bool cgnr_listening_q(const rls_cgnr* s);
+static int32_t cgnr_queue_init(rls_cgnr* s, const void* b, float lambda, float rel_tol, int32_t iterations);
+static int32_t cgnr_queue_step(rls_cgnr* s, int32_t n_steps);
+static bool cgnr_use_queue(const rls_cgnr* s);
+static int32_t cgnr_queue_launch(rls_cgnr* s, unsigned seq0, int32_t n_steps);
+}
 int32_t rls_cgnr_init(rls_cgnr* s, const void* b, float lambda, float rel_tol, int32_t iterations) {
+  // queue mode: the plan's kernel is listening -- init! travels with the next rls_cgnr_step, nothing is launched
+  if (s && b && s->nrhs == 1 && cgnr_listening_q(s) && (reinterpret_cast<uintptr_t>(b) & 15) == 0)
+    return cgnr_queue_init(s, b, lambda, rel_tol, iterations);
   // small systems: init! is the single-workgroup kernel's own (r = A^H b from the registers: ONE launch instead of a GEMV and an
   // init kernel, and the same bits whether a solve is init + steps or one fused launch, rls_cgnr_init_step_group)
   if (s && b && s->nrhs == 1 && s->op->A && cgnr_use_small(s)) return cgnr_group(&s, &b, 1, lambda, rel_tol, iterations, 0);
@@ -2449,15 +2473,27 @@ static int32_t cgnr_step_impl(rls_cgnr* s, int32_t n_steps) {
   return run_steps(ctx, &s->graph, n_steps, [s]() { return cgnr_enqueue_iteration(s); });
 }
 
-int32_t rls_cgnr_step(rls_cgnr* s, int32_t n_steps) {
+// `queue`: the call may post to (or start) a kernel that stays across solves (queue mode, cgnr_use_queue)
+static int32_t cgnr_step_call(rls_cgnr* s, int32_t n_steps, bool queue) {
   if (!s) return RLS_E_INVALID;
   rls_ctx* ctx = s->op->ctx;
   if (!s->initialised) return rls_fail(ctx, RLS_E_STATE, "cgnr_step before cgnr_init");
   if (n_steps < 0) return rls_fail(ctx, RLS_E_INVALID, "cgnr_step: n_steps < 0");
+  if (queue && cgnr_listening_q(s) && (unsigned)n_steps <= RLS_Q_STEPS) {
+    const int32_t r = cgnr_queue_step(s, n_steps);
+    if (r <= 0) return r;  // (1: the plan left queue mode and this call has run its init!, if any: the steps go the ordinary way)
+  }
   RLS_HIP(ctx, rls_enter(ctx));
   s->requested += n_steps;
+  // queue mode starts on the second resident step call of back-to-back solves: no status read (resident_used) and no host wait for
+  // the stream (ctx->syncs) since the plan's previous one.  The first call of a run is the plain single launch.
+  if (queue && n_steps > 1 && (unsigned)n_steps <= RLS_Q_STEPS && cgnr_use_resident(s)) {
+    if (s->resident_used && s->q_mark == ctx->syncs && cgnr_use_queue(s)) return cgnr_queue_launch(s, s->srv.seq + 1u, n_steps);
+    s->q_mark = ctx->syncs;
+  }
   return cgnr_step_impl(s, n_steps);
 }
+int32_t rls_cgnr_step(rls_cgnr* s, int32_t n_steps) { return cgnr_step_call(s, n_steps, true); }
 
 // ---- K independent small systems in ONE launch (small.hip, rls_small_group) -----------------------------------------------------
 // The distinct-A flavour of a multi-solve (docs/src/literate/howto/multi_threading.jl:8-17: one solver and one A per problem) for
@@ -2855,9 +2891,11 @@ static void server_life_over(rls_ctx* ctx, srv_state* v) {
   if (ctx->server == v) ctx->server = nullptr;
 }
 
+static void cgnr_queue_stop(rls_ctx* ctx, srv_state* v);
 void rls_server_stop(rls_ctx* ctx) {
   srv_state* v = static_cast<srv_state*>(ctx->server);
   if (!v) return;
+  if (v->queue) return cgnr_queue_stop(ctx, v);
   if (v->alive) {
     volatile unsigned* ctl = v->ctl;
     if (!ctl[17]) {
@@ -2954,6 +2992,198 @@ static int32_t server_command(rls_ctx* ctx, srv_state* v, void* mirror, int32_t 
   return 1;
 }
 
+// ---- queue mode: back-to-back solves served by ONE resident launch that keeps A in its registers ---------------------------------
+// The first resident step call of a run is the plain launch; the second (no status read, no host wait in between: rls_cgnr_step)
+// launches the QUEUE instantiation, which stays when its command is done.  From then on rls_cgnr_init + rls_cgnr_step post ONE
+// command {INIT b, lambda, relTol, maxiter; STEP n} into the ring behind the control block and return; rls_cgnr_step alone posts
+// {STEP n}.  Every other entry point goes through rls_enter, which posts EXIT behind the queued commands and waits until the kernel
+// has left: stream order for everything the caller can observe.  b must be final on the device when rls_cgnr_init is called.
+static bool cgnr_use_queue(const rls_cgnr* s) {
+  const rls_ctx* ctx = s->op->ctx;
+  return s->q_ok && ctx->tune.resident_queue && ctx->tune.resident_server && !s->srv.off &&
+         (ctx->server == nullptr || ctx->server == &s->srv) && cgnr_use_resident(s);
+}
+static bool cgnr_listening_q(const rls_cgnr* s) {
+  const srv_state& v = s->srv;
+  return s->op->ctx->server == &v && v.alive && v.queue && s->op->ctx->tune.resident_queue;
+}
+// a new life of the queue instantiation: its first command (seq0, n_steps) travels as launch arguments; a life that takes over
+// the commands left in the ring starts at the last one done with n_steps = 0
+static int32_t cgnr_queue_launch(rls_cgnr* s, unsigned seq0, int32_t n_steps) {
+  rls_ctx* ctx = s->op->ctx;
+  srv_state* v = &s->srv;
+  volatile unsigned* ctl = v->ctl;
+  ctl[16] = ctl[17] = 0;
+  if (n_steps > 0) {  // (a fresh command)
+    ctl[RLS_Q_DONE] = seq0 - 1u;
+    v->seq = v->q_last = seq0;
+  }
+  rls_cg_start St;
+  St.srv_ctl = v->ctl;
+  St.srv_seq0 = seq0;
+  St.srv_idle_us = (unsigned)(ctx->tune.resident_server_idle_us > 0 ? ctx->tune.resident_server_idle_us : 1) | RLS_SRV_QUEUE;
+  const rls_cgnr_pipe P = cgnr_pipe_desc(s);
+  s->resident_used = true;
+  RLS_TRY(resident_chain(ctx, s->rsync, [&]() {
+    return rls_cgnr_resident_launch(ctx, s->op->dtype, P, s->rdots, s->rsync, n_steps, (unsigned)ctx->tune.resident_spin, St);
+  }, &s->rsync_clean));
+  v->alive = true;
+  v->queue = true;
+  v->served = (int)(v->q_last - seq0) + (n_steps > 0 ? 1 : 0);
+  ctx->server = v;
+  return 0;
+}
+// one command on the ordinary path (init! by GEMV + init kernel, the steps by whatever cgnr_step_impl picks)
+static int32_t cgnr_queue_ordinary(rls_cgnr* s, unsigned cmd, const unsigned* pay) {
+  if (cmd & RLS_Q_INIT) {
+    const void* b = reinterpret_cast<const void*>((uintptr_t)pay[1] | ((uintptr_t)pay[2] << 32));
+    const long long req = s->requested;
+    const bool off = s->srv.off;
+    RLS_TRY(rls_cgnr_init_local_a(s, b, __builtin_bit_cast(float, pay[3]), __builtin_bit_cast(float, pay[4]), (int32_t)pay[0]));
+    RLS_TRY(rls_cgnr_init_local_b(s));
+    s->requested = req;
+    s->srv.off = off;
+  }
+  const int32_t n = (int32_t)(cmd & RLS_Q_STEPS);
+  return n > 0 ? cgnr_step_impl(s, n) : 0;
+}
+// The life has left (ctl[17]): the commands posted after the last one it finished are served by a new life -- or, behind a wait
+// that ran out (a lost launch) or when lives keep ending early, one by one on the ordinary path.  Leaves v->alive as the new state.
+static int32_t cgnr_queue_resume(rls_cgnr* s) {
+  rls_ctx* ctx = s->op->ctx;
+  srv_state* v = &s->srv;
+  volatile unsigned* ctl = v->ctl;
+  const bool gave_up = ctl[17] == 2;
+  const unsigned done = ctl[RLS_Q_DONE];
+  server_life_over(ctx, v);
+  v->queue = false;
+  if (done == v->q_last) return 0;
+  if (!gave_up && cgnr_use_queue(s)) return cgnr_queue_launch(s, done, 0);
+  if (gave_up) s->resident_off = true;  // (the status call behind it reads the lost launch from the sync block: resident_lost)
+  for (unsigned q = done + 1u; q != v->q_last + 1u; ++q) {
+    const volatile unsigned* sl = v->ctl + RLS_Q_RING_OFF + (q % RLS_Q_RING) * RLS_Q_SLOT_WORDS;
+    const unsigned pay[5] = {sl[2], sl[4], sl[6], sl[8], sl[10]};
+    RLS_TRY(cgnr_queue_ordinary(s, sl[0], pay));
+  }
+  return 0;
+}
+// Posts one command to the ring of the listening life.  0: posted (or, the life being gone, already served another way);
+// 1: the plan has left queue mode before the command could be posted (the caller runs it on the ordinary path); < 0: error.
+static int32_t cgnr_queue_post(rls_cgnr* s, unsigned cmd, const unsigned (&pay)[5]) {
+  rls_ctx* ctx = s->op->ctx;
+  srv_state* v = &s->srv;
+  volatile unsigned* ctl = v->ctl;
+  const unsigned seq = v->seq + 1u;
+  auto t0 = std::chrono::steady_clock::now();
+  // a free slot: the command RLS_Q_RING before this one is done (bounded: behind 2 s the host waits for the stream, which ends the
+  // life at its idle time at the latest)
+  for (unsigned n = 0; seq - ctl[RLS_Q_DONE] > RLS_Q_RING; ++n) {
+    if (ctl[17]) {
+      RLS_TRY(cgnr_queue_resume(s));
+      if (!v->alive) return 1;
+      t0 = std::chrono::steady_clock::now();
+      continue;
+    }
+    rls_cpu_relax();
+    if ((n & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
+      (void)hipSetDevice(ctx->device);
+      (void)hipStreamSynchronize(ctx->stream);
+      if (!ctl[17]) ctl[17] = 2;  // (nothing left running on the stream: the life is over whatever it said)
+    }
+  }
+  // six 8-byte halves {payload, sequence number}, each ONE store: the kernel takes the slot once all six carry `seq`
+  volatile unsigned long long* sl = reinterpret_cast<volatile unsigned long long*>(v->ctl + RLS_Q_RING_OFF + (seq % RLS_Q_RING) * RLS_Q_SLOT_WORDS);
+  const unsigned w[6] = {cmd, pay[0], pay[1], pay[2], pay[3], pay[4]};
+  for (int i = 0; i < 6; ++i) sl[i] = ((unsigned long long)seq << 32) | w[i];
+  v->seq = seq;
+  if (cmd != RLS_SRV_EXIT) v->q_last = seq;
+  v->served += 1;
+  std::atomic_thread_fence(std::memory_order_seq_cst);
+  // a life that is leaving (idle, life cap) either takes this command (and says so by clearing "leaving") or leaves
+  t0 = std::chrono::steady_clock::now();
+  for (unsigned n = 0; ctl[16] || ctl[17]; ++n) {
+    if (ctl[17]) return cgnr_queue_resume(s);
+    rls_cpu_relax();
+    if ((n & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(500)) {
+      (void)hipSetDevice(ctx->device);
+      (void)hipStreamSynchronize(ctx->stream);
+      if (!ctl[17]) ctl[17] = 2;
+    }
+  }
+  return 0;
+}
+static int32_t cgnr_queue_init(rls_cgnr* s, const void* b, float lambda, float rel_tol, int32_t iterations) {
+  srv_state* v = &s->srv;
+  if (v->q_pending) {  // an init! nobody stepped: it still sets the plan's state
+    v->q_pending = false;
+    const int32_t r = cgnr_queue_post(s, RLS_Q_INIT, v->q_pay);
+    if (r < 0) return r;
+    if (r == 1) RLS_TRY(cgnr_queue_ordinary(s, RLS_Q_INIT, v->q_pay));
+    if (!cgnr_listening_q(s)) return rls_cgnr_init(s, b, lambda, rel_tol, iterations);
+  }
+  const int max_iter = cgnr_effective_iterations(s, iterations);
+  const uintptr_t bp = reinterpret_cast<uintptr_t>(b);
+  v->q_pay[0] = (unsigned)max_iter;
+  v->q_pay[1] = (unsigned)bp;
+  v->q_pay[2] = (unsigned)(bp >> 32);
+  v->q_pay[3] = __builtin_bit_cast(unsigned, lambda);
+  v->q_pay[4] = __builtin_bit_cast(unsigned, rel_tol);
+  v->q_pending = true;
+  s->sc_h->lambda = lambda;
+  s->sc_h->rel_tol = rel_tol;
+  s->sc_h->max_iter = max_iter;
+  s->initialised = true;
+  s->requested = 0;
+  return 0;
+}
+// 0: posted; 1: the plan left queue mode (its pending init!, if any, has run): the caller runs the steps the ordinary way
+static int32_t cgnr_queue_step(rls_cgnr* s, int32_t n_steps) {
+  srv_state* v = &s->srv;
+  static const unsigned none[5] = {0u, 0u, 0u, 0u, 0u};
+  const bool init = v->q_pending;
+  if (!init && n_steps == 0) return 0;
+  unsigned pay[5];
+  for (int i = 0; i < 5; ++i) pay[i] = init ? v->q_pay[i] : none[i];
+  const unsigned cmd = (unsigned)n_steps | (init ? RLS_Q_INIT : 0u);
+  v->q_pending = false;
+  const long long req = s->requested;
+  s->requested += n_steps;
+  const int32_t r = cgnr_queue_post(s, cmd, pay);
+  if (r != 1) return r;
+  s->requested = req;
+  if (init) RLS_TRY(cgnr_queue_ordinary(s, RLS_Q_INIT, pay));
+  return 1;
+}
+// rls_enter on a queue life: the pending init!, then EXIT behind everything posted; a life that leaves before it reaches the EXIT
+// hands the rest to the next (cgnr_queue_resume) until all is done
+static void cgnr_queue_stop(rls_ctx* ctx, srv_state* v) {
+  rls_cgnr* s = static_cast<rls_cgnr*>(v->q_plan);
+  static const unsigned none[5] = {0u, 0u, 0u, 0u, 0u};
+  if (v->q_pending) {
+    v->q_pending = false;
+    const unsigned pay[5] = {v->q_pay[0], v->q_pay[1], v->q_pay[2], v->q_pay[3], v->q_pay[4]};
+    const int32_t r = cgnr_queue_post(s, RLS_Q_INIT, pay);
+    if (r == 1) (void)cgnr_queue_ordinary(s, RLS_Q_INIT, pay);
+    if (r != 0) return;
+  }
+  if (!v->alive) return;
+  if (cgnr_queue_post(s, RLS_SRV_EXIT, none) != 0) return;
+  volatile unsigned* ctl = v->ctl;
+  for (int lives = 0; v->alive && v->queue && lives < 1024; ++lives) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned n = 0; !ctl[17]; ++n) {
+      rls_cpu_relax();
+      if ((n & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(500)) {
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);  // (its idle timeout or its wait bounds end it at the latest)
+        if (!ctl[17]) ctl[17] = 2;
+      }
+    }
+    if (cgnr_queue_resume(s) != 0) break;
+  }
+  if (ctx->server == v) ctx->server = nullptr;
+}
+
 extern "C" int32_t rls_cgnr_step_status(rls_cgnr* s, int32_t n_steps, rls_cgnr_status* out);
 static int32_t cgnr_step_status_server(rls_cgnr* s, int32_t n_steps, rls_cgnr_status* out) {
   rls_ctx* ctx = s->op->ctx;
@@ -3010,6 +3240,7 @@ static int32_t cgnr_step_status_server(rls_cgnr* s, int32_t n_steps, rls_cgnr_st
 int32_t rls_cgnr_step_status(rls_cgnr* s, int32_t n_steps, rls_cgnr_status* out) {
   if (!s || !out) return RLS_E_INVALID;
   rls_ctx* ctx = s->op->ctx;
+  if (cgnr_listening_q(s)) rls_server_stop(ctx);  // (queue mode: the calls of a solve! loop with callbacks take their own path)
   // (whole-solve calls gain nothing from a kernel that stays: server mode is for the per-iterate calls of a solve! loop with callbacks)
   if (s->initialised && n_steps > 0 && n_steps <= 8 && !s->resident_used && cgnr_use_server(s)) return cgnr_step_status_server(s, n_steps, out);
   if (s->initialised && s->nrhs == 1 && n_steps > 0 && !s->resident_used) {
@@ -3017,7 +3248,7 @@ int32_t rls_cgnr_step_status(rls_cgnr* s, int32_t n_steps, rls_cgnr_status* out)
     s->mb_arm = rls_mailbox_arm(ctx, s->sc_h);
   }
   s->mb_sent = false;
-  const int32_t st = rls_cgnr_step(s, n_steps);
+  const int32_t st = cgnr_step_call(s, n_steps, false);
   const rls_mailbox_slot mb = s->mb_arm;
   s->mb_arm = rls_mailbox_slot();
   if (st != 0) return st;
