@@ -210,3 +210,20 @@ static inline void resident_chain_forget(std::mutex& mu, resident_chain_state& s
   const int d = device < 0 ? 0 : (device < 64 ? device : 63);
   if (st.last[d] == stream) st.last[d] = nullptr;
 }
+
+// ---- lost resident launches ------------------------------------------------------------------------------------------------------
+// What a plan (and its context) remembers about resident launches that gave up (solvers.hip, resident_slot): the plan stays off
+// the resident kernels from its first lost launch on, and a context that has met losses twice stops using them at all -- whatever
+// keeps a grid from being resident (another process on the device, a long kernel on another stream) would cost every later
+// attempt its full wait bound.
+struct resident_loss_state {
+  bool off = false;   // the plan has lost a launch: per-iteration pipeline from here on
+  int fallbacks = 0;  // launches lost (and recovered by the caller) so far
+};
+// `lost`: the count read back from the plan's sync block.  Returns whether the CONTEXT stops using resident kernels.
+static inline bool resident_note_lost(resident_loss_state& plan, int& ctx_failures, unsigned lost) {
+  if (!lost) return false;
+  plan.off = true;
+  plan.fallbacks += (int)lost;
+  return ++ctx_failures >= 2;
+}

@@ -43,7 +43,7 @@ struct resident_sync {
   // ---- everything above is zeroed ahead of every launch (rls_resident_sync_clear_bytes); what follows is STICKY ----
   unsigned failed;       // launches of this plan that were no-ops because workgroup 0 gave up: only workgroup 0 writes the
                          // state back, so "workgroup 0 timed out" is exactly "the launch changed nothing".  Zeroed at plan
-                         // creation and by the HOST once a status call has seen it (resident_lost: it re-runs what the current
+                         // creation and by the HOST once a status call has seen it (resident_slot::lost: it re-runs what the current
                          // solve is missing and retires the plan from the resident kernels); init! does NOT clear it, so a loss
                          // nobody asked about is still reported -- by the next status call, of whichever solve.
   unsigned srv_n, srv_mb;  // server mode: the command workgroup 0 relays to the grid (n_steps or RLS_SRV_EXIT, mailbox sequence)

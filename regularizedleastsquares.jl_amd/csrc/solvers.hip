@@ -63,6 +63,18 @@ struct step_graph {
   int mode = 0;  // which kernel sequence was captured
   bool failed = false;
   uint64_t epoch = 0;  // rls_ctx::tune_epoch at capture: launch shapes and kernel choices follow the context's switches
+  // forget the cached graph (another kernel sequence, other baked arguments, the plan goes away): the next step call captures afresh
+  void drop() {
+    if (exec) hipGraphExecDestroy(exec);
+    *this = step_graph();
+  }
+  // the call about to run captures / replays kernel sequence `m` on solution vector `x` (the captured kernels carry its address):
+  // a graph cached for another key is dropped
+  void keep_for(int m, void* x = nullptr) {
+    if (exec && (mode != m || x_bound != x)) drop();
+    mode = m;
+    x_bound = x;
+  }
 };
 
 // `rewind(c)`: a capture that fails has already called enqueue_one c times WITHOUT any of those launches running; a
@@ -129,6 +141,104 @@ static inline int pipe_cur_hint(const rls_ctx* ctx, int k) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// resident launches: the chain across streams, and what a plan keeps to run them and to notice lost ones
+// ---------------------------------------------------------------------------------------------
+static inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+template <typename... P>
+static inline bool aligned16(const void* q, P... more) { return aligned16(q) && aligned16(more...); }
+
+// A resident kernel needs every one of its workgroups on a CU at the same time.  Other kernels only delay that, but
+// two resident kernels running side by side (two contexts = two streams of this process) could each hold CUs the
+// other is waiting for.  So resident launches on one device form ONE chain across all streams of the process.  A launch
+// on the stream that issued the previous one is ordered by the stream itself (no event traffic at all: the common
+// single-context case); only when the stream CHANGES is an event recorded on the previous stream -- now, i.e. behind
+// everything it has queued since: conservative -- and waited for by the new one.  (Another PROCESS on the same device
+// is not covered: its symptom is the bounded-wait timeout reported by rls_cgnr_get_status.)
+static hipEvent_t g_resident_ev[64];
+static resident_chain_state g_resident_chain;  // guarded by rls_capture_mutex(); cleared by rls_resident_forget (context teardown)
+void rls_resident_forget(int device, hipStream_t stream) {
+  resident_chain_forget(rls_capture_mutex(), g_resident_chain, device, (void*)stream);
+}
+
+// What a plan needs to run resident launches and to notice lost ones.  A launch whose workgroups were not all on the chip in
+// time is a no-op (x, r, p and the scalars are written back by workgroup 0 only after its last barrier) that counts itself in
+// the sync block's sticky third flag word; the plan's next status read fetches the flags, and the plan re-runs what is missing
+// on the per-iteration pipeline (status_recover below; cg!, the PGM plans and ADMM have their own re-run rule).  `off` and
+// `fallbacks` (resident_loss_state, host_pool.hpp): the plan stays off the resident kernels from its first loss on.
+struct resident_slot : resident_loss_state {
+  void* sync = nullptr;         // device: arrival counters, {fail, completed, failed} (resident_sync.hpp), the exchange's group partials
+  unsigned* flags_h = nullptr;  // pinned mirror of the three flag words, read with the status
+  bool used = false;            // a resident launch went out since the last status read: that read fetches the flags
+  bool clean = false;           // the plan's init kernel has just zeroed the arrival counters itself (chain)
+
+  // the sync block (zeroed once: the sticky word starts at 0) and the pinned mirror
+  hipError_t alloc(rls_ctx* ctx, const rls_operator* op) {
+    hipError_t e = dmalloc(&sync, rls_resident_sync_alloc_bytes(op->dtype, op->N));
+    if (e == hipSuccess) e = hipMemsetAsync(sync, 0, rls_cgnr_resident_sync_bytes(), ctx->stream);
+    if (e == hipSuccess && !flags_h) {
+      e = hmalloc(&flags_h, 4 * sizeof(unsigned));
+      if (e == hipSuccess) memset(flags_h, 0, 4 * sizeof(unsigned));
+    }
+    return e;
+  }
+  // (inside the plan's rls_alloc_scope.)  Also the way out of a failed alloc(): resident mode is an optimisation, the plan
+  // runs on its per-iteration pipeline without the block
+  void release() {
+    if (sync) dfree(sync);
+    if (flags_h) hfree(flags_h);
+    sync = nullptr;
+    flags_h = nullptr;
+  }
+  bool usable(const rls_ctx* ctx) const { return sync && !off && ctx->tune.resident; }
+
+  // `launch(sync, spin_limit)` as the next link of the device's chain, behind the memset of the arrival counters and of the
+  // {fail, completed} words of THIS launch (the count of lost launches behind them is sticky).  `clean`: the init kernel has
+  // zeroed them and nothing has used them since -- the memset (a launch of its own: ~4 us on the stream between init! and the
+  // resident kernel of every solve) is skipped, once.
+  template <typename F>
+  int32_t chain(rls_ctx* ctx, F&& launch) {
+    const int d = ctx->device < 64 ? ctx->device : 63;
+    return resident_chain_step(
+        rls_capture_mutex(), g_resident_chain, ctx->device, (void*)ctx->stream,
+        [&](void* prev) -> int32_t {  // the chain changes streams: order this launch behind everything the previous stream has queued
+          if (!g_resident_ev[d]) RLS_HIP(ctx, hipEventCreateWithFlags(&g_resident_ev[d], hipEventDisableTiming));
+          RLS_HIP(ctx, hipEventRecord(g_resident_ev[d], (hipStream_t)prev));
+          RLS_HIP(ctx, hipStreamWaitEvent(ctx->stream, g_resident_ev[d], 0));
+          return 0;
+        },
+        [&]() -> int32_t {
+          if (clean && ctx->tune.resident_preclear) clean = false;
+          else RLS_HIP(ctx, hipMemsetAsync(sync, 0, rls_resident_sync_clear_bytes(), ctx->stream));
+          if (!ctx->tune.resident_l2_rows)  // measurement switch: pretend a workgroup is misplaced -- partial rows are written through
+            RLS_HIP(ctx, hipMemsetAsync((char*)sync + rls_resident_sync_placement_offset(), 1, 1, ctx->stream));
+          return launch(sync, (unsigned)ctx->tune.resident_spin);
+        });
+  }
+  // a launch the plan's next status read has to account for (the launches of a kernel that stays and listens are accounted for
+  // when its life ends: srv_state::resident_used; the PGM plans count theirs in rls_pgm_lost)
+  template <typename F>
+  int32_t launch(rls_ctx* ctx, F&& f) {
+    used = true;
+    return chain(ctx, f);
+  }
+
+  // enqueue the read-back of {fail, completed, failed}; the caller synchronises (normally with its scalar read-back)
+  int32_t fetch_flags(rls_ctx* ctx) {
+    return rls_fetch_add(ctx, (const char*)sync + rls_resident_sync_flags_offset(), flags_h, 3 * sizeof(unsigned));
+  }
+  // Launches lost since the last call (0 = none), behind a fetch_flags() the host has waited for.  The plan is off the resident
+  // kernels from here on, and a context that has met losses twice stops using them at all (resident_note_lost, host_pool.hpp).
+  unsigned lost(rls_ctx* ctx) {
+    const unsigned n = flags_h[2];
+    if (!n) return 0;
+    (void)hipMemsetAsync((char*)sync + rls_resident_sync_flags_offset() + 2 * sizeof(unsigned), 0, sizeof(unsigned), ctx->stream);
+    flags_h[2] = 0;
+    if (resident_note_lost(*this, ctx->resident_failures, n)) ctx->tune.resident = 0;
+    return n;
+  }
+};
+
+// ---------------------------------------------------------------------------------------------
 // CGNR
 // ---------------------------------------------------------------------------------------------
 // server mode of a plan's resident kernel (rls_cg_start::srv_ctl / rls_srv_args): the control block in pinned host memory and what
@@ -178,21 +288,14 @@ struct rls_cgnr {
   void* Vpart;
   int splits;
   int half;  // operand-panel layout, fixed at creation (rls_skinny_half)
-  // resident mode (normal.hip, cgnr_resident_kernel): arrival counters + flags, per-workgroup partial dots
-  void* rsync;
+  // resident mode (normal.hip, cgnr_resident_kernel): sync block + lost-launch bookkeeping, per-workgroup partial dots
+  resident_slot resident;
   double* rdots;
-  unsigned* rsync_h;  // pinned: {fail, completed, failed} (resident_sync), read with the status
-  bool resident_used;
   rls_mailbox_slot mb_arm;  // step_status: the call's last kernel publishes the scalars (pipeline and small-system paths)
   srv_state srv;  // server mode of the resident kernel (rls_cgnr_step_status)
   bool mb_sent = false;     // ... and this call's path did take the slot
   bool gram_resident;  // Gram mode: AHA fits the register files (rls_gram_resident_ok)
-  // a resident launch whose workgroups were not all on the chip in time is a no-op (normal.hip); the status call re-runs
-  // what was lost on the per-iteration pipeline and the plan stays there
-  bool resident_off;
-  int fallbacks;        // resident launches lost and recovered so far
-  long long requested;  // iterations asked for since init
-  bool rsync_clean = false;  // the init kernel has just zeroed the arrival counters (resident_chain)
+  long long requested;  // iterations asked for since init (what a lost launch did not run: requested - the device's count)
   bool small = false;  // the system fits one CU's registers: a step call is ONE single-workgroup launch (small.hip)
   // batched plan on an explicit Gram matrix, <= 8 ComplexF32 columns, AHA in the register files (gramk.hip): exchange scratch
   bool gramk = false;
@@ -212,22 +315,28 @@ static bool cgnr_use_gram_pipeline(const rls_cgnr* s) {
   return s->gram_pipe && s->op->G && s->op->ctx->tune.gram_pipeline;
 }
 
-static rls_gram_pipe cgnr_gram_desc(const rls_cgnr* s) {
+// the Gram-mode pipeline's view of a CGNR recurrence (a CGNR plan's own, or cg! on AHA + rho I: p = u, v = c): index 0 = the
+// caller's vectors, 1 = the second parity in plan scratch
+static rls_gram_pipe gram_pipe_desc(const rls_operator* op, void* x, void* r, void* r1, void* p, void* p1, void* v, void* v1,
+                                    double* gdots, cgnr_scalars* sc, cgnr_scalars* scn) {
   rls_gram_pipe P;
-  P.G = s->op->G;
-  P.ldg = s->op->ldg;
-  P.N = s->op->N;
-  P.x = s->x;
-  P.r[0] = s->r;
-  P.r[1] = s->r1;
-  P.p[0] = s->p;
-  P.p[1] = s->p1;
-  P.v[0] = s->v;
-  P.v[1] = s->v1;
-  P.dots = s->gdots;
-  P.sc[0] = s->sc;
-  P.sc[1] = s->scn;
+  P.G = op->G;
+  P.ldg = op->ldg;
+  P.N = op->N;
+  P.x = x;
+  P.r[0] = r;
+  P.r[1] = r1;
+  P.p[0] = p;
+  P.p[1] = p1;
+  P.v[0] = v;
+  P.v[1] = v1;
+  P.dots = gdots;
+  P.sc[0] = sc;
+  P.sc[1] = scn;
   return P;
+}
+static rls_gram_pipe cgnr_gram_desc(const rls_cgnr* s) {
+  return gram_pipe_desc(s->op, s->x, s->r, s->r1, s->p, s->p1, s->v, s->v1, s->gdots, s->sc, s->scn);
 }
 
 static rls_skinny cgnr_skinny_desc(const rls_cgnr* s) {
@@ -264,7 +373,7 @@ static bool cgnr_use_small(const rls_cgnr* s) {
 // batched Gram mode as ONE resident launch per step call (a call of one iteration -- the callback cadence -- is cheaper on
 // the streaming kernels: a resident launch loads its rows of AHA and gathers x once per call)
 static bool cgnr_use_gramk(const rls_cgnr* s, int n_steps) {
-  return s->gramk && s->rsync && !s->resident_off && s->op->ctx->tune.resident &&
+  return s->gramk && s->resident.usable(s->op->ctx) &&
          (n_steps != 1 || s->op->ctx->tune.resident == 2);  // resident = 2 (tools, tests): single-iteration calls too
 }
 
@@ -288,8 +397,7 @@ static rls_gramk cgnr_gramk_desc(const rls_cgnr* s) {
 }
 
 static bool cgnr_use_gram_resident(const rls_cgnr* s) {
-  return s->gram_resident && s->rsync && !s->resident_off && s->nrhs == 1 && cgnr_use_gram_pipeline(s) &&
-         s->op->ctx->tune.resident;
+  return s->gram_resident && s->resident.usable(s->op->ctx) && s->nrhs == 1 && cgnr_use_gram_pipeline(s);
 }
 
 static bool cgnr_use_pipeline(const rls_cgnr* s) {
@@ -300,102 +408,51 @@ static bool cgnr_use_pipeline(const rls_cgnr* s) {
 // the whole step call as one launch: single right-hand side, matrix-free, A small enough to stay in the register
 // files (one workgroup per CU), 16-byte aligned state vectors
 static bool cgnr_use_resident(const rls_cgnr* s) {
-  const rls_ctx* ctx = s->op->ctx;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  return s->rsync && !s->resident_off && s->nrhs == 1 && cgnr_use_pipeline(s) && ctx->tune.resident && al16(s->x) &&
-         al16(s->r) && al16(s->p) && al16(s->v);
+  return s->resident.usable(s->op->ctx) && s->nrhs == 1 && cgnr_use_pipeline(s) && aligned16(s->x, s->r, s->p, s->v);
 }
 
-// A resident kernel needs every one of its workgroups on a CU at the same time.  Other kernels only delay that, but
-// two resident kernels running side by side (two contexts = two streams of this process) could each hold CUs the
-// other is waiting for.  So resident launches on one device form ONE chain across all streams of the process.  A launch
-// on the stream that issued the previous one is ordered by the stream itself (no event traffic at all: the common
-// single-context case); only when the stream CHANGES is an event recorded on the previous stream -- now, i.e. behind
-// everything it has queued since: conservative -- and waited for by the new one.  (Another PROCESS on the same device
-// is not covered: its symptom is the bounded-wait timeout reported by rls_cgnr_get_status.)
-static hipEvent_t g_resident_ev[64];
-static resident_chain_state g_resident_chain;  // guarded by rls_capture_mutex(); cleared by rls_resident_forget (context teardown)
-void rls_resident_forget(int device, hipStream_t stream) {
-  resident_chain_forget(rls_capture_mutex(), g_resident_chain, device, (void*)stream);
-}
-// `clean` (nullable): the plan's init kernel has zeroed the counters itself and nothing has used them since -- the memset
-// (a launch of its own: ~4 us on the stream between init! and the resident kernel of every solve) is skipped, once
-template <typename F>
-static int32_t resident_chain(rls_ctx* ctx, void* rsync, F&& launch, bool* clean = nullptr) {
-  const int d = ctx->device < 64 ? ctx->device : 63;
-  return resident_chain_step(
-      rls_capture_mutex(), g_resident_chain, ctx->device, (void*)ctx->stream,
-      [&](void* prev) -> int32_t {  // the chain changes streams: order this launch behind everything the previous stream has queued
-        if (!g_resident_ev[d]) RLS_HIP(ctx, hipEventCreateWithFlags(&g_resident_ev[d], hipEventDisableTiming));
-        RLS_HIP(ctx, hipEventRecord(g_resident_ev[d], (hipStream_t)prev));
-        RLS_HIP(ctx, hipStreamWaitEvent(ctx->stream, g_resident_ev[d], 0));
-        return 0;
-      },
-      [&]() -> int32_t {
-        // arrival counters and the {fail, completed} words of THIS launch; the count of lost launches behind them is sticky
-        if (clean && *clean && ctx->tune.resident_preclear) *clean = false;
-        else RLS_HIP(ctx, hipMemsetAsync(rsync, 0, rls_resident_sync_clear_bytes(), ctx->stream));
-        if (!ctx->tune.resident_l2_rows)  // measurement switch: pretend a workgroup is misplaced -- partial rows are written through
-          RLS_HIP(ctx, hipMemsetAsync((char*)rsync + rls_resident_sync_placement_offset(), 1, 1, ctx->stream));
-        return launch();
-      });
-}
-static int32_t resident_chain_launch(rls_ctx* ctx, rls_cgnr* s, const rls_cgnr_pipe& P, int n_steps) {
-  return resident_chain(ctx, s->rsync, [&]() {
-    return rls_cgnr_resident_launch(ctx, s->op->dtype, P, s->rdots, s->rsync, n_steps, (unsigned)ctx->tune.resident_spin);
-  }, &s->rsync_clean);
-}
-// the sync block of a plan (zeroed once: the sticky word starts at 0) and the pinned mirror of its three flag words
-static hipError_t resident_alloc(rls_ctx* ctx, const rls_operator* op, void** rsync, unsigned** rsync_h) {
-  hipError_t e = dmalloc(rsync, rls_resident_sync_alloc_bytes(op->dtype, op->N));
-  if (e == hipSuccess) e = hipMemsetAsync(*rsync, 0, rls_cgnr_resident_sync_bytes(), ctx->stream);
-  if (e == hipSuccess && rsync_h && !*rsync_h) {
-    e = hmalloc(rsync_h, 4 * sizeof(unsigned));
-    if (e == hipSuccess) memset(*rsync_h, 0, 4 * sizeof(unsigned));
-  }
-  return e;
-}
-// enqueue the read-back of {fail, completed, failed}; the caller synchronises (normally with its scalar read-back)
-static int32_t resident_fetch_flags(rls_ctx* ctx, const void* rsync, unsigned* rsync_h) {
-  return rls_fetch_add(ctx, (const char*)rsync + rls_resident_sync_flags_offset(), rsync_h, 3 * sizeof(unsigned));
-}
-// Launches lost since the last call (0 = none).  A lost launch changed nothing (x, r, p and the scalars are written back by
-// workgroup 0 only after its last barrier), so the caller re-runs the missing iterations on the per-iteration pipeline.
-// The plan stays off the resident kernels from here on, and a context that has lost two launches stops using them at all:
-// whatever keeps the grid from being resident (another process on the device, a long kernel on another stream) would
-// cost every later attempt its full wait bound.
-static unsigned resident_lost(rls_ctx* ctx, void* rsync, unsigned* rsync_h, bool* off, int* fallbacks) {
-  const unsigned lost = rsync_h[2];
-  if (!lost) return 0;
-  (void)hipMemsetAsync((char*)rsync + rls_resident_sync_flags_offset() + 2 * sizeof(unsigned), 0, sizeof(unsigned), ctx->stream);
-  rsync_h[2] = 0;
-  *off = true;
-  *fallbacks += (int)lost;
-  if (++ctx->resident_failures >= 2) ctx->tune.resident = 0;
-  return lost;
-}
-
-static rls_cgnr_pipe cgnr_pipe_desc(const rls_cgnr* s) {
+// the matrix-free pipeline's view of a CGNR recurrence (as gram_pipe_desc); the batch fields keep their single-column defaults
+static rls_cgnr_pipe pipe_desc(const rls_operator* op, void* x, void* r, void* r1, void* p, void* p1, void* v, double* dots,
+                               cgnr_scalars* sc, cgnr_scalars* scn) {
   rls_cgnr_pipe P;
-  P.A = s->op->A;
-  P.lda = s->op->lda;
-  P.M = s->op->M;
-  P.N = s->op->N;
-  P.x = s->x;
-  P.r0 = s->r;
-  P.p0 = s->p;
-  P.r1 = s->r1;
-  P.p1 = s->p1;
-  P.v = s->v;
-  P.slab = s->slab_b ? s->slab_b : s->op->slab;
-  P.dots = s->dots;
+  P.A = op->A;
+  P.lda = op->lda;
+  P.M = op->M;
+  P.N = op->N;
+  P.x = x;
+  P.r0 = r;
+  P.p0 = p;
+  P.r1 = r1;
+  P.p1 = p1;
+  P.v = v;
+  P.slab = op->slab;
+  P.dots = dots;
+  P.ndots = (int)((op->N + 15) / 16);
+  P.sc = sc;
+  P.scn = scn;
+  return P;
+}
+static rls_cgnr_pipe cgnr_pipe_desc(const rls_cgnr* s) {
+  rls_cgnr_pipe P = pipe_desc(s->op, s->x, s->r, s->r1, s->p, s->p1, s->v, s->dots, s->sc, s->scn);
+  if (s->slab_b) P.slab = s->slab_b;
   P.ttw = s->ttw;
-  P.ndots = (int)((s->op->N + 15) / 16);
-  P.sc = s->sc;
-  P.scn = s->scn;
   P.nrhs = s->nrhs;
   P.vstride = s->ldv;
   return P;
+}
+// small systems (small.hip): the plan as the single-workgroup kernel sees it
+static rls_small cgnr_small_desc(const rls_cgnr* s) {
+  rls_small D;
+  D.A = s->op->A;
+  D.lda = s->op->lda;
+  D.M = s->op->M;
+  D.N = s->op->N;
+  D.x = s->x;
+  D.r = s->r;
+  D.p = s->p;
+  D.v = s->v;
+  D.sc = s->sc;
+  return D;
 }
 
 constexpr int UPD_THREADS = 1024;
@@ -568,11 +625,11 @@ __global__ __launch_bounds__(UPD_THREADS) void cgnr_update_reg_kernel(E* __restr
 template <typename E>
 static void cgnr_launch_init(rls_cgnr* s, float lambda, float rel_tol, int max_iter) {
   rls_operator* op = s->op;
-  const bool clr = s->rsync && s->nrhs == 1;
+  const bool clr = s->resident.sync && s->nrhs == 1;
   hipLaunchKernelGGL(cgnr_init_kernel<E>, dim3(1), dim3(UPD_THREADS), 0, op->ctx->stream, (E*)s->x, (const E*)s->r,
-                     (E*)s->p, (E*)s->v, op->N, s->sc, lambda, rel_tol, max_iter, clr ? (unsigned*)s->rsync : nullptr,
+                     (E*)s->p, (E*)s->v, op->N, s->sc, lambda, rel_tol, max_iter, clr ? (unsigned*)s->resident.sync : nullptr,
                      clr ? (int)(rls_resident_sync_clear_bytes() / sizeof(unsigned)) : 0);
-  s->rsync_clean = clr;
+  s->resident.clean = clr;
 }
 template <typename E>
 static void cgnr_launch_update(rls_cgnr* s) {
@@ -642,21 +699,15 @@ struct rls_fista {
   int splits = 1;
   int half = 0;  // operand-panel layout, fixed at creation (rls_skinny_half)
   fista_scalars* scb_h = nullptr;  // pinned [nrhs]
-  int enq = 0;           // iterations enqueued since init (== the device's count unless the plan stopped early)
-  int graph_parity = 0;  // parity of `enq` the cached graph's buffer hints were captured with
+  int enq = 0;           // iterations enqueued since init (== the device's count unless the plan stopped early); its parity at
+                         // capture is the key of the cached graph (step_graph::mode): the buffer hints belong to it
   float theta0 = 1.f;    // theta given to the last init (rls_fista_set_start needs it)
-  // resident mode (normal.hip, fista_resident_kernel)
-  void* rsync = nullptr;
-  unsigned* rsync_h = nullptr;
-  bool resident_used = false;
+  resident_slot resident;     // resident mode (normal.hip, fista_resident_kernel)
   bool small = false;         // dense A that fits ONE CU's registers: whole step calls on fista_small_kernel (small.hip)
   srv_state srv;              // server mode of the resident kernel (rls_fista_step_status)
   rls_mailbox_slot mb_arm;    // as the cgnr plan's
   bool mb_sent = false;
-  bool resident_off = false;  // a resident launch was lost: the plan stays on the per-iteration pipeline (cgnr plan, above)
-  int fallbacks = 0;
   long long requested = 0;    // iterations asked for since init
-  bool rsync_clean = false;   // the init kernel has just zeroed the arrival counters (resident_chain)
   // batched plan on an explicit Gram matrix, <= 8 ComplexF32 columns, AHA in the register files (gramk.hip): exchange scratch
   bool fgramk = false;
   int restart_b = 0;          // gradient restart asked for at init (the resident batched kernel does not carry it)
@@ -1059,13 +1110,9 @@ struct rls_cg {
   int splits = 1;
   // resident mode: cg! on (AHA + rho I) IS the CGNR recurrence, so after the start kernel the whole inner solve runs as
   // ONE launch of cgnr_resident_kernel with A in registers (normal.hip)
-  void* rsync = nullptr;
+  resident_slot resident;
   double* rdots = nullptr;
-  unsigned* rsync_h = nullptr;  // pinned {fail, completed, failed}
-  bool resident_used = false;
   bool gram_resident = false;  // Gram mode with AHA small enough for the register files (rls_gram_resident_ok)
-  bool resident_off = false;   // a resident launch was lost: the plan stays on the per-iteration pipeline
-  int fallbacks = 0;
   // the last rls_cg_solve, kept so that rls_cg_get_status can repeat it on the pipeline if its resident launch was lost
   // (a lost launch is a no-op: x still holds the warm start)
   struct {
@@ -1082,21 +1129,7 @@ static bool cg_use_gram_pipeline(const rls_cg* s) {
 }
 
 static rls_gram_pipe cg_gram_desc(const rls_cg* s, void* x) {
-  rls_gram_pipe P;
-  P.G = s->op->G;
-  P.ldg = s->op->ldg;
-  P.N = s->op->N;
-  P.x = x;
-  P.r[0] = s->r;
-  P.r[1] = s->r1;
-  P.p[0] = s->u;
-  P.p[1] = s->p1;
-  P.v[0] = s->c;
-  P.v[1] = s->v1;
-  P.dots = s->gdots;
-  P.sc[0] = s->psc;
-  P.sc[1] = s->pscn;
-  return P;
+  return gram_pipe_desc(s->op, x, s->r, s->r1, s->u, s->p1, s->c, s->v1, s->gdots, s->psc, s->pscn);
 }
 
 static bool cg_use_pipeline(const rls_cg* s) {
@@ -1105,23 +1138,7 @@ static bool cg_use_pipeline(const rls_cg* s) {
 }
 
 static rls_cgnr_pipe cg_pipe_desc(const rls_cg* s, void* x) {
-  rls_cgnr_pipe P;
-  P.A = s->op->A;
-  P.lda = s->op->lda;
-  P.M = s->op->M;
-  P.N = s->op->N;
-  P.x = x;
-  P.r0 = s->r;
-  P.p0 = s->u;
-  P.r1 = s->r1;
-  P.p1 = s->p1;
-  P.v = s->c;
-  P.slab = s->op->slab;
-  P.dots = s->dots;
-  P.ndots = (int)((s->op->N + 15) / 16);
-  P.sc = s->psc;
-  P.scn = s->pscn;
-  return P;
+  return pipe_desc(s->op, x, s->r, s->r1, s->u, s->p1, s->c, s->dots, s->psc, s->pscn);
 }
 
 // warm start of the pipeline: c = AHA x is in place; r = b - c - rho x, u = r, scalars reset.
@@ -1449,6 +1466,47 @@ static int32_t fetch_scalars(rls_ctx* ctx, S* d, S* h) {
   return rls_fetch_wait(ctx);  // one publishing launch for everything queued (resident flags, logs), then the host sees it
 }
 
+// ---- status read-back of a CGNR / FISTA plan, with the recovery of lost resident launches -----------------------------------------
+// `h`: the pinned mirror of the plan's `nrhs` scalar structs.  First half: enqueue the read-back of the scalars and, behind
+// resident launches, of the sync block's flags; the caller waits (rls_fetch_wait: one publishing launch for everything queued).
+template <typename Plan, typename S>
+static int32_t status_fetch_add(rls_ctx* ctx, Plan* s, S* h, int nrhs) {
+  static_assert(sizeof(S) % 4 == 0, "status structs are copied dword by dword");
+  if (s->resident.used) RLS_TRY(s->resident.fetch_flags(ctx));
+  return rls_fetch_add(ctx, s->sc, h, sizeof(S) * (size_t)nrhs);
+}
+// Second half, the mirrors being current.  A lost resident launch changed nothing: the live columns are all at the same count
+// (they advance in lockstep since init; retired ones stay behind), so what is missing is `requested` - that count, and
+// `rerun(n)` runs it on the plan's per-iteration path -- the plan is off the resident kernels by then -- before the scalars are
+// read again.  `on_lost(count)`: what else of the plan follows the device's count.  Every resident launch up to here is then
+// accounted for (the lost count is sticky until it is read).
+template <typename Plan, typename S, typename R, typename L>
+static int32_t status_recover(rls_ctx* ctx, Plan* s, S* h, int nrhs, R&& rerun, L&& on_lost) {
+  if (s->resident.used && s->resident.lost(ctx)) {
+    long long at = 0;
+    bool live = false;
+    for (int b = 0; b < nrhs; ++b) {
+      if (h[b].iteration > at) at = h[b].iteration;
+      live = live || !h[b].done;
+    }
+    on_lost(at);
+    const long long missing = s->requested - at;
+    if (live && missing > 0) {
+      RLS_TRY(rerun((int32_t)(missing > 0x7fffffff ? 0x7fffffff : missing)));
+      RLS_TRY(rls_fetch_add(ctx, s->sc, h, sizeof(S) * (size_t)nrhs));
+      RLS_TRY(rls_fetch_wait(ctx));
+    }
+  }
+  s->resident.used = false;
+  return 0;
+}
+template <typename Plan, typename S, typename R, typename L>
+static int32_t status_read(rls_ctx* ctx, Plan* s, S* h, int nrhs, R&& rerun, L&& on_lost) {
+  RLS_TRY(status_fetch_add(ctx, s, h, nrhs));
+  RLS_TRY(rls_fetch_wait(ctx));
+  return status_recover(ctx, s, h, nrhs, rerun, on_lost);
+}
+
 // G = A^H A is Hermitian with a real diagonal (Julia's A'*A goes through herk).  The generic kernels compute
 // both triangles independently, so the two images of an entry can differ in the last bit: copy the upper triangle
 // over the lower one as its conjugate and clear the imaginary part of the diagonal (the 64 x 64 tile kernel is
@@ -1674,35 +1732,32 @@ static int32_t cg_solve_impl(rls_cg* s, void* x, const void* b, float rho, int32
   const int64_t n = op->N;
   const admm_fuse<float> Ff = typed_fuse<float>(FV);
   const admm_fuse<float2> Fc = typed_fuse<float2>(FV);
-  if (cg_use_gram_pipeline(s) && s->gram_resident && s->rsync && !s->resident_off && ctx->tune.resident && maxiter > 0) {
-    // Gram mode, AHA in the register files: the whole cg! -- warm-start apply, r = b - (AHA + rho I) x (with beta formed on
-    // the way for ADMM), every iteration -- is ONE launch of cgnr_gram_resident_kernel (normal.hip)
+  // the cg! entry folded into a resident launch: warm-start apply, r = b - (AHA + rho I) x (ADMM's beta formed on the way)
+  rls_cg_start St;
+  St.enabled = 1;
+  St.b = b;
+  St.beta_y = FV.beta_y;
+  St.z = FV.z;
+  St.u = FV.u;
+  St.beta = FV.beta;
+  St.xold = FV.xold;
+  St.rho_admm = FV.rho;
+  St.rho = rho;
+  St.reltol = reltol;
+  St.maxiter = maxiter;
+  St.skip = FV.skip;
+  St.poison = FV.poison;
+  if (cg_use_gram_pipeline(s) && s->gram_resident && s->resident.usable(ctx) && maxiter > 0) {
+    // Gram mode, AHA in the register files: the whole cg! -- start and every iteration -- is ONE launch of
+    // cgnr_gram_resident_kernel (normal.hip)
     s->used_pipeline = true;
-    s->resident_used = true;
     const rls_gram_pipe P = cg_gram_desc(s, x);
-    rls_cg_start St;
-    St.enabled = 1;
-    St.b = b;
-    St.beta_y = FV.beta_y;
-    St.z = FV.z;
-    St.u = FV.u;
-    St.beta = FV.beta;
-    St.xold = FV.xold;
-    St.rho_admm = FV.rho;
-    St.rho = rho;
-    St.reltol = reltol;
-    St.maxiter = maxiter;
-    St.skip = FV.skip;
-    St.poison = FV.poison;
-    return resident_chain(ctx, s->rsync, [&]() {
-      return rls_gram_resident_launch(ctx, op->dtype, P, s->rsync, maxiter, (unsigned)ctx->tune.resident_spin, St);
+    return s->resident.launch(ctx, [&](void* sync, unsigned spin) {
+      return rls_gram_resident_launch(ctx, op->dtype, P, sync, maxiter, spin, St);
     });
   }
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  const bool resident_mf = cg_use_pipeline(s) && !cg_use_gram_pipeline(s) && s->rsync && !s->resident_off &&
-                           ctx->tune.resident && maxiter > 0 &&
-                           al16(x) && al16(s->r) && al16(s->u) && al16(s->c) && al16(b) && al16(FV.beta_y) && al16(FV.z) &&
-                           al16(FV.u) && al16(FV.beta) && al16(FV.xold);
+  const bool resident_mf = cg_use_pipeline(s) && !cg_use_gram_pipeline(s) && s->resident.usable(ctx) && maxiter > 0 &&
+                           aligned16(x, s->r, s->u, s->c, b, FV.beta_y, FV.z, FV.u, FV.beta, FV.xold);
   // warm start: one operator apply for r = b - (AHA + rho I) x   (inside the resident launch where that runs)
   if (!resident_mf) RLS_TRY(op_normal(op, x, s->c, FV.skip));
   if (cg_use_gram_pipeline(s)) {
@@ -1718,12 +1773,7 @@ static int32_t cg_solve_impl(rls_cg* s, void* x, const void* b, float rho, int32
     RLS_TRY(launch_status(ctx));
     const rls_gram_pipe P = cg_gram_desc(s, x);
     const int32_t dtype = op->dtype;
-    if (s->graph.exec && (s->graph.x_bound != x || s->graph.mode != 3)) {  // the captured kernels carry x's address
-      hipGraphExecDestroy(s->graph.exec);
-      s->graph = step_graph();
-    }
-    s->graph.x_bound = x;
-    s->graph.mode = 3;
+    s->graph.keep_for(3, x);
     int parity = 0;
     auto one = [ctx, dtype, &P, &parity]() {
       const int32_t st = rls_gram_pipe_iteration(ctx, dtype, P, parity);
@@ -1740,26 +1790,10 @@ static int32_t cg_solve_impl(rls_cg* s, void* x, const void* b, float rho, int32
   s->used_pipeline = cg_use_pipeline(s);
   if (s->used_pipeline) {
     if (resident_mf) {
-      // matrix-free, A in the register files: warm-start apply, residual (ADMM's beta formed on the way) and every
-      // iteration in ONE launch of cgnr_resident_kernel (normal.hip)
-      s->resident_used = true;
+      // matrix-free, A in the register files: start and every iteration in ONE launch of cgnr_resident_kernel (normal.hip)
       const rls_cgnr_pipe P = cg_pipe_desc(s, x);
-      rls_cg_start St;
-      St.enabled = 1;
-      St.b = b;
-      St.beta_y = FV.beta_y;
-      St.z = FV.z;
-      St.u = FV.u;
-      St.beta = FV.beta;
-      St.xold = FV.xold;
-      St.rho_admm = FV.rho;
-      St.rho = rho;
-      St.reltol = reltol;
-      St.maxiter = maxiter;
-      St.skip = FV.skip;
-      St.poison = FV.poison;
-      return resident_chain(ctx, s->rsync, [&]() {
-        return rls_cgnr_resident_launch(ctx, op->dtype, P, s->rdots, s->rsync, maxiter, (unsigned)ctx->tune.resident_spin, St);
+      return s->resident.launch(ctx, [&](void* sync, unsigned spin) {
+        return rls_cgnr_resident_launch(ctx, op->dtype, P, s->rdots, sync, maxiter, spin, St);
       });
     }
     if (op->dtype == RLS_F32)
@@ -1773,12 +1807,7 @@ static int32_t cg_solve_impl(rls_cg* s, void* x, const void* b, float rho, int32
     RLS_TRY(launch_status(ctx));
     rls_cgnr_pipe P = cg_pipe_desc(s, x);
     const int32_t dtype = op->dtype;
-    if (s->graph.exec && (s->graph.x_bound != x || s->graph.mode != 1)) {  // the captured kernels carry x's address
-      hipGraphExecDestroy(s->graph.exec);
-      s->graph = step_graph();
-    }
-    s->graph.x_bound = x;
-    s->graph.mode = 1;
+    s->graph.keep_for(1, x);
     int k = 0;
     RLS_TRY(run_steps(ctx, &s->graph, maxiter, [ctx, dtype, &P, &k]() {
       P.cur_hint = pipe_cur_hint(ctx, k++);
@@ -2082,13 +2111,8 @@ static int32_t cgnr_create_impl(rls_operator* op, int32_t nrhs, void* x, void* r
   s->nrhs = nrhs;
   s->ldv = ldv;
   s->slab_b = nullptr;
-  s->rsync = nullptr;
   s->rdots = nullptr;
-  s->rsync_h = nullptr;
-  s->resident_used = false;
   s->gram_resident = false;
-  s->resident_off = false;
-  s->fallbacks = 0;
   s->requested = 0;
   const size_t sb = sizeof(cgnr_scalars) * (size_t)nrhs;
   hipError_t e = dmalloc(&s->sc, sb);
@@ -2122,7 +2146,7 @@ static int32_t cgnr_create_impl(rls_operator* op, int32_t nrhs, void* x, void* r
   if (e == hipSuccess && nrhs == 1 && op->slab && op->A && !op->G &&
       rls_cgnr_resident_ok(ctx, op->dtype, op->M, op->N, op->A, op->lda)) {
     const size_t db = (size_t)rls_cgnr_resident_nwg(op->ctx, op->dtype, op->M, op->N) * 4 * sizeof(double);
-    e = resident_alloc(ctx, op, &s->rsync, &s->rsync_h);
+    e = s->resident.alloc(ctx, op);
     if (e == hipSuccess) e = dmalloc(&s->rdots, db);
     if (e == hipSuccess) e = hipMemsetAsync(s->rdots, 0, db, ctx->stream);
     if (e == hipSuccess && !s->srv.ctl) {
@@ -2131,7 +2155,7 @@ static int32_t cgnr_create_impl(rls_operator* op, int32_t nrhs, void* x, void* r
       s->q_ok = e == hipSuccess && rls_cgnr_resident_queue_ok(ctx, op->dtype, op->M, op->N);
     }
     if (e == hipSuccess) memset(s->srv.ctl, 0, 32 * sizeof(unsigned));
-    s->srv.resident_used = &s->resident_used;
+    s->srv.resident_used = &s->resident.used;
     s->srv.q_plan = s;
   }
   if (e == hipSuccess && nrhs == 1 && op->G && rls_gram_pipe_ok(op->dtype, op->N, op->G, op->ldg)) {
@@ -2148,13 +2172,13 @@ static int32_t cgnr_create_impl(rls_operator* op, int32_t nrhs, void* x, void* r
     if (e == hipSuccess) e = hipMemsetAsync(s->gdots, 0, nd, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(s->scn, 0, sb, ctx->stream);
     s->gram_pipe = e == hipSuccess;
-    if (e == hipSuccess && !s->rsync && rls_gram_resident_ok(ctx, op->dtype, op->N, op->G, op->ldg)) {
-      e = resident_alloc(ctx, op, &s->rsync, &s->rsync_h);
+    if (e == hipSuccess && !s->resident.sync && rls_gram_resident_ok(ctx, op->dtype, op->N, op->G, op->ldg)) {
+      e = s->resident.alloc(ctx, op);
       s->gram_resident = e == hipSuccess;
       if (e == hipSuccess && !s->srv.ctl && rls_gram_resident_server_ok(op->dtype, op->N) &&
           hmalloc(&s->srv.ctl, 32 * sizeof(unsigned)) == hipSuccess) {
         memset(s->srv.ctl, 0, 32 * sizeof(unsigned));
-        s->srv.resident_used = &s->resident_used;
+        s->srv.resident_used = &s->resident.used;
       }
     }
   }
@@ -2169,7 +2193,7 @@ static int32_t cgnr_create_impl(rls_operator* op, int32_t nrhs, void* x, void* r
     if (e == hipSuccess && op->G && s->half && rls_gramk_resident_ok(ctx, op->dtype, op->N, nrhs, op->G, op->ldg)) {
       size_t xb, xxb, db;
       rls_gramk_sizes(op->N, &xb, &xxb, &db);
-      e = resident_alloc(ctx, op, &s->rsync, &s->rsync_h);
+      e = s->resident.alloc(ctx, op);
       if (e == hipSuccess) e = dmalloc(&s->gk_vx, xb);
       if (e == hipSuccess) e = hipMemsetAsync(s->gk_vx, 0, xb, ctx->stream);  // rows >= N are read, never written
       if (e == hipSuccess) e = dmalloc(&s->gk_xx, xxb);
@@ -2201,7 +2225,7 @@ int32_t rls_cgnr_destroy(rls_cgnr* s) {
   if (rls_ctx_alive(s->actx, s->actx_id) && s->actx->server == &s->srv) rls_server_stop(s->actx);  // (a kernel of this plan left listening)
   hipSetDevice(s->device);
   rls_alloc_scope alloc_scope(alloc_ctx_of(s->actx, s->actx_id));
-  if (s->graph.exec) hipGraphExecDestroy(s->graph.exec);
+  s->graph.drop();
   if (s->r1) dfree(s->r1);
   if (s->p1) dfree(s->p1);
   if (s->dots) dfree(s->dots);
@@ -2219,9 +2243,8 @@ int32_t rls_cgnr_destroy(rls_cgnr* s) {
   if (s->q_b) dfree(s->q_b);
   if (s->q_bh) hfree(s->q_bh);
   if (s->q_xh) hfree(s->q_xh);
-  if (s->rsync) dfree(s->rsync);
+  s->resident.release();
   if (s->rdots) dfree(s->rdots);
-  if (s->rsync_h) hfree(s->rsync_h);
   if (s->srv.ctl) hfree(s->srv.ctl);
   if (s->sc) dfree(s->sc);
   if (s->sc_h) hfree(s->sc_h);
@@ -2324,44 +2347,17 @@ int32_t rls_cgnr_init_batched(rls_cgnr* s, const void* B, int64_t ldb, float lam
 
 static int32_t cgnr_step_impl(rls_cgnr* s, int32_t n_steps);
 static void cgnr_status_out(const rls_cgnr* s, const cgnr_scalars& h, rls_cgnr_status* out);
+// a CGNR plan's status read: the first `nrhs` structs of sc_h (rls_cgnr_get_status: 1)
+static int32_t cgnr_fetch_status(rls_cgnr* s, int nrhs) {
+  return status_read(s->op->ctx, s, s->sc_h, nrhs, [s](int32_t n) { return cgnr_step_impl(s, n); }, [](long long) {});
+}
 int32_t rls_cgnr_get_status_batched(rls_cgnr* s, rls_cgnr_status* out) {
   if (!s || !out) return RLS_E_INVALID;
   rls_ctx* ctx = s->op->ctx;
   if (!s->initialised) return rls_fail(ctx, RLS_E_STATE, "cgnr_get_status before cgnr_init");
   RLS_HIP(ctx, rls_enter(ctx));
-  if (s->resident_used) RLS_TRY(resident_fetch_flags(ctx, s->rsync, s->rsync_h));
-  RLS_TRY(rls_fetch_add(ctx, s->sc, s->sc_h, sizeof(cgnr_scalars) * (size_t)s->nrhs));
-  RLS_TRY(rls_fetch_wait(ctx));
-  if (s->resident_used && resident_lost(ctx, s->rsync, s->rsync_h, &s->resident_off, &s->fallbacks)) {
-    // a lost resident launch changed nothing: the live columns are all at the same count (they advance in lockstep since
-    // init; retired ones stay behind), so what is missing is requested - that count, re-run on the streaming kernels
-    long long at = 0;
-    bool live = false;
-    for (int b = 0; b < s->nrhs; ++b) {
-      if (s->sc_h[b].iteration > at) at = s->sc_h[b].iteration;
-      live = live || !s->sc_h[b].done;
-    }
-    const long long missing = s->requested - at;
-    if (live && missing > 0) {
-      RLS_TRY(cgnr_step_impl(s, (int32_t)(missing > 0x7fffffff ? 0x7fffffff : missing)));
-      RLS_TRY(rls_fetch_add(ctx, s->sc, s->sc_h, sizeof(cgnr_scalars) * (size_t)s->nrhs));
-      RLS_TRY(rls_fetch_wait(ctx));
-    }
-  }
-  s->resident_used = false;
-  for (int b = 0; b < s->nrhs; ++b) {
-    const cgnr_scalars& h = s->sc_h[b];
-    out[b].iteration = h.iteration;
-    out[b].done = h.done;
-    out[b].alpha_re = (float)h.alpha_re;
-    out[b].alpha_im = (float)h.alpha_im;
-    out[b].beta_re = (float)h.beta_re;
-    out[b].beta_im = (float)h.beta_im;
-    out[b].zeta = (float)h.zeta;
-    out[b].residual = (float)sqrt(h.rr);
-    out[b].z0 = (float)h.z0;
-    out[b].fallbacks = s->fallbacks;
-  }
+  RLS_TRY(cgnr_fetch_status(s, s->nrhs));
+  for (int b = 0; b < s->nrhs; ++b) cgnr_status_out(s, s->sc_h[b], out + b);
   return 0;
 }
 
@@ -2369,16 +2365,7 @@ static int32_t cgnr_step_impl(rls_cgnr* s, int32_t n_steps) {
   rls_ctx* ctx = s->op->ctx;
   if (cgnr_use_small(s)) {
     if (n_steps == 0) return 0;
-    rls_small D;
-    D.A = s->op->A;
-    D.lda = s->op->lda;
-    D.M = s->op->M;
-    D.N = s->op->N;
-    D.x = s->x;
-    D.r = s->r;
-    D.p = s->p;
-    D.v = s->v;
-    D.sc = s->sc;
+    rls_small D = cgnr_small_desc(s);
     D.mb = s->mb_arm;
     s->mb_sent = s->mb_arm.dst != nullptr;
     return rls_small_launch(ctx, s->op->dtype, D, n_steps);
@@ -2386,19 +2373,12 @@ static int32_t cgnr_step_impl(rls_cgnr* s, int32_t n_steps) {
   if (s->skinny && cgnr_use_gramk(s, n_steps)) {
     if (n_steps == 0) return 0;
     const rls_gramk D = cgnr_gramk_desc(s);
-    s->resident_used = true;
-    return resident_chain(ctx, s->rsync, [&]() {
-      return rls_gramk_resident_launch(ctx, D, s->rsync, n_steps, (unsigned)ctx->tune.resident_spin);
-    }, &s->rsync_clean);
+    return s->resident.launch(ctx, [&](void* sync, unsigned spin) { return rls_gramk_resident_launch(ctx, D, sync, n_steps, spin); });
   }
   if (s->skinny) {
     const rls_skinny K = cgnr_skinny_desc(s);
     const int32_t dtype = s->op->dtype;
-    if (s->graph.steps && s->graph.mode != 2) {
-      hipGraphExecDestroy(s->graph.exec);
-      s->graph = step_graph();
-    }
-    s->graph.mode = 2;
+    s->graph.keep_for(2);
     return run_steps(ctx, &s->graph, n_steps, [ctx, dtype, &K]() { return rls_skinny_launch(ctx, dtype, K, 7); });
   }
   if (cgnr_use_gram_pipeline(s)) {
@@ -2409,16 +2389,11 @@ static int32_t cgnr_step_impl(rls_cgnr* s, int32_t n_steps) {
     const int32_t dtype = s->op->dtype;
     if (cgnr_use_gram_resident(s)) {  // the whole call as ONE launch, AHA in registers, one grid exchange per iteration
       if (n_steps == 0) return 0;
-      s->resident_used = true;
-      return resident_chain(ctx, s->rsync, [&]() {
-        return rls_gram_resident_launch(ctx, dtype, P, s->rsync, n_steps, (unsigned)ctx->tune.resident_spin);
-      }, &s->rsync_clean);
+      return s->resident.launch(ctx, [&](void* sync, unsigned spin) {
+        return rls_gram_resident_launch(ctx, dtype, P, sync, n_steps, spin);
+      });
     }
-    if (s->graph.steps && s->graph.mode != 3) {
-      hipGraphExecDestroy(s->graph.exec);
-      s->graph = step_graph();
-    }
-    s->graph.mode = 3;
+    s->graph.keep_for(3);
     int parity = 0;
     auto one = [ctx, dtype, &P, &parity]() {
       const int32_t st = rls_gram_pipe_iteration(ctx, dtype, P, parity);
@@ -2440,19 +2415,16 @@ static int32_t cgnr_step_impl(rls_cgnr* s, int32_t n_steps) {
     // grid-wide all-reduce (normal.hip).  The arrival counters and flags are zeroed ahead of every launch.
     if (n_steps == 0) return 0;
     const rls_cgnr_pipe P = cgnr_pipe_desc(s);
-    s->resident_used = true;
-    return resident_chain_launch(ctx, s, P, n_steps);
+    return s->resident.launch(ctx, [&](void* sync, unsigned spin) {
+      return rls_cgnr_resident_launch(ctx, s->op->dtype, P, s->rdots, sync, n_steps, spin);
+    });
   }
   if (cgnr_use_pipeline(s)) {
     // iteration k = K_A (applies update k-1 in its prologue, then one pass over A) + K_R; the last
     // update of this call is applied by K_F, which also returns r, p to the caller's vectors
     rls_cgnr_pipe P = cgnr_pipe_desc(s);
     const int32_t dtype = s->op->dtype;
-    if (s->graph.steps && s->graph.mode != 1) {  // graph captured for the other kernel sequence
-      hipGraphExecDestroy(s->graph.exec);
-      s->graph = step_graph();
-    }
-    s->graph.mode = 1;
+    s->graph.keep_for(1);
     int k = 0;
     RLS_TRY(run_steps(ctx, &s->graph, n_steps, [ctx, dtype, &P, &k]() {
       P.cur_hint = pipe_cur_hint(ctx, k++);
@@ -2465,11 +2437,7 @@ static int32_t cgnr_step_impl(rls_cgnr* s, int32_t n_steps) {
     return rls_cgnr_pipe_finish(ctx, dtype, P);
   }
   if (s->nrhs != 1) return rls_fail(ctx, RLS_E_UNSUPPORTED, "batched CGNR: fused pipeline switched off");
-  if (s->graph.steps && s->graph.mode != 0) {
-    hipGraphExecDestroy(s->graph.exec);
-    s->graph = step_graph();
-  }
-  s->graph.mode = 0;
+  s->graph.keep_for(0);
   return run_steps(ctx, &s->graph, n_steps, [s]() { return cgnr_enqueue_iteration(s); });
 }
 
@@ -2488,7 +2456,7 @@ static int32_t cgnr_step_call(rls_cgnr* s, int32_t n_steps, bool queue) {
   // queue mode starts on the second resident step call of back-to-back solves: no status read (resident_used) and no host wait for
   // the stream (ctx->syncs) since the plan's previous one.  The first call of a run is the plain single launch.
   if (queue && n_steps > 1 && (unsigned)n_steps <= RLS_Q_STEPS && cgnr_use_resident(s)) {
-    if (s->resident_used && s->q_mark == ctx->syncs && cgnr_use_queue(s)) return cgnr_queue_launch(s, s->srv.seq + 1u, n_steps);
+    if (s->resident.used && s->q_mark == ctx->syncs && cgnr_use_queue(s)) return cgnr_queue_launch(s, s->srv.seq + 1u, n_steps);
     s->q_mark = ctx->syncs;
   }
   return cgnr_step_impl(s, n_steps);
@@ -2518,16 +2486,7 @@ static int32_t cgnr_group(rls_cgnr* const* plans, const void* const* b, int32_t 
     G.count = count - k0 < RLS_SMALL_GROUP_MAX ? count - k0 : RLS_SMALL_GROUP_MAX;
     for (int j = 0; j < G.count; ++j) {
       rls_cgnr* s = plans[k0 + j];
-      rls_small& D = G.d[j];
-      D.A = s->op->A;
-      D.lda = s->op->lda;
-      D.M = s->op->M;
-      D.N = s->op->N;
-      D.x = s->x;
-      D.r = s->r;
-      D.p = s->p;
-      D.v = s->v;
-      D.sc = s->sc;
+      rls_small& D = G.d[j] = cgnr_small_desc(s);
       if (b) {
         D.b = b[k0 + j];
         D.lambda = lambda;
@@ -2555,7 +2514,7 @@ int32_t rls_cgnr_get_status_group(rls_cgnr* const* plans, int32_t count, rls_cgn
     rls_cgnr* s = plans[k];
     if (!s || s->op->ctx != ctx || s->nrhs != 1) return rls_fail(ctx, RLS_E_INVALID, "cgnr status group: single-column plans of one context");
     if (!s->initialised) return rls_fail(ctx, RLS_E_STATE, "cgnr_get_status before cgnr_init");
-    if (s->resident_used) return rls_fail(ctx, RLS_E_UNSUPPORTED, "cgnr status group: a plan has resident launches to account for (use rls_cgnr_get_status)");
+    if (s->resident.used) return rls_fail(ctx, RLS_E_UNSUPPORTED, "cgnr status group: a plan has resident launches to account for (use rls_cgnr_get_status)");
   }
   for (int32_t k0 = 0; k0 < count; k0 += RLS_FETCH_MAX) {
     const int32_t k1 = k0 + RLS_FETCH_MAX < count ? k0 + RLS_FETCH_MAX : count;
@@ -2593,23 +2552,12 @@ static int32_t cgnr_queue_statuses(rls_ctx* ctx, rls_cgnr* const* plans, int32_t
   constexpr int32_t PER = RLS_FETCH_MAX / 2;  // two read-backs per plan at most
   for (int32_t k0 = 0; k0 < count; k0 += PER) {
     const int32_t k1 = k0 + PER < count ? k0 + PER : count;
-    for (int32_t k = k0; k < k1; ++k) {
-      rls_cgnr* s = plans[k];
-      if (s->resident_used) RLS_TRY(resident_fetch_flags(ctx, s->rsync, s->rsync_h));
-      RLS_TRY(rls_fetch_add(ctx, s->sc, s->sc_h, sizeof(cgnr_scalars)));
-    }
+    for (int32_t k = k0; k < k1; ++k) RLS_TRY(status_fetch_add(ctx, plans[k], plans[k]->sc_h, 1));
     RLS_TRY(rls_fetch_wait(ctx));
   }
   for (int32_t k = 0; k < count; ++k) {
     rls_cgnr* s = plans[k];
-    if (s->resident_used && resident_lost(ctx, s->rsync, s->rsync_h, &s->resident_off, &s->fallbacks)) {
-      const long long missing = s->requested - (long long)s->sc_h->iteration;
-      if (!s->sc_h->done && missing > 0) {
-        RLS_TRY(cgnr_step_impl(s, (int32_t)(missing > 0x7fffffff ? 0x7fffffff : missing)));
-        RLS_TRY(fetch_scalars(ctx, s->sc, s->sc_h));
-      }
-    }
-    s->resident_used = false;
+    RLS_TRY(status_recover(ctx, s, s->sc_h, 1, [s](int32_t n) { return cgnr_step_impl(s, n); }, [](long long) {}));
     if (out) cgnr_status_out(s, *s->sc_h, out + k);
   }
   return 0;
@@ -2659,7 +2607,7 @@ int32_t rls_cgnr_solve_queue_host(rls_cgnr* const* plans, const void* const* b_h
   bool any = false;
   for (int32_t k = 0; k < count; ++k) {
     rls_cgnr* s = plans[k];
-    if (s->resident_off && s->fallbacks > 0) {
+    if (s->resident.off && s->resident.fallbacks > 0) {
       RLS_HIP(ctx, hipMemcpyAsync(s->q_xh, s->x, (size_t)s->op->N * rls_elem_size(s->op->dtype), hipMemcpyDeviceToHost, ctx->stream));
       any = true;
     }
@@ -2818,22 +2766,6 @@ int32_t rls_cgnr_step_local_b(rls_cgnr* s) {
   return cgnr_enqueue_update(s);
 }
 
-// status read-back of a single-RHS plan; re-runs on the per-iteration pipeline whatever a lost resident launch left undone
-static int32_t cgnr_fetch_status(rls_cgnr* s) {
-  rls_ctx* ctx = s->op->ctx;
-  if (s->resident_used) RLS_TRY(resident_fetch_flags(ctx, s->rsync, s->rsync_h));
-  RLS_TRY(fetch_scalars(ctx, s->sc, s->sc_h));
-  if (s->resident_used && resident_lost(ctx, s->rsync, s->rsync_h, &s->resident_off, &s->fallbacks)) {
-    const long long missing = s->requested - (long long)s->sc_h->iteration;
-    if (!s->sc_h->done && missing > 0) {
-      RLS_TRY(cgnr_step_impl(s, (int32_t)(missing > 0x7fffffff ? 0x7fffffff : missing)));
-      RLS_TRY(fetch_scalars(ctx, s->sc, s->sc_h));
-    }
-  }
-  s->resident_used = false;  // every resident launch up to here is accounted for (the lost count is sticky until it is read)
-  return 0;
-}
-
 int32_t rls_cgnr_get_status(rls_cgnr* s, rls_cgnr_status* out) {
   if (!s || !out) return RLS_E_INVALID;
   rls_ctx* ctx = s->op->ctx;
@@ -2843,7 +2775,7 @@ int32_t rls_cgnr_get_status(rls_cgnr* s, rls_cgnr_status* out) {
     return 0;
   }
   RLS_HIP(ctx, rls_enter(ctx));
-  RLS_TRY(cgnr_fetch_status(s));
+  RLS_TRY(cgnr_fetch_status(s, 1));
   cgnr_status_out(s, *s->sc_h, out);
   return 0;
 }
@@ -2858,7 +2790,7 @@ static void cgnr_status_out(const rls_cgnr* s, const cgnr_scalars& h, rls_cgnr_s
   out->zeta = (float)h.zeta;
   out->residual = (float)sqrt(h.rr);
   out->z0 = (float)h.z0;
-  out->fallbacks = s->fallbacks;
+  out->fallbacks = s->resident.fallbacks;
 }
 
 // ---- resident kernels in server mode (rls_cg_start::srv_ctl, rls_srv_args) ---------------------------------------------------------
@@ -3023,10 +2955,9 @@ static int32_t cgnr_queue_launch(rls_cgnr* s, unsigned seq0, int32_t n_steps) {
   St.srv_seq0 = seq0;
   St.srv_idle_us = (unsigned)(ctx->tune.resident_server_idle_us > 0 ? ctx->tune.resident_server_idle_us : 1) | RLS_SRV_QUEUE;
   const rls_cgnr_pipe P = cgnr_pipe_desc(s);
-  s->resident_used = true;
-  RLS_TRY(resident_chain(ctx, s->rsync, [&]() {
-    return rls_cgnr_resident_launch(ctx, s->op->dtype, P, s->rdots, s->rsync, n_steps, (unsigned)ctx->tune.resident_spin, St);
-  }, &s->rsync_clean));
+  RLS_TRY(s->resident.launch(ctx, [&](void* sync, unsigned spin) {
+    return rls_cgnr_resident_launch(ctx, s->op->dtype, P, s->rdots, sync, n_steps, spin, St);
+  }));
   v->alive = true;
   v->queue = true;
   v->served = (int)(v->q_last - seq0) + (n_steps > 0 ? 1 : 0);
@@ -3059,7 +2990,7 @@ static int32_t cgnr_queue_resume(rls_cgnr* s) {
   v->queue = false;
   if (done == v->q_last) return 0;
   if (!gave_up && cgnr_use_queue(s)) return cgnr_queue_launch(s, done, 0);
-  if (gave_up) s->resident_off = true;  // (the status call behind it reads the lost launch from the sync block: resident_lost)
+  if (gave_up) s->resident.off = true;  // (the status call behind it reads the lost launch from the sync block: resident_slot::lost)
   for (unsigned q = done + 1u; q != v->q_last + 1u; ++q) {
     const volatile unsigned* sl = v->ctl + RLS_Q_RING_OFF + (q % RLS_Q_RING) * RLS_Q_SLOT_WORDS;
     const unsigned pay[5] = {sl[2], sl[4], sl[6], sl[8], sl[10]};
@@ -3184,78 +3115,75 @@ static void cgnr_queue_stop(rls_ctx* ctx, srv_state* v) {
   if (ctx->server == v) ctx->server = nullptr;
 }
 
-extern "C" int32_t rls_cgnr_step_status(rls_cgnr* s, int32_t n_steps, rls_cgnr_status* out);
-static int32_t cgnr_step_status_server(rls_cgnr* s, int32_t n_steps, rls_cgnr_status* out) {
+// One iterate per call is the reference's solve! loop with callbacks (src/RegularizedLeastSquares.jl:161-176): step and read-back
+// as ONE entry point (rls_cgnr_step_status, rls_fista_step_status).
+//   `serve`: the plan's resident kernel in server mode -- the command is posted to the kernel left listening, or carried by
+// `serve_launch(args)` (whole-solve calls gain nothing from a kernel that stays: per-iterate calls of up to 8 steps only).
+// `account(+-n)` books the command's iterations into the plan's counts and takes them back when nothing ran.
+//   Otherwise `step`, and on the per-iteration pipeline and the small-system kernel the call's last kernel stores the scalars into
+// the plan's pinned mirror itself (the armed mailbox slot) -- no publishing launch behind it; where the path did not take the
+// slot, `get_status`.
+template <typename Plan, typename Status, typename SL, typename A, typename St, typename G, typename F>
+static int32_t step_status(Plan* s, int32_t n_steps, Status* out, bool serve, SL&& serve_launch, A&& account, St&& step, G&& get_status,
+                           F&& status_out) {
   rls_ctx* ctx = s->op->ctx;
-  RLS_HIP(ctx, hipSetDevice(s->device));
-  s->requested += n_steps;
-  const int32_t r = server_command(ctx, &s->srv, s->sc_h, n_steps, true, [&](const rls_srv_args& a) {
+  if (serve && s->initialised && n_steps > 0 && n_steps <= 8 && !s->resident.used) {
+    RLS_HIP(ctx, hipSetDevice(s->device));
+    account(n_steps);
+    const int32_t r = server_command(ctx, &s->srv, s->sc_h, n_steps, true, serve_launch);
+    if (r < 0) return r;
+    if (r == 0) {
+      status_out(s, *s->sc_h, out);
+      return 0;
+    }
+    if (r == 2) return get_status(s, out);  // a launch gave up inside the command: the lost-launch recovery re-runs it
+    account(-n_steps);  // r == 1, nothing ran (and the plan's server mode is off): the ordinary path
+  }
+  if (s->initialised && s->nrhs == 1 && n_steps > 0 && !s->resident.used) {
+    RLS_HIP(ctx, rls_enter(ctx));
+    s->mb_arm = rls_mailbox_arm(ctx, s->sc_h);
+  }
+  s->mb_sent = false;
+  const int32_t st = step(s, n_steps);
+  const rls_mailbox_slot mb = s->mb_arm;
+  s->mb_arm = rls_mailbox_slot();
+  if (st != 0) return st;
+  if (!s->mb_sent) return get_status(s, out);
+  RLS_TRY(rls_mailbox_wait(ctx, mb.seq));
+  status_out(s, *s->sc_h, out);
+  return 0;
+}
+}  // extern "C++"
+
+int32_t rls_cgnr_step_status(rls_cgnr* s, int32_t n_steps, rls_cgnr_status* out) {
+  if (!s || !out) return RLS_E_INVALID;
+  rls_ctx* ctx = s->op->ctx;
+  if (cgnr_listening_q(s)) rls_server_stop(ctx);  // (queue mode: the calls of a solve! loop with callbacks take their own path)
+  auto serve_launch = [&](const rls_srv_args& a) {
     rls_cg_start St;
     St.srv_ctl = a.ctl;
     St.srv_seq0 = a.seq0;
     St.srv_idle_us = a.idle_us & ~RLS_SRV_AHEAD;
     St.srv_mb = a.mb;
     if (cgnr_use_small(s)) {  // the single-workgroup kernel: one CU stays, nothing to chain
-      rls_small D;
-      D.A = s->op->A;
-      D.lda = s->op->lda;
-      D.M = s->op->M;
-      D.N = s->op->N;
-      D.x = s->x;
-      D.r = s->r;
-      D.p = s->p;
-      D.v = s->v;
-      D.sc = s->sc;
+      rls_small D = cgnr_small_desc(s);
       D.mb = a.mb;
       D.srv = a;
       return rls_small_launch(ctx, s->op->dtype, D, n_steps);
     }
     if (cgnr_use_gram_resident(s)) {  // AHA explicit, held in the register files
       const rls_gram_pipe G = cgnr_gram_desc(s);
-      return resident_chain(ctx, s->rsync, [&]() {
-        return rls_gram_resident_launch(ctx, s->op->dtype, G, s->rsync, n_steps, (unsigned)ctx->tune.resident_spin, St);
-      }, &s->rsync_clean);
+      return s->resident.chain(ctx, [&](void* sync, unsigned spin) {
+        return rls_gram_resident_launch(ctx, s->op->dtype, G, sync, n_steps, spin, St);
+      });
     }
     const rls_cgnr_pipe P = cgnr_pipe_desc(s);
-    return resident_chain(ctx, s->rsync, [&]() {
-      return rls_cgnr_resident_launch(ctx, s->op->dtype, P, s->rdots, s->rsync, n_steps, (unsigned)ctx->tune.resident_spin, St);
-    }, &s->rsync_clean);
-  });
-  if (r < 0) return r;
-  if (r == 0) {
-    cgnr_status_out(s, *s->sc_h, out);
-    return 0;
-  }
-  if (r == 1) {  // nothing ran: the ordinary path
-    s->requested -= n_steps;
-    return rls_cgnr_step_status(s, n_steps, out);
-  }
-  return rls_cgnr_get_status(s, out);  // (reads the sync block's flags: iterations a lost launch did not run are re-run here)
-}
-}  // extern "C++"
-
-// One iterate per call is the reference's solve! loop with callbacks (src/RegularizedLeastSquares.jl:161-176): step and read-back
-// as ONE entry point, and on the per-iteration pipeline and the small-system kernel the call's last kernel stores the scalars into
-// the plan's pinned mirror itself -- no publishing launch behind it.
-int32_t rls_cgnr_step_status(rls_cgnr* s, int32_t n_steps, rls_cgnr_status* out) {
-  if (!s || !out) return RLS_E_INVALID;
-  rls_ctx* ctx = s->op->ctx;
-  if (cgnr_listening_q(s)) rls_server_stop(ctx);  // (queue mode: the calls of a solve! loop with callbacks take their own path)
-  // (whole-solve calls gain nothing from a kernel that stays: server mode is for the per-iterate calls of a solve! loop with callbacks)
-  if (s->initialised && n_steps > 0 && n_steps <= 8 && !s->resident_used && cgnr_use_server(s)) return cgnr_step_status_server(s, n_steps, out);
-  if (s->initialised && s->nrhs == 1 && n_steps > 0 && !s->resident_used) {
-    RLS_HIP(ctx, rls_enter(ctx));
-    s->mb_arm = rls_mailbox_arm(ctx, s->sc_h);
-  }
-  s->mb_sent = false;
-  const int32_t st = cgnr_step_call(s, n_steps, false);
-  const rls_mailbox_slot mb = s->mb_arm;
-  s->mb_arm = rls_mailbox_slot();
-  if (st != 0) return st;
-  if (!s->mb_sent) return rls_cgnr_get_status(s, out);
-  RLS_TRY(rls_mailbox_wait(ctx, mb.seq));
-  cgnr_status_out(s, *s->sc_h, out);
-  return 0;
+    return s->resident.chain(ctx, [&](void* sync, unsigned spin) {
+      return rls_cgnr_resident_launch(ctx, s->op->dtype, P, s->rdots, sync, n_steps, spin, St);
+    });
+  };
+  return step_status(s, n_steps, out, cgnr_use_server(s), serve_launch, [s](int32_t n) { s->requested += n; },
+                     [](rls_cgnr* p, int32_t n) { return cgnr_step_call(p, n, false); }, rls_cgnr_get_status, cgnr_status_out);
 }
 
 // ---- FISTA ----------------------------------------------------------------------------------
@@ -3313,14 +3241,13 @@ int32_t rls_fista_create(rls_operator* op, void* x, void* x0, void* xold, void* 
   }
   if ((op->slab && op->A && !op->G && rls_cgnr_resident_ok(ctx, op->dtype, op->M, op->N, op->A, op->lda)) ||
       (gram && rls_gram_resident_ok(ctx, op->dtype, op->N, op->G, op->ldg))) {
-    if (resident_alloc(ctx, op, &s->rsync, &s->rsync_h) != hipSuccess) {
-      if (s->rsync) dfree(s->rsync);
-      s->rsync = nullptr;  // resident mode is an optimisation: without its scratch the pipeline runs
+    if (s->resident.alloc(ctx, op) != hipSuccess) {
+      s->resident.release();  // resident mode is an optimisation: without its scratch the pipeline runs
       (void)hipGetLastError();
     } else if ((!gram || rls_gram_resident_server_ok(op->dtype, op->N)) &&
                (s->srv.ctl || hmalloc(&s->srv.ctl, 32 * sizeof(unsigned)) == hipSuccess)) {  // (both resident kernels can stay and listen)
       memset(s->srv.ctl, 0, 32 * sizeof(unsigned));
-      s->srv.resident_used = &s->resident_used;
+      s->srv.resident_used = &s->resident.used;
     }
   }
   int32_t st = alloc_scalars(ctx, &s->sc, &s->sc_h);
@@ -3343,7 +3270,7 @@ int32_t rls_fista_destroy(rls_fista* s) {
   hipSetDevice(s->device);
   if (s->srv.ctl) hfree(s->srv.ctl);
   rls_alloc_scope alloc_scope(alloc_ctx_of(s->actx, s->actx_id));
-  if (s->graph.exec) hipGraphExecDestroy(s->graph.exec);
+  s->graph.drop();
   dfree(s->y);
   if (s->y1) dfree(s->y1);
   if (s->res_raw) dfree(s->res_raw);
@@ -3353,8 +3280,7 @@ int32_t rls_fista_destroy(rls_fista* s) {
   if (s->Tpack) dfree(s->Tpack);
   if (s->Vpart) dfree(s->Vpart);
   if (s->scb_h) hfree(s->scb_h);
-  if (s->rsync) dfree(s->rsync);
-  if (s->rsync_h) hfree(s->rsync_h);
+  s->resident.release();
   if (s->fk_yx) dfree(s->fk_yx);
   if (s->fk_xx) dfree(s->fk_xx);
   if (s->fk_dots) dfree(s->fk_dots);
@@ -3368,11 +3294,7 @@ int32_t rls_fista_destroy(rls_fista* s) {
 
 // A cached graph of this plan's iteration holds the kernel SEQUENCE of its regulariser and, for TV, the threshold rho * lambda, the
 // image geometry and iterationsTV as kernel arguments (every other regulariser reads rho and lambda from the scalars on the device):
-// whatever changes one of them drops the graph, the next step call captures afresh.
-static void fista_drop_graph(rls_fista* s) {
-  if (s->graph.exec) hipGraphExecDestroy(s->graph.exec);
-  s->graph = step_graph();
-}
+// whatever changes one of them drops the graph (step_graph::drop), the next step call captures afresh.
 
 int32_t rls_fista_set_reg(rls_fista* s, int32_t reg_kind, float lambda, int64_t l21_slices, int32_t proj_kind) {
   if (!s) return RLS_E_INVALID;
@@ -3383,7 +3305,7 @@ int32_t rls_fista_set_reg(rls_fista* s, int32_t reg_kind, float lambda, int64_t 
     return rls_fail(ctx, RLS_E_INVALID, "fista_set_reg: unknown kind");
   if (reg_kind == RLS_REG_L21 && (l21_slices <= 0 || s->op->N / l21_slices == 0))
     return rls_fail(ctx, RLS_E_INVALID, "fista_set_reg: slices must be in 1..N");
-  if (s->reg_kind == RLS_REG_TV || reg_kind != s->reg_kind) fista_drop_graph(s);  // another kernel sequence (or TV's baked arguments)
+  if (s->reg_kind == RLS_REG_TV || reg_kind != s->reg_kind) s->graph.drop();  // another kernel sequence (or TV's baked arguments)
   s->reg_kind = reg_kind;
   s->proj_kind = proj_kind;
   s->lambda = lambda;
@@ -3421,7 +3343,7 @@ int32_t rls_fista_set_reg_tv(rls_fista* s, float lambda, int32_t ndims, const in
               s->tv_ntv == ntv && s->proj_kind == proj_kind;
   for (int k = 0; k < 4 && same; ++k)
     same = s->tv_shape[k] == (k < ndims ? shape[k] : 1) && s->tv_dims[k] == (k < ntv ? dims[k] : 0);
-  if (!same) fista_drop_graph(s);
+  if (!same) s->graph.drop();
   s->tv_ndims = ndims;
   s->tv_ntv = ntv;
   for (int k = 0; k < 4; ++k) {
@@ -3459,20 +3381,20 @@ static int32_t fista_init_finish(rls_fista* s, float rho, float theta, float rel
     hipLaunchKernelGGL(fista_init_kernel<float>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (float*)s->buf[0],
                        (float*)s->buf[1], (float*)s->x0, (float*)s->res, (float*)s->y, op->N, s->sc, rho, theta,
                        rel_tol, iterations, restart_gradient, s->reg_kind, s->proj_kind, s->lambda,
-                       (long long)s->l21_slices, fista_batch<float>{0, nullptr, 1, 0, nullptr, 0}, (unsigned*)s->rsync,
-                       s->rsync ? (int)(rls_resident_sync_clear_bytes() / sizeof(unsigned)) : 0);
+                       (long long)s->l21_slices, fista_batch<float>{0, nullptr, 1, 0, nullptr, 0}, (unsigned*)s->resident.sync,
+                       s->resident.sync ? (int)(rls_resident_sync_clear_bytes() / sizeof(unsigned)) : 0);
   else
     hipLaunchKernelGGL(fista_init_kernel<float2>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (float2*)s->buf[0],
                        (float2*)s->buf[1], (float2*)s->x0, (float2*)s->res, (float2*)s->y, op->N, s->sc, rho,
                        theta, rel_tol, iterations, restart_gradient, s->reg_kind, s->proj_kind, s->lambda,
-                       (long long)s->l21_slices, fista_batch<float2>{0, nullptr, 1, 0, nullptr, 0}, (unsigned*)s->rsync,
-                       s->rsync ? (int)(rls_resident_sync_clear_bytes() / sizeof(unsigned)) : 0);
-  s->rsync_clean = s->rsync != nullptr;
+                       (long long)s->l21_slices, fista_batch<float2>{0, nullptr, 1, 0, nullptr, 0}, (unsigned*)s->resident.sync,
+                       s->resident.sync ? (int)(rls_resident_sync_clear_bytes() / sizeof(unsigned)) : 0);
+  s->resident.clean = s->resident.sync != nullptr;
   s->enq = 0;
   s->requested = 0;
   s->theta0 = theta;
   if (s->reg_kind == RLS_REG_TV) {
-    if (rho != s->rho_h) fista_drop_graph(s);  // rho * lambda is an argument of the captured FGP launch
+    if (rho != s->rho_h) s->graph.drop();  // rho * lambda is an argument of the captured FGP launch
     // the single-workgroup FGP kernel was checked when the regulariser was set; its limits are context tunables that may have moved
     if (!rls_tv_single_ok(op->ctx, op->dtype, s->tv_ndims, s->tv_shape, s->tv_ntv, s->tv_dims))
       return rls_fail(ctx, RLS_E_UNSUPPORTED, "fista_init: the TV image no longer fits the single-workgroup FGP kernel");
@@ -3484,10 +3406,7 @@ static int32_t fista_init_finish(rls_fista* s, float rho, float theta, float rel
   // row-sharded plans exchange `res` between the operator apply and the update: two-half iterations only
   const bool gram = !local && fista_gram_ok(s);
   const bool pipe = !local && !gram && fista_pipe_ok(s);
-  if ((pipe != s->use_pipe || gram != s->use_gram) && s->graph.exec) {  // captured for another kernel sequence
-    hipGraphExecDestroy(s->graph.exec);
-    s->graph = step_graph();
-  }
+  if ((pipe != s->use_pipe || gram != s->use_gram) && s->graph.exec) s->graph.drop();  // captured for another kernel sequence
   s->use_pipe = pipe;
   s->use_gram = gram;
   return launch_status(ctx);
@@ -3576,7 +3495,7 @@ int32_t rls_fista_create_batched(rls_operator* op, int32_t nrhs, void* x, void* 
   if (e == hipSuccess && op->G && s->half && vec16 && rls_fgramk_resident_ok(ctx, op->dtype, op->N, nrhs, op->G, op->ldg)) {
     size_t yxb, xxb, db;
     rls_fgramk_sizes(op->N, &yxb, &xxb, &db);
-    e = resident_alloc(ctx, op, &s->rsync, &s->rsync_h);
+    e = s->resident.alloc(ctx, op);
     if (e == hipSuccess) e = dmalloc(&s->fk_yx, yxb);
     if (e == hipSuccess) e = hipMemsetAsync(s->fk_yx, 0, yxb, ctx->stream);  // rows >= N are read, never written
     if (e == hipSuccess) e = dmalloc(&s->fk_xx, xxb);
@@ -3585,8 +3504,7 @@ int32_t rls_fista_create_batched(rls_operator* op, int32_t nrhs, void* x, void* 
     s->fgramk = e == hipSuccess;
   }
   if (e != hipSuccess) {
-    if (s->rsync) dfree(s->rsync);
-    if (s->rsync_h) hfree(s->rsync_h);
+    s->resident.release();
     if (s->fk_yx) dfree(s->fk_yx);
     if (s->fk_xx) dfree(s->fk_xx);
     if (s->fk_dots) dfree(s->fk_dots);
@@ -3614,64 +3532,36 @@ int32_t rls_fista_init_batched(rls_fista* s, const void* B, int64_t ldb, float r
   RLS_HIP(ctx, rls_enter(ctx));
   RLS_TRY(rls_skinny_atb(ctx, op->dtype, fista_skinny_desc(s), B, ldb));  // partial rows of A^H B   (src/FISTA.jl:114)
   // (the resident launch's arrival counters are zeroed by the init kernel: every workgroup writes the same zeros)
-  const int n_clear = s->rsync ? (int)(rls_resident_sync_clear_bytes() / sizeof(unsigned)) : 0;
+  const int n_clear = s->resident.sync ? (int)(rls_resident_sync_clear_bytes() / sizeof(unsigned)) : 0;
   if (op->dtype == RLS_F32)
     hipLaunchKernelGGL(fista_init_kernel<float>, dim3((unsigned)s->nrhs), dim3(UPD_THREADS), 0, ctx->stream,
                        (float*)s->buf[0], (float*)s->buf[1], (float*)s->x0, (float*)s->res, (float*)s->y, op->N, s->sc,
                        rho, theta, rel_tol, iterations, restart_gradient, s->reg_kind, s->proj_kind, s->lambda,
-                       (long long)s->l21_slices, fista_batch_desc<float>(s), (unsigned*)s->rsync, n_clear);
+                       (long long)s->l21_slices, fista_batch_desc<float>(s), (unsigned*)s->resident.sync, n_clear);
   else
     hipLaunchKernelGGL(fista_init_kernel<float2>, dim3((unsigned)s->nrhs), dim3(UPD_THREADS), 0, ctx->stream,
                        (float2*)s->buf[0], (float2*)s->buf[1], (float2*)s->x0, (float2*)s->res, (float2*)s->y, op->N,
                        s->sc, rho, theta, rel_tol, iterations, restart_gradient, s->reg_kind, s->proj_kind, s->lambda,
-                       (long long)s->l21_slices, fista_batch_desc<float2>(s), (unsigned*)s->rsync, n_clear);
+                       (long long)s->l21_slices, fista_batch_desc<float2>(s), (unsigned*)s->resident.sync, n_clear);
   s->initialised = true;
   s->use_pipe = s->use_gram = false;
   s->restart_b = restart_gradient;
-  s->rsync_clean = s->rsync != nullptr;
+  s->resident.clean = s->resident.sync != nullptr;
   s->requested = 0;
   s->enq = 0;
-  s->resident_used = false;
+  s->resident.used = false;
   return launch_status(ctx);
 }
 
 static int32_t fista_step_impl(rls_fista* s, int32_t n_steps);
+static void fista_status_out(const rls_fista* s, const fista_scalars& h, rls_fista_status* out);
 int32_t rls_fista_get_status_batched(rls_fista* s, rls_fista_status* out) {
   if (!s || !out) return RLS_E_INVALID;
   rls_ctx* ctx = s->op->ctx;
   if (!s->initialised || !s->scb_h) return rls_fail(ctx, RLS_E_STATE, "fista_get_status_batched: not a batched, initialised plan");
   RLS_HIP(ctx, rls_enter(ctx));
-  if (s->resident_used) RLS_TRY(resident_fetch_flags(ctx, s->rsync, s->rsync_h));
-  RLS_TRY(rls_fetch_add(ctx, s->sc, s->scb_h, sizeof(fista_scalars) * (size_t)s->nrhs));
-  RLS_TRY(rls_fetch_wait(ctx));
-  if (s->resident_used && resident_lost(ctx, s->rsync, s->rsync_h, &s->resident_off, &s->fallbacks)) {
-    // a lost resident launch changed nothing (rls_cgnr_get_status_batched): the live columns are in lockstep, what is missing
-    // is re-run on the streaming kernels
-    long long at = 0;
-    bool live = false;
-    for (int b = 0; b < s->nrhs; ++b) {
-      if (s->scb_h[b].iteration > at) at = s->scb_h[b].iteration;
-      live = live || !s->scb_h[b].done;
-    }
-    const long long missing = s->requested - at;
-    if (live && missing > 0) {
-      RLS_TRY(fista_step_impl(s, (int32_t)(missing > 0x7fffffff ? 0x7fffffff : missing)));
-      RLS_TRY(rls_fetch_add(ctx, s->sc, s->scb_h, sizeof(fista_scalars) * (size_t)s->nrhs));
-      RLS_TRY(rls_fetch_wait(ctx));
-    }
-  }
-  s->resident_used = false;
-  for (int b = 0; b < s->nrhs; ++b) {
-    const fista_scalars& h = s->scb_h[b];
-    out[b].iteration = h.iteration;
-    out[b].done = h.done;
-    out[b].theta = h.theta;
-    out[b].theta_old = h.theta_old;
-    out[b].rel_res_norm = (float)h.rel_res_norm;
-    out[b].residual = (float)h.res_norm;
-    out[b].norm_x0 = (float)h.norm_x0;
-    out[b].fallbacks = s->fallbacks;
-  }
+  RLS_TRY(status_read(ctx, s, s->scb_h, s->nrhs, [s](int32_t n) { return fista_step_impl(s, n); }, [](long long) {}));
+  for (int b = 0; b < s->nrhs; ++b) fista_status_out(s, s->scb_h[b], out + b);
   return 0;
 }
 
@@ -3693,7 +3583,7 @@ int32_t rls_fista_set_start(rls_fista* s, const void* x_init, int64_t n) {
 
 static bool fista_use_resident(const rls_fista* s);
 static bool fista_use_gram_resident(const rls_fista* s) {
-  return s->nrhs == 1 && s->use_gram && s->rsync && !s->resident_off && s->op->ctx->tune.resident;
+  return s->nrhs == 1 && s->use_gram && s->resident.usable(s->op->ctx);
 }
 
 // small systems: the whole step call as a single-workgroup launch, A in ONE CU's registers (as cgnr_use_small), for the
@@ -3703,9 +3593,29 @@ static bool fista_use_gram_resident(const rls_fista* s) {
 // batched Gram mode as ONE resident launch per step call (cgnr_use_gramk): no gradient restart -- its theta is the one global
 // scalar the distributed update would have to wait for -- and the elementwise regularisers
 static bool fista_use_gramk(const rls_fista* s, int n_steps) {
-  return s->fgramk && s->rsync && !s->resident_off && s->op->ctx->tune.resident && !s->restart_b &&
+  return s->fgramk && s->resident.usable(s->op->ctx) && !s->restart_b &&
          (s->reg_kind == RLS_REG_NONE || s->reg_kind == RLS_REG_L1 || s->reg_kind == RLS_REG_L2) &&
          (n_steps != 1 || s->op->ctx->tune.resident == 2);
+}
+
+static rls_fgramk fista_gramk_desc(const rls_fista* s) {
+  rls_fgramk D;
+  D.G = s->op->G;
+  D.ldg = s->op->ldg;
+  D.N = s->op->N;
+  D.nrhs = s->nrhs;
+  D.b0 = s->buf[0];
+  D.b1 = s->buf[1];
+  D.x0 = s->x0;
+  D.res = s->res;
+  D.y = s->y;
+  D.ldv = s->ldv;
+  D.sc = s->sc;
+  D.Yx = s->fk_yx;
+  D.Xx = s->fk_xx;
+  D.dots = s->fk_dots;
+  D.Ypack = s->Ypack;
+  return D;
 }
 
 static bool fista_use_small(const rls_fista* s) {
@@ -3726,26 +3636,8 @@ static int32_t fista_step_impl(rls_fista* s, int32_t n_steps) {
   }
   if (fista_use_gramk(s, n_steps)) {  // AHA explicit, <= 8 columns: the whole call as ONE launch (fista_gramk_resident_kernel)
     if (n_steps == 0) return 0;
-    rls_fgramk D;
-    D.G = s->op->G;
-    D.ldg = s->op->ldg;
-    D.N = s->op->N;
-    D.nrhs = s->nrhs;
-    D.b0 = s->buf[0];
-    D.b1 = s->buf[1];
-    D.x0 = s->x0;
-    D.res = s->res;
-    D.y = s->y;
-    D.ldv = s->ldv;
-    D.sc = s->sc;
-    D.Yx = s->fk_yx;
-    D.Xx = s->fk_xx;
-    D.dots = s->fk_dots;
-    D.Ypack = s->Ypack;
-    s->resident_used = true;
-    return resident_chain(ctx, s->rsync, [&]() {
-      return rls_fgramk_resident_launch(ctx, D, s->rsync, n_steps, (unsigned)ctx->tune.resident_spin);
-    }, &s->rsync_clean);
+    const rls_fgramk D = fista_gramk_desc(s);
+    return s->resident.launch(ctx, [&](void* sync, unsigned spin) { return rls_fgramk_resident_launch(ctx, D, sync, n_steps, spin); });
   }
   if (s->nrhs > 1) {  // K columns share A: T = A Y, V = A^H T on the matrix cores, then one workgroup per column
     return run_steps(ctx, &s->graph, n_steps, [s]() { return fista_enqueue_batched(s); });
@@ -3757,18 +3649,13 @@ static int32_t fista_step_impl(rls_fista* s, int32_t n_steps) {
     const int32_t dtype = s->op->dtype;
     if (fista_use_gram_resident(s)) {  // the whole call as ONE launch, AHA in registers (fista_gram_resident_kernel)
       if (n_steps == 0) return 0;
-      s->resident_used = true;
       s->enq += n_steps;
-      return resident_chain(ctx, s->rsync, [&]() {
-        return rls_fista_gram_resident_launch(ctx, dtype, P, s->rsync, n_steps, (unsigned)ctx->tune.resident_spin);
-      }, &s->rsync_clean);
+      return s->resident.launch(ctx, [&](void* sync, unsigned spin) {
+        return rls_fista_gram_resident_launch(ctx, dtype, P, sync, n_steps, spin);
+      });
     }
     const int it0 = s->enq;  // buffer hints as in the slab pipeline below
-    if (s->graph.exec && s->graph_parity != (it0 & 1)) {
-      hipGraphExecDestroy(s->graph.exec);
-      s->graph = step_graph();
-    }
-    s->graph_parity = it0 & 1;
+    s->graph.keep_for(it0 & 1);
     int parity = 0, k = 0;
     auto one = [ctx, dtype, &P, &parity, &k, it0]() {
       const int hk = pipe_cur_hint(ctx, k);
@@ -3791,11 +3678,10 @@ static int32_t fista_step_impl(rls_fista* s, int32_t n_steps) {
     // the whole call as ONE launch, A held in registers (normal.hip, fista_resident_kernel)
     if (n_steps == 0) return 0;
     const rls_fista_pipe P = fista_pipe_desc(s);
-    s->resident_used = true;
     s->enq += n_steps;
-    return resident_chain(ctx, s->rsync, [&]() {
-      return rls_fista_resident_launch(ctx, s->op->dtype, P, s->rsync, n_steps, (unsigned)ctx->tune.resident_spin);
-    }, &s->rsync_clean);
+    return s->resident.launch(ctx, [&](void* sync, unsigned spin) {
+      return rls_fista_resident_launch(ctx, s->op->dtype, P, sync, n_steps, spin);
+    });
   }
   if (s->use_pipe) {
     // iteration k = K_A (applies the gradient/prox/momentum update k-1 in its prologue, then one pass
@@ -3805,11 +3691,7 @@ static int32_t fista_step_impl(rls_fista* s, int32_t n_steps) {
     // buffer hints: launch k >= 1 of this call finds iteration count enq + k - 1 (launch 0 applies nothing); the
     // hints a cached graph carries belong to the parity of `enq` it was captured with
     const int it0 = s->enq;
-    if (s->graph.exec && s->graph_parity != (it0 & 1)) {
-      hipGraphExecDestroy(s->graph.exec);
-      s->graph = step_graph();
-    }
-    s->graph_parity = it0 & 1;
+    s->graph.keep_for(it0 & 1);
     int k = 0;
     RLS_TRY(run_steps(ctx, &s->graph, n_steps, [ctx, dtype, &P, &k, it0]() {
       const int h = pipe_cur_hint(ctx, k);  // -1 where the position may be replayed out of sequence
@@ -3837,27 +3719,14 @@ int32_t rls_fista_step(rls_fista* s, int32_t n_steps) {
 }
 
 static bool fista_use_resident(const rls_fista* s) {
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  return s->nrhs == 1 && s->use_pipe && s->rsync && !s->resident_off && s->op->ctx->tune.resident && al16(s->buf[0]) &&
-         al16(s->buf[1]) && al16(s->x0) && al16(s->res);
+  return s->nrhs == 1 && s->use_pipe && s->resident.usable(s->op->ctx) && aligned16(s->buf[0], s->buf[1], s->x0, s->res);
 }
 
 // status read-back of a single-column plan; re-runs on the per-iteration pipeline whatever a lost resident launch left
 // undone (cgnr_fetch_status)
 static int32_t fista_fetch_status(rls_fista* s) {
-  rls_ctx* ctx = s->op->ctx;
-  if (s->resident_used) RLS_TRY(resident_fetch_flags(ctx, s->rsync, s->rsync_h));
-  RLS_TRY(fetch_scalars(ctx, s->sc, s->sc_h));
-  if (s->resident_used && resident_lost(ctx, s->rsync, s->rsync_h, &s->resident_off, &s->fallbacks)) {
-    const long long missing = s->requested - (long long)s->sc_h->iteration;
-    s->enq = s->sc_h->iteration;  // the buffer-parity hints of the pipeline follow the device's count
-    if (!s->sc_h->done && missing > 0) {
-      RLS_TRY(fista_step_impl(s, (int32_t)(missing > 0x7fffffff ? 0x7fffffff : missing)));
-      RLS_TRY(fetch_scalars(ctx, s->sc, s->sc_h));
-    }
-  }
-  s->resident_used = false;
-  return 0;
+  return status_read(s->op->ctx, s, s->sc_h, 1, [s](int32_t n) { return fista_step_impl(s, n); },
+                     [s](long long at) { s->enq = (int)at; });  // the buffer-parity hints of the pipeline follow the device's count
 }
 
 int32_t rls_fista_path(rls_fista* s, int32_t* out) {
@@ -3874,7 +3743,7 @@ static void fista_status_out(const rls_fista* s, const fista_scalars& h, rls_fis
   out->rel_res_norm = (float)h.rel_res_norm;
   out->residual = (float)h.res_norm;
   out->norm_x0 = (float)h.norm_x0;
-  out->fallbacks = s->fallbacks;
+  out->fallbacks = s->resident.fallbacks;
 }
 
 int32_t rls_fista_get_status(rls_fista* s, rls_fista_status* out) {
@@ -3894,56 +3763,28 @@ int32_t rls_fista_get_status(rls_fista* s, rls_fista_status* out) {
 int32_t rls_fista_step_status(rls_fista* s, int32_t n_steps, rls_fista_status* out) {  // as rls_cgnr_step_status
   if (!s || !out) return RLS_E_INVALID;
   rls_ctx* ctx = s->op->ctx;
-  if (s->initialised && n_steps > 0 && n_steps <= 8 && !s->resident_used && server_usable(ctx, &s->srv) &&
-      (fista_use_small(s) || fista_use_gram_resident(s) || fista_use_resident(s))) {
-    // the resident kernel in server mode (cgnr_step_status_server): posted to the kernel left listening, or carried by a launch
-    RLS_HIP(ctx, hipSetDevice(s->device));
-    s->requested += n_steps;
-    s->enq += n_steps;
-    const int32_t r = server_command(ctx, &s->srv, s->sc_h, n_steps, true, [&](const rls_srv_args& a) {
-      rls_fista_pipe P = fista_pipe_desc(s);
-      if (fista_use_small(s)) {  // the single-workgroup kernel: one CU stays, nothing to chain
-        if (!P.y1) P.y1 = P.y0;
-        P.mb = a.mb;
-        return rls_fista_small_launch(ctx, s->op->dtype, P, n_steps, a);
-      }
-      rls_srv_args ar = a;  // (the resident kernels take the idle time as it is: the run-ahead choice is their instantiation)
-      ar.idle_us &= ~RLS_SRV_AHEAD;
-      if (fista_use_gram_resident(s)) {  // AHA explicit, in the register files (fista_gram_resident_kernel)
-        const rls_fista_gram Pg = fista_gram_desc(s);
-        return resident_chain(ctx, s->rsync, [&]() {
-          return rls_fista_gram_resident_launch(ctx, s->op->dtype, Pg, s->rsync, n_steps, (unsigned)ctx->tune.resident_spin, ar);
-        }, &s->rsync_clean);
-      }
-      return resident_chain(ctx, s->rsync, [&]() {
-        return rls_fista_resident_launch(ctx, s->op->dtype, P, s->rsync, n_steps, (unsigned)ctx->tune.resident_spin, ar);
-      }, &s->rsync_clean);
+  auto serve_launch = [&](const rls_srv_args& a) {
+    rls_fista_pipe P = fista_pipe_desc(s);
+    if (fista_use_small(s)) {  // the single-workgroup kernel: one CU stays, nothing to chain
+      if (!P.y1) P.y1 = P.y0;
+      P.mb = a.mb;
+      return rls_fista_small_launch(ctx, s->op->dtype, P, n_steps, a);
+    }
+    rls_srv_args ar = a;  // (the resident kernels take the idle time as it is: the run-ahead choice is their instantiation)
+    ar.idle_us &= ~RLS_SRV_AHEAD;
+    if (fista_use_gram_resident(s)) {  // AHA explicit, in the register files (fista_gram_resident_kernel)
+      const rls_fista_gram Pg = fista_gram_desc(s);
+      return s->resident.chain(ctx, [&](void* sync, unsigned spin) {
+        return rls_fista_gram_resident_launch(ctx, s->op->dtype, Pg, sync, n_steps, spin, ar);
+      });
+    }
+    return s->resident.chain(ctx, [&](void* sync, unsigned spin) {
+      return rls_fista_resident_launch(ctx, s->op->dtype, P, sync, n_steps, spin, ar);
     });
-    if (r < 0) return r;
-    if (r == 0) {
-      fista_status_out(s, *s->sc_h, out);
-      return 0;
-    }
-    if (r == 1) {  // nothing ran: the ordinary path
-      s->requested -= n_steps;
-      s->enq -= n_steps;
-      return rls_fista_step_status(s, n_steps, out);
-    }
-    return rls_fista_get_status(s, out);  // a launch gave up inside the command: the lost-launch recovery re-runs it
-  }
-  if (s->initialised && s->nrhs == 1 && n_steps > 0 && !s->resident_used) {
-    RLS_HIP(ctx, rls_enter(ctx));
-    s->mb_arm = rls_mailbox_arm(ctx, s->sc_h);
-  }
-  s->mb_sent = false;
-  const int32_t st = rls_fista_step(s, n_steps);
-  const rls_mailbox_slot mb = s->mb_arm;
-  s->mb_arm = rls_mailbox_slot();
-  if (st != 0) return st;
-  if (!s->mb_sent) return rls_fista_get_status(s, out);
-  RLS_TRY(rls_mailbox_wait(ctx, mb.seq));
-  fista_status_out(s, *s->sc_h, out);
-  return 0;
+  };
+  const bool serve = server_usable(ctx, &s->srv) && (fista_use_small(s) || fista_use_gram_resident(s) || fista_use_resident(s));
+  return step_status(s, n_steps, out, serve, serve_launch, [s](int32_t n) { s->requested += n; s->enq += n; }, rls_fista_step,
+                     rls_fista_get_status, fista_status_out);
 }
 
 int32_t rls_fista_solution(rls_fista* s, void** x_out) {
@@ -3998,20 +3839,18 @@ int32_t rls_cg_create(rls_operator* op, void* u, void* r, void* c, rls_cg** out)
       return rls_fail(ctx, (int32_t)e, "cg_create: hipMalloc failed");
     }
     if (rls_gram_resident_ok(ctx, op->dtype, op->N, op->G, op->ldg)) {
-      if (resident_alloc(ctx, op, &s->rsync, &s->rsync_h) == hipSuccess) {
+      if (s->resident.alloc(ctx, op) == hipSuccess) {
         s->gram_resident = true;
       } else {
-        if (s->rsync) dfree(s->rsync);
-        s->rsync = nullptr;  // an optimisation only: the one-launch-per-iteration pipeline runs without it
+        s->resident.release();  // an optimisation only: the one-launch-per-iteration pipeline runs without it
         (void)hipGetLastError();
       }
     }
   } else if (op->slab) {
     if (op->A && rls_cgnr_resident_ok(ctx, op->dtype, op->M, op->N, op->A, op->lda)) {
       const size_t db = (size_t)rls_cgnr_resident_nwg(op->ctx, op->dtype, op->M, op->N) * 4 * sizeof(double);
-      if (resident_alloc(ctx, op, &s->rsync, &s->rsync_h) != hipSuccess || dmalloc(&s->rdots, db) != hipSuccess) {
-        if (s->rsync) dfree(s->rsync);
-        s->rsync = nullptr;  // an optimisation only: the two-launch pipeline runs without it
+      if (s->resident.alloc(ctx, op) != hipSuccess || dmalloc(&s->rdots, db) != hipSuccess) {
+        s->resident.release();  // an optimisation only: the two-launch pipeline runs without it
         (void)hipGetLastError();
       }
     }
@@ -4079,13 +3918,12 @@ int32_t rls_cg_destroy(rls_cg* s) {
   if (!s) return RLS_E_INVALID;
   hipSetDevice(s->device);
   rls_alloc_scope alloc_scope(alloc_ctx_of(s->actx, s->actx_id));
-  if (s->graph.exec) hipGraphExecDestroy(s->graph.exec);
+  s->graph.drop();
   if (s->Ppack) dfree(s->Ppack);
   if (s->Tpack) dfree(s->Tpack);
   if (s->Vpart) dfree(s->Vpart);
-  if (s->rsync) dfree(s->rsync);
+  s->resident.release();
   if (s->rdots) dfree(s->rdots);
-  if (s->rsync_h) hfree(s->rsync_h);
   if (s->r1) dfree(s->r1);
   if (s->p1) dfree(s->p1);
   if (s->dots) dfree(s->dots);
@@ -4171,11 +4009,8 @@ struct rls_pgm {
   rls_ctx* actx;
   uint64_t actx_id = 0;
   int device;
-  void* rsync = nullptr;
-  unsigned* rsync_h = nullptr;
+  resident_slot resident;  // (`used` stays false: the caller asks rls_pgm_lost behind its launches)
   void* raw = nullptr;
-  bool resident_off = false;
-  int fallbacks = 0;
 };
 
 int32_t rls_pgm_create(rls_operator* op, rls_pgm** out) {
@@ -4191,11 +4026,10 @@ int32_t rls_pgm_create(rls_operator* op, rls_pgm** out) {
   s->actx = ctx;
   s->actx_id = ctx->id;
   s->device = ctx->device;
-  hipError_t e = resident_alloc(ctx, op, &s->rsync, &s->rsync_h);
+  hipError_t e = s->resident.alloc(ctx, op);
   if (e == hipSuccess) e = dmalloc(&s->raw, (size_t)op->N * rls_elem_size(op->dtype));
   if (e != hipSuccess) {
-    if (s->rsync) dfree(s->rsync);
-    if (s->rsync_h) hfree(s->rsync_h);
+    s->resident.release();
     if (s->raw) dfree(s->raw);
     delete s;
     (void)hipGetLastError();
@@ -4209,30 +4043,16 @@ int32_t rls_pgm_destroy(rls_pgm* s) {
   if (!s) return RLS_E_INVALID;
   hipSetDevice(s->device);
   rls_alloc_scope alloc_scope(alloc_ctx_of(s->actx, s->actx_id));
-  dfree(s->rsync);
+  s->resident.release();
   dfree(s->raw);
-  hfree(s->rsync_h);
   delete s;
   return 0;
 }
 
-int32_t rls_pgm_step_resident(rls_pgm* s, int32_t kind, int32_t n_steps, int32_t first_iteration, const float* coefs, void* v0,
-                              void* v1, void* v2, void* o0, void* res, const void* x0, int32_t reg_kind, int32_t proj_kind,
-                              float norm_x0, float rel_tol, void* state_d) {
-  if (!s) return RLS_E_INVALID;
-  rls_ctx* ctx = s->op->ctx;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  if ((kind != 0 && kind != 1) || n_steps < 0 || n_steps > RLS_PGM_MAX_IT || first_iteration < 0 || !coefs || !v0 || !v1 || !v2 ||
-      !o0 || !res || !x0 || !state_d || reg_kind < RLS_REG_NONE || reg_kind > RLS_REG_L2 || proj_kind < RLS_PROJ_NONE ||
-      proj_kind > RLS_PROJ_POSITIVE || (kind == 0 && proj_kind != RLS_PROJ_NONE))
-    return rls_fail(ctx, RLS_E_INVALID, "pgm_step_resident: bad argument");
-  if (!(al16(v0) && al16(v1) && al16(v2) && al16(o0) && al16(res) && al16(x0)))
-    return rls_fail(ctx, RLS_E_INVALID, "pgm_step_resident: vectors must be 16-byte aligned");
-  if (s->resident_off || !ctx->tune.resident) return RLS_E_UNSUPPORTED;  // lost a launch earlier: per-iteration launches
-  if (n_steps == 0) return 0;
-  RLS_HIP(ctx, rls_enter(ctx));
-  rls_pgm_coefs C;
-  memcpy(C.c, coefs, sizeof(float) * 8 * (size_t)n_steps);
+// the launch's view of the caller's state: `kind` 0 = OptISTA (v0..v2 = x, y, z; o0 = zold), 1 / 2 = POGM (x, y, z; o0 = xold;
+// kind 2 also w in D.v3)
+static rls_pgm_desc pgm_desc(const rls_pgm* s, int kind, void* v0, void* v1, void* v2, void* o0, void* res, const void* x0,
+                             int32_t reg_kind, int32_t proj_kind, float norm_x0, float rel_tol, void* state_d, int32_t first_iteration) {
   rls_pgm_desc D;
   D.A = s->op->A;
   D.lda = s->op->lda;
@@ -4253,9 +4073,34 @@ int32_t rls_pgm_step_resident(rls_pgm* s, int32_t kind, int32_t n_steps, int32_t
   D.reg_kind = reg_kind;
   D.proj_kind = proj_kind;
   D.first_it = first_iteration;
-  return resident_chain(ctx, s->rsync, [&]() {
-    return rls_pgm_resident_launch(ctx, s->op->dtype, D, C, s->rsync, n_steps, (unsigned)ctx->tune.resident_spin);
+  return D;
+}
+// (not through resident_slot::launch: the caller accounts for its launches itself, rls_pgm_lost)
+static int32_t pgm_launch(rls_pgm* s, const rls_pgm_desc& D, const rls_pgm_coefs& C, int32_t n_steps) {
+  rls_ctx* ctx = s->op->ctx;
+  return s->resident.chain(ctx, [&](void* sync, unsigned spin) {
+    return rls_pgm_resident_launch(ctx, s->op->dtype, D, C, sync, n_steps, spin);
   });
+}
+
+int32_t rls_pgm_step_resident(rls_pgm* s, int32_t kind, int32_t n_steps, int32_t first_iteration, const float* coefs, void* v0,
+                              void* v1, void* v2, void* o0, void* res, const void* x0, int32_t reg_kind, int32_t proj_kind,
+                              float norm_x0, float rel_tol, void* state_d) {
+  if (!s) return RLS_E_INVALID;
+  rls_ctx* ctx = s->op->ctx;
+  if ((kind != 0 && kind != 1) || n_steps < 0 || n_steps > RLS_PGM_MAX_IT || first_iteration < 0 || !coefs || !v0 || !v1 || !v2 ||
+      !o0 || !res || !x0 || !state_d || reg_kind < RLS_REG_NONE || reg_kind > RLS_REG_L2 || proj_kind < RLS_PROJ_NONE ||
+      proj_kind > RLS_PROJ_POSITIVE || (kind == 0 && proj_kind != RLS_PROJ_NONE))
+    return rls_fail(ctx, RLS_E_INVALID, "pgm_step_resident: bad argument");
+  if (!aligned16(v0, v1, v2, o0, res, x0))
+    return rls_fail(ctx, RLS_E_INVALID, "pgm_step_resident: vectors must be 16-byte aligned");
+  if (s->resident.off || !ctx->tune.resident) return RLS_E_UNSUPPORTED;  // lost a launch earlier: per-iteration launches
+  if (n_steps == 0) return 0;
+  RLS_HIP(ctx, rls_enter(ctx));
+  rls_pgm_coefs C;
+  memcpy(C.c, coefs, sizeof(float) * 8 * (size_t)n_steps);
+  return pgm_launch(s, pgm_desc(s, kind, v0, v1, v2, o0, res, x0, reg_kind, proj_kind, norm_x0, rel_tol, state_d, first_iteration), C,
+                    n_steps);
 }
 
 // POGM with restart = :gradient as resident launches: theta, sigma, gamma live in the record (pogm_auto_state) and the kernel
@@ -4267,13 +4112,12 @@ int32_t rls_pogm_step_resident_restart(rls_pgm* s, int32_t n_steps, int32_t firs
                                        void* state_d) {
   if (!s) return RLS_E_INVALID;
   rls_ctx* ctx = s->op->ctx;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   if (n_steps < 0 || first_iteration < 0 || iterations < 1 || iterations >= (1 << 24) || !xbuf || !ybuf || !z || !w || !xold || !res ||
       !x0 || !state_d || reg_kind < RLS_REG_NONE || reg_kind > RLS_REG_L2 || proj_kind < RLS_PROJ_NONE || proj_kind > RLS_PROJ_POSITIVE)
     return rls_fail(ctx, RLS_E_INVALID, "pogm_step_resident_restart: bad argument");
-  if (!(al16(xbuf) && al16(ybuf) && al16(z) && al16(w) && al16(xold) && al16(res) && al16(x0)))
+  if (!aligned16(xbuf, ybuf, z, w, xold, res, x0))
     return rls_fail(ctx, RLS_E_INVALID, "pogm_step_resident_restart: vectors must be 16-byte aligned");
-  if (s->resident_off || !ctx->tune.resident) return RLS_E_UNSUPPORTED;
+  if (s->resident.off || !ctx->tune.resident) return RLS_E_UNSUPPORTED;
   if (n_steps == 0) return 0;
   RLS_HIP(ctx, rls_enter(ctx));
   rls_pgm_coefs C;
@@ -4281,30 +4125,9 @@ int32_t rls_pogm_step_resident_restart(rls_pgm* s, int32_t n_steps, int32_t firs
   C.c[0][1] = lambda;
   C.c[0][2] = sigma_fac;
   C.c[0][3] = (float)iterations;  // (exact: < 2^24)
-  rls_pgm_desc D;
-  D.A = s->op->A;
-  D.lda = s->op->lda;
-  D.M = s->op->M;
-  D.N = s->op->N;
-  D.kind = 2;
-  D.v0 = xbuf;
-  D.v1 = ybuf;
-  D.v2 = z;
+  rls_pgm_desc D = pgm_desc(s, 2, xbuf, ybuf, z, xold, res, x0, reg_kind, proj_kind, norm_x0, rel_tol, state_d, first_iteration);
   D.v3 = w;
-  D.o0 = xold;
-  D.res = res;
-  D.x0 = x0;
-  D.slab = s->op->slab;
-  D.raw = s->raw;
-  D.st = (pgm_state*)state_d;
-  D.norm_x0 = norm_x0;
-  D.rel_tol = rel_tol;
-  D.reg_kind = reg_kind;
-  D.proj_kind = proj_kind;
-  D.first_it = first_iteration;
-  return resident_chain(ctx, s->rsync, [&]() {
-    return rls_pgm_resident_launch(ctx, s->op->dtype, D, C, s->rsync, n_steps, (unsigned)ctx->tune.resident_spin);
-  });
+  return pgm_launch(s, D, C, n_steps);
 }
 
 // after the launches of a sequence: how many of them gave up (bounded wait; they changed nothing).  Synchronises.
@@ -4312,17 +4135,17 @@ int32_t rls_pgm_lost(rls_pgm* s, int32_t* lost, int32_t* fallbacks_total) {
   if (!s || !lost) return RLS_E_INVALID;
   rls_ctx* ctx = s->op->ctx;
   RLS_HIP(ctx, rls_enter(ctx));
-  RLS_TRY(resident_fetch_flags(ctx, s->rsync, s->rsync_h));
+  RLS_TRY(s->resident.fetch_flags(ctx));
   RLS_TRY(rls_fetch_wait(ctx));
-  *lost = (int32_t)resident_lost(ctx, s->rsync, s->rsync_h, &s->resident_off, &s->fallbacks);
-  if (fallbacks_total) *fallbacks_total = s->fallbacks;
+  *lost = (int32_t)s->resident.lost(ctx);
+  if (fallbacks_total) *fallbacks_total = s->resident.fallbacks;
   return 0;
 }
 
 int32_t rls_cg_path(rls_cg* s, int32_t* out) {
   if (!s || !out) return RLS_E_INVALID;
   const rls_ctx* ctx = s->op->ctx;
-  const bool res = s->rsync && !s->resident_off && ctx->tune.resident;
+  const bool res = s->resident.usable(ctx);
   if (s->nrhs > 1 || s->Vpart) *out = 3;
   else if (cg_use_gram_pipeline(s)) *out = (res && s->gram_resident) ? 5 : 2;
   else if (cg_use_pipeline(s)) *out = res ? 4 : 1;
@@ -4334,15 +4157,14 @@ int32_t rls_cg_get_status(rls_cg* s, rls_cg_status* out) {
   if (!s || !out) return RLS_E_INVALID;
   rls_ctx* ctx = s->op->ctx;
   RLS_HIP(ctx, rls_enter(ctx));
-  out->fallbacks = s->fallbacks;
-  if (s->resident_used) {
+  if (s->resident.used) {
     // a lost resident launch left x at its warm start: repeat the solve on the per-iteration pipeline
-    RLS_TRY(resident_fetch_flags(ctx, s->rsync, s->rsync_h));
+    RLS_TRY(s->resident.fetch_flags(ctx));
     RLS_TRY(rls_fetch_wait(ctx));
-    if (resident_lost(ctx, s->rsync, s->rsync_h, &s->resident_off, &s->fallbacks) && s->last.valid)
+    if (s->resident.lost(ctx) && s->last.valid)
       RLS_TRY(cg_solve_impl(s, s->last.x, s->last.b, s->last.rho, s->last.maxiter, s->last.reltol, admm_fuse_v()));
-    out->fallbacks = s->fallbacks;
   }
+  out->fallbacks = s->resident.fallbacks;
   if (s->used_pipeline) {
     RLS_TRY(fetch_scalars(ctx, s->psc, s->psc_h));
     out->iterations = s->psc_h->iteration;
@@ -4673,13 +4495,13 @@ int32_t rls_admm_get_status(rls_admm* a, rls_admm_status* out, float* log_h, int
   rls_cg* cg = a->cg;
   int nrec = a->enq < a->log_cap ? a->enq : a->log_cap;
   if (nrec > 0) RLS_TRY(rls_fetch_add(ctx, a->log, a->log_h, sizeof(float) * ADMM_REC * nrec));
-  if (cg->resident_used) RLS_TRY(resident_fetch_flags(ctx, cg->rsync, cg->rsync_h));
+  if (cg->resident.used) RLS_TRY(cg->resident.fetch_flags(ctx));
   RLS_TRY(fetch_scalars(ctx, a->sc, a->sc_h));  // synchronises the stream
-  if (cg->resident_used && resident_lost(ctx, cg->rsync, cg->rsync_h, &cg->resident_off, &cg->fallbacks)) {
+  if (cg->resident.used && cg->resident.lost(ctx)) {
     // A resident cg! gave up: it was a no-op and poisoned `done` (= 2), so everything queued behind it skipped.  The
     // outer iteration it belonged to has changed nothing that its repetition does not rewrite (beta, xold), so clear the
     // poison and run the missing outer iterations again; the inner solves now take the per-iteration pipeline.
-    a->fallbacks = cg->fallbacks;
+    a->fallbacks = cg->resident.fallbacks;
     if (a->sc_h->done == 2) {
       const int it_done = a->sc_h->iteration;
       RLS_HIP(ctx, hipMemsetAsync(&a->sc->done, 0, sizeof(int), ctx->stream));

@@ -138,12 +138,30 @@ static void test_chain(int nthreads, int iters) {
   std::printf("resident chain: %ld launches, %ld stream switches\n", launches, switches);
 }
 
+// the bookkeeping of lost resident launches: a plan is off the resident kernels from its first loss, the context from its second
+static void test_resident_loss() {
+  resident_loss_state plan_a, plan_b;
+  int ctx_failures = 0;
+  CHECK(!resident_note_lost(plan_a, ctx_failures, 0));  // nothing lost: nothing changes
+  CHECK(!plan_a.off && plan_a.fallbacks == 0 && ctx_failures == 0);
+  CHECK(!resident_note_lost(plan_a, ctx_failures, 1));  // one lost launch: the plan is off, the context still on
+  CHECK(plan_a.off && plan_a.fallbacks == 1 && ctx_failures == 1);
+  CHECK(!resident_note_lost(plan_a, ctx_failures, 0));
+  CHECK(plan_a.off && plan_a.fallbacks == 1 && ctx_failures == 1);
+  CHECK(resident_note_lost(plan_b, ctx_failures, 3));   // the context's second loss (another plan, three launches): context off
+  CHECK(plan_b.off && plan_b.fallbacks == 3 && ctx_failures == 2);
+  CHECK(plan_a.fallbacks == 1);
+  CHECK(resident_note_lost(plan_a, ctx_failures, 1) && plan_a.fallbacks == 2 && ctx_failures == 3);  // and it stays off
+  std::printf("resident loss: plan off after 1, context off after 2\n");
+}
+
 int main(int argc, char** argv) {
   const int rounds = argc > 1 ? std::atoi(argv[1]) : 10000;
   test_pool(8, rounds);
   test_pool(2, rounds / 4);
   test_pinned(8, 4000);
   test_chain(8, 20000);
+  test_resident_loss();
   std::printf(fails ? "FAILED (%d)\n" : "host concurrency OK\n", fails);
   return fails ? 1 : 0;
 }
