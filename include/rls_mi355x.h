@@ -273,6 +273,39 @@ int32_t rls_pgm_step_resident(rls_pgm* plan, int32_t kind, int32_t n_steps, int3
                               void* v1, void* v2, void* o0, void* res, const void* x0, int32_t reg_kind, int32_t proj_kind,
                               float norm_x0, float rel_tol, void* state_d);
 int32_t rls_pgm_lost(rls_pgm* plan, int32_t* lost, int32_t* fallbacks_total);
+/* Batched OptISTA / POGM: nrhs right-hand sides share ONE pass over A per product (the matrix-core skinny products of the
+ * batched CGNR / FISTA plans; one product over AHA when the operator carries an explicit Gram matrix), then one workgroup
+ * per column applies the update of rls_optista_update / rls_pogm_update.  Per-column scalars and per-column retirement: the
+ * results are those of nrhs independent solves.  kind 0 = OptISTA, 1 = POGM.  The state matrices are the caller's, N x nrhs,
+ * columns ldv elements apart:
+ *   OptISTA: v0, v1, z, old = x, y, z, zold (w unused, may be null)
+ *   POGM:    v0, v1 = the two x / y buffers -- the reference swaps their roles every iteration (src/POGM.jl:203) and columns
+ *            retire at different iterations, so the role is a function of the COLUMN's iteration count: its x is in v0 after an
+ *            even number of iterations, in v1 after an odd one; z, w (gradient restart only, else nullable), old = xold
+ * rls_pgm_create_batched returns RLS_E_UNSUPPORTED (nothing allocated) unless M and N are multiples of 16 (A and an explicit
+ * AHA alike): the caller solves column by column then.  set_reg: RLS_REG_NONE / L1 / L2 and, POGM only, RLS_PROJ_REAL /
+ * RLS_PROJ_POSITIVE.  init: x0 = A^H B, ||x0|| per column, every state vector zero, res = Inf, the records reset
+ * (done = iterations <= 0).  restart_gradient (POGM): theta, sigma, gamma travel in the column's record and the kernel forms
+ * the coefficients and applies the restart rule as rls_pogm_update_auto does; gamma0 = the gamma every column starts from.
+ * Otherwise table_d is a DEVICE array of table_rows >= iterations rows of 8 floats, row k = the coefficients of iteration k
+ * in the layout of rls_pgm_step_resident's `coefs` (host-side Float32 recurrences); it must stay valid until the last step.
+ * Each column indexes it with its own iteration count.  step: n_steps x {products, update}; a column whose `done` is set
+ * (rel_res_norm < rel_tol, the quotient in double, or iteration >= iterations) is left untouched.  Everything is enqueued on
+ * the context's stream; only get_status synchronises (one read-back for all columns). */
+typedef struct rls_pgm_batched rls_pgm_batched;
+typedef struct rls_pgm_status {
+  int32_t iteration, done;
+  float res_norm, rel_res_norm, norm_x0;
+  float theta, theta_old, sigma, gamma; /* maintained on the device for POGM with gradient restart only */
+} rls_pgm_status;
+int32_t rls_pgm_create_batched(rls_operator* op, int32_t kind, int32_t nrhs, void* v0, void* v1, void* z, void* w, void* old,
+                               void* res, void* x0, int64_t ldv, rls_pgm_batched** out);
+int32_t rls_pgm_destroy_batched(rls_pgm_batched* s);
+int32_t rls_pgm_set_reg_batched(rls_pgm_batched* s, int32_t reg_kind, float lambda, int32_t proj_kind);
+int32_t rls_pgm_init_batched(rls_pgm_batched* s, const void* B, int64_t ldb, float rho, float theta, float sigma_fac, float gamma0,
+                             float rel_tol, int32_t iterations, int32_t restart_gradient, const void* table_d, int32_t table_rows);
+int32_t rls_pgm_step_batched(rls_pgm_batched* s, int32_t n_steps);
+int32_t rls_pgm_get_status_batched(rls_pgm_batched* s, rls_pgm_status* out_h /* [nrhs] */);
 /* POGM with restart = :gradient, deferred: theta, sigma, gamma live in the device record (8 words: int32 iteration,
  * int32 done, float ||res||, pad, float theta, theta_old, sigma, gamma) and every launch derives its coefficients
  * from them in Float32 with the host's operation order (src/POGM.jl:183-201), applies the update, evaluates the

@@ -34,6 +34,12 @@ class FistaStatus(C.Structure):
                 ("rel_res_norm", C.c_float), ("residual", C.c_float), ("norm_x0", C.c_float), ("fallbacks", C.c_int32)]
 
 
+class PgmStatus(C.Structure):
+    _fields_ = [("iteration", C.c_int32), ("done", C.c_int32), ("res_norm", C.c_float), ("rel_res_norm", C.c_float),
+                ("norm_x0", C.c_float), ("theta", C.c_float), ("theta_old", C.c_float), ("sigma", C.c_float),
+                ("gamma", C.c_float)]
+
+
 class CgStatus(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("residual", C.c_float), ("tol", C.c_float), ("fallbacks", C.c_int32)]
 
@@ -142,6 +148,12 @@ PROTOTYPES = {
     "rls_pgm_destroy": (_i32, [_vp]),
     "rls_pgm_step_resident": (_i32, [_vp, _i32, _i32, _i32, _pf, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f, _f, _vp]),
     "rls_pgm_lost": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
+    "rls_pgm_create_batched": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _pvp]),
+    "rls_pgm_destroy_batched": (_i32, [_vp]),
+    "rls_pgm_set_reg_batched": (_i32, [_vp, _i32, _f, _i32]),
+    "rls_pgm_init_batched": (_i32, [_vp, _vp, _i64, _f, _f, _f, _f, _f, _i32, _i32, _vp, _i32]),
+    "rls_pgm_step_batched": (_i32, [_vp, _i32]),
+    "rls_pgm_get_status_batched": (_i32, [_vp, C.POINTER(PgmStatus)]),
     "rls_pogm_update_auto": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i32, _i32, _i32, _f, _f, _vp]),
     "rls_pogm_step_resident_restart": (_i32, [_vp, _i32, _i32, _f, _f, _f, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f, _f, _vp]),
     "rls_operator_mul_normal_skip": (_i32, [_vp, _vp, _vp, _vp]),

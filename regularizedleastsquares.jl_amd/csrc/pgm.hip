@@ -25,6 +25,22 @@ __device__ static inline double redot(E a, E b) {  // real(conj(a) * b)
 
 // zold = z; z = y; res -= x0; y -= step * res; prox(y, thr); z = z / (-gamma) + x + y / gamma;
 // x = -beta x + (1 + alpha + beta) z - alpha zold
+// One element of it (shared with the batched kernel below): `raw` = (AHA x)[i], zo / ztmp / xi = z[i], y[i], x[i] on entry.
+struct optista_coefs {
+  float step, thr, c_z, c_y, c_x, c_zn, c_zo;
+  int reg_kind;
+};
+template <typename E>
+__device__ static inline void optista_elem(const optista_coefs& c, E raw, E x0i, E zo, E ztmp, E xi, E& r, E& yn, E& zn, E& xn) {
+  r = elem<E>::sub(raw, x0i);
+  yn = elem<E>::add(ztmp, elem<E>::scale(-c.step, r));
+  yn = fista_prox_elem<E>(yn, c.reg_kind, c.thr);
+  zn = elem<E>::add(elem<E>::scale(c.c_z, ztmp), xi);
+  zn = elem<E>::add(zn, elem<E>::scale(c.c_y, yn));
+  xn = elem<E>::add(elem<E>::scale(c.c_x, xi), elem<E>::scale(c.c_zn, zn));
+  xn = elem<E>::add(xn, elem<E>::scale(c.c_zo, zo));
+}
+
 template <typename E>
 __global__ __launch_bounds__(PGM_THREADS) void optista_update_kernel(E* __restrict__ res, const E* __restrict__ x0,
                                                                      E* __restrict__ x, E* __restrict__ y,
@@ -35,18 +51,14 @@ __global__ __launch_bounds__(PGM_THREADS) void optista_update_kernel(E* __restri
                                                                      float norm_x0, float rel_tol) {
   __shared__ double sm[16];
   if (state && state->done) return;
+  const optista_coefs c{step, thr, c_z, c_y, c_x, c_zn, c_zo, reg_kind};
   double rn = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += PGM_THREADS) {
     const E zo = z[i], ztmp = y[i], xi = x[i];
-    const E r = elem<E>::sub(res[i], x0[i]);
+    E r, yn, zn, xn;
+    optista_elem<E>(c, res[i], x0[i], zo, ztmp, xi, r, yn, zn, xn);
     res[i] = r;
     rn += redot<E>(r, r);
-    E yn = elem<E>::add(ztmp, elem<E>::scale(-step, r));
-    yn = fista_prox_elem<E>(yn, reg_kind, thr);
-    E zn = elem<E>::add(elem<E>::scale(c_z, ztmp), xi);
-    zn = elem<E>::add(zn, elem<E>::scale(c_y, yn));
-    E xn = elem<E>::add(elem<E>::scale(c_x, xi), elem<E>::scale(c_zn, zn));
-    xn = elem<E>::add(xn, elem<E>::scale(c_zo, zo));
     zold[i] = zo;
     y[i] = yn;
     z[i] = zn;
@@ -62,6 +74,34 @@ __global__ __launch_bounds__(PGM_THREADS) void optista_update_kernel(E* __restri
 // xbuf holds x_k, ybuf holds y_{k-1} on entry; on exit xbuf holds the gradient point (the new y after the
 // reference's swap, src/POGM.jl:203) and ybuf the new x, so the caller swaps its two references.
 // Returns (valid in every thread) ||res||^2 and, with RESTART, real <w,x>, <w,z>, <w,res>.
+// One element of it (shared with the batched kernel below): `raw` = (AHA x)[i]; xo, yp, zi, wi = xbuf[i], ybuf[i], z[i], w[i]
+// on entry (wi is read with RESTART only).  x1 goes to xbuf, xn to ybuf, zn to z, wn to w, xo to xold.
+struct pogm_coefs {
+  float rho, c_y, c_x1, c_xo, c_z, thr, rg;
+  int reg_kind, proj_kind;
+};
+template <typename E, bool RESTART>
+__device__ static inline void pogm_elem(const pogm_coefs& c, E raw, E x0i, E xo, E yp, E zi, E wi, E& r, E& x1, E& xn, E& zn,
+                                        E& wn, double& dwx, double& dwz, double& dwr) {
+  r = elem<E>::sub(raw, x0i);                             // res .-= x0                         :178
+  x1 = elem<E>::add(xo, elem<E>::scale(-c.rho, r));       // x .-= rho .* res                   :179
+  xn = elem<E>::add(elem<E>::scale(c.c_y, yp), elem<E>::scale(c.c_x1, x1));  // after the swap  :204-205
+  xn = elem<E>::add(xn, elem<E>::scale(c.c_xo, xo));
+  xn = elem<E>::add(xn, elem<E>::scale(c.c_z, zi));
+  zn = xn;                                                // z .= x                              :210
+  xn = fista_proj_elem<E>(fista_prox_elem<E>(xn, c.reg_kind, c.thr), c.proj_kind);
+  if constexpr (RESTART) {                                // gradient restart                    :218-232
+    wi = elem<E>::add(wi, x1);
+    wi = elem<E>::add(wi, elem<E>::scale(c.rg, xn));
+    wi = elem<E>::add(wi, elem<E>::scale(-c.rg, zn));
+    dwx += redot<E>(wi, xn);
+    dwz += redot<E>(wi, zn);
+    dwr += redot<E>(wi, r);
+    wn = elem<E>::add(elem<E>::scale(c.rg, zn), elem<E>::scale(-c.rg, xn));
+    wn = elem<E>::sub(wn, x1);
+  }
+}
+
 template <typename E, bool RESTART>
 __device__ static inline void pogm_update_body(E* __restrict__ res, const E* __restrict__ x0, E* __restrict__ xbuf,
                                                E* __restrict__ ybuf, E* __restrict__ xold, E* __restrict__ z,
@@ -69,31 +109,20 @@ __device__ static inline void pogm_update_body(E* __restrict__ res, const E* __r
                                                float c_xo, float c_z, int reg_kind, float thr, int proj_kind, float rg,
                                                double* sm /* 48 */, double& rn, double& dwx, double& dwz, double& dwr) {
   rn = dwx = dwz = dwr = 0.0;
+  const pogm_coefs c{rho, c_y, c_x1, c_xo, c_z, thr, rg, reg_kind, proj_kind};
   for (int64_t i = threadIdx.x; i < n; i += PGM_THREADS) {
     const E xo = xbuf[i], yp = ybuf[i];
-    const E r = elem<E>::sub(res[i], x0[i]);              // res .-= x0                         :178
+    E wi = elem<E>::zero();
+    if constexpr (RESTART) wi = w[i];
+    E r, x1, xn, zn, wn;
+    pogm_elem<E, RESTART>(c, res[i], x0[i], xo, yp, z[i], wi, r, x1, xn, zn, wn, dwx, dwz, dwr);
     res[i] = r;
     rn += redot<E>(r, r);
-    const E x1 = elem<E>::add(xo, elem<E>::scale(-rho, r));  // x .-= rho .* res               :179
-    E xn = elem<E>::add(elem<E>::scale(c_y, yp), elem<E>::scale(c_x1, x1));  // after the swap  :204-205
-    xn = elem<E>::add(xn, elem<E>::scale(c_xo, xo));
-    xn = elem<E>::add(xn, elem<E>::scale(c_z, z[i]));
-    const E zn = xn;                                      // z .= x                              :210
-    xn = fista_proj_elem<E>(fista_prox_elem<E>(xn, reg_kind, thr), proj_kind);
     xold[i] = xo;
     z[i] = zn;
     xbuf[i] = x1;
     ybuf[i] = xn;
-    if constexpr (RESTART) {                              // gradient restart                    :218-232
-      E wi = elem<E>::add(w[i], x1);
-      wi = elem<E>::add(wi, elem<E>::scale(rg, xn));
-      wi = elem<E>::add(wi, elem<E>::scale(-rg, zn));
-      dwx += redot<E>(wi, xn);
-      dwz += redot<E>(wi, zn);
-      dwr += redot<E>(wi, r);
-      E wn = elem<E>::add(elem<E>::scale(rg, zn), elem<E>::scale(-rg, xn));
-      w[i] = elem<E>::sub(wn, x1);
-    }
+    if constexpr (RESTART) w[i] = wn;
   }
   rn = block_sum(rn, sm);
   if constexpr (RESTART) block_sum3(dwx, dwz, dwr, sm);
@@ -122,6 +151,32 @@ __global__ __launch_bounds__(PGM_THREADS) void pogm_update_kernel(E* __restrict_
   }
 }
 
+// the coefficients of one POGM iteration with restart = :gradient, formed from the record's theta, sigma, gamma
+// (src/POGM.jl:183-201; `last`: the final iteration's theta rule, :185).  One rounding per operation, as NumPy's Float32
+// scalars on the host (f32_mul / f32_add: never fused).
+struct pogm_auto_coefs {
+  float th, alpha, c_x1, gamma, c_z, c_xo, thr, rg;
+};
+__device__ static inline pogm_auto_coefs pogm_auto_form(float tho, float sigma, float gamma_old, bool last, float rho, float lam) {
+  pogm_auto_coefs a;
+  const float t2 = f32_mul(f32_mul(last ? 8.f : 4.f, tho), tho);      // :183-187
+  a.th = f32_add(1.f, sqrtf(f32_add(1.f, t2))) / 2.f;  // sqrtf: correctly rounded (v_sqrt_f32 alone is not)
+  a.alpha = f32_sub(tho, 1.f) / a.th;                                  // :189
+  const float beta = f32_mul(sigma, tho) / a.th;                       // :190
+  a.c_x1 = f32_add(f32_add(1.f, a.alpha), beta);
+  a.gamma = f32_mul(rho, a.c_x1);                                      // :195  rho (1 + alpha + beta)
+  a.c_z = f32_mul(rho, a.alpha) / gamma_old;
+  a.c_xo = -f32_add(beta, a.c_z);
+  a.thr = f32_mul(a.gamma, lam);
+  a.rg = rho / a.gamma;
+  return a;
+}
+// the restart criterion (:224) from the three real dot products
+__device__ static inline bool pogm_auto_restart(float gamma, double dwx, double dwz, double dwr) {
+  const float crit = f32_sub(f32_sub((float)dwx, (float)dwz) / gamma, (float)dwr);
+  return crit < 0.f;
+}
+
 // POGM with gradient restart, deferred: theta, sigma and gamma live in the device record and the coefficients of an
 // iteration (src/POGM.jl:183-201) are formed HERE from them, in Float32 with the host's operation order (explicit
 // round-to-nearest intrinsics: no contraction), so that the data-dependent restart decision (:218-232) never has to
@@ -137,36 +192,221 @@ __global__ __launch_bounds__(PGM_THREADS) void pogm_auto_kernel(E* __restrict__ 
                                                                 float rel_tol) {
   __shared__ double sm[48];
   if (st->done) return;
-  float th, alpha, c_x1, gamma, c_z, c_xo, thr, rg;
-  const float tho = st->theta, sigma = st->sigma, gamma_old = st->gamma;
-  {  // one rounding per operation, as NumPy's Float32 scalars on the host (f32_mul / f32_add: never fused)
-    const bool last = st->iteration == max_iter - 1;                     // :183-187
-    const float t2 = f32_mul(f32_mul(last ? 8.f : 4.f, tho), tho);
-    th = f32_add(1.f, sqrtf(f32_add(1.f, t2))) / 2.f;  // sqrtf: correctly rounded (v_sqrt_f32 alone is not)
-    alpha = f32_sub(tho, 1.f) / th;                                      // :189
-    const float beta = f32_mul(sigma, tho) / th;                         // :190
-    c_x1 = f32_add(f32_add(1.f, alpha), beta);
-    gamma = f32_mul(rho, c_x1);                                          // :195  rho (1 + alpha + beta)
-    c_z = f32_mul(rho, alpha) / gamma_old;
-    c_xo = -f32_add(beta, c_z);
-    thr = f32_mul(gamma, lam);
-    rg = rho / gamma;
-  }
+  const float tho = st->theta, sigma = st->sigma;
+  const pogm_auto_coefs a = pogm_auto_form(tho, sigma, st->gamma, st->iteration == max_iter - 1, rho, lam);
   double rn, dwx, dwz, dwr;
-  pogm_update_body<E, true>(res, x0, xbuf, ybuf, xold, z, w, n, rho, -alpha, c_x1, c_xo, c_z, reg_kind, thr, proj_kind, rg,
-                            sm, rn, dwx, dwz, dwr);
+  pogm_update_body<E, true>(res, x0, xbuf, ybuf, xold, z, w, n, rho, -a.alpha, a.c_x1, a.c_xo, a.c_z, reg_kind, a.thr, proj_kind,
+                            a.rg, sm, rn, dwx, dwz, dwr);
   if (threadIdx.x == 0) {
-    const float crit = f32_sub(f32_sub((float)dwx, (float)dwz) / gamma, (float)dwr);   // :224
-    const bool restart = crit < 0.f;
+    const bool restart = pogm_auto_restart(a.gamma, dwx, dwz, dwr);
     st->theta_old = tho;
-    st->theta = restart ? 1.f : th;
+    st->theta = restart ? 1.f : a.th;
     st->sigma = restart ? 1.f : f32_mul(sigma, sigma_fac);
-    st->gamma = gamma;
+    st->gamma = a.gamma;
     const float rnorm = (float)sqrt(rn);
     st->res_norm = rnorm;
     st->iteration += 1;
     st->done = ((double)rnorm / (double)norm_x0) < (double)rel_tol;
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Batched OptISTA / POGM: K right-hand sides share one pass over A per product (skinny.hip); these kernels are the
+// per-column halves, workgroup b = column b (the plan: solvers.hip, rls_pgm_create_batched).  AHA x arrives as `S`
+// partial rows per column and is summed here in fixed order; the next gradient point also goes into the operand
+// panel.  Every column carries its own iteration count: the coefficient row and (POGM) the roles of the two x / y
+// buffers follow it, so columns that retire at different iterations need nothing from the host.
+// ---------------------------------------------------------------------------------------------
+constexpr int PGMB_THREADS = 1024;
+
+template <typename E>
+__device__ static inline E pgmb_parts(const E* __restrict__ Vpart, int S, int nrhs_pad, int b, int64_t N, int64_t i) {
+  E v = Vpart[(int64_t)b * N + i];
+  for (int s = 1; s < S; ++s) v = elem<E>::add(v, Vpart[((int64_t)s * nrhs_pad + b) * N + i]);
+  return v;
+}
+
+// x0 = A^H b from the partial rows, ||x0||, the state vectors as OptISTA.init_ / POGM.init_ leave them (x = 0 and every
+// other vector 0, res = Inf), the first gradient point (x = 0) in the panel, the column's record
+template <typename E>
+__global__ __launch_bounds__(PGMB_THREADS) void pgmb_init_kernel(rls_pgmb D) {
+  __shared__ double sm[16];
+  const int b = blockIdx.x;
+  const int64_t n = D.N, off = (int64_t)b * D.ldv;
+  E* x0 = (E*)D.x0 + off;
+  E* res = (E*)D.res + off;
+  E* v[5] = {(E*)D.v0 + off, (E*)D.v1 + off, (E*)D.v2 + off, (E*)D.o0 + off, D.v3 ? (E*)D.v3 + off : nullptr};
+  const panel_col<E> pc = panel_column<E>((E*)D.panel, n, b, D.half);
+  const float inf = __builtin_huge_valf();
+  double nn = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += PGMB_THREADS) {
+    const E a = pgmb_parts<E>((const E*)D.Vpart, D.S, D.nrhs_pad, b, n, i);
+    x0[i] = a;
+    nn += redot<E>(a, a);
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+      if (v[k]) v[k][i] = elem<E>::zero();
+    res[i] = elem<E>::make(inf, 0.f);
+    pc.put(i, elem<E>::zero());
+  }
+  nn = block_sum_n<PGMB_THREADS / 64>(nn, sm);
+  if (threadIdx.x == 0) {
+    pgmb_scalars* sc = D.sc + b;
+    sc->norm_x0 = sqrt(nn);
+    sc->res_norm = inf;
+    sc->rel_res_norm = inf;
+    sc->theta = D.theta;
+    sc->theta_old = D.theta;
+    sc->sigma = 1.f;
+    sc->gamma = D.gamma0;
+    sc->iteration = 0;
+    sc->done = (0 >= D.max_iter);
+  }
+}
+
+// One iteration of column b after the two products: optista_elem / pogm_elem over the column, in tiles of EPT elements per
+// thread whose loads are all requested before the first use (EPT * PGMB_THREADS >= N: the whole column in registers, one
+// tile; EPT = 1 is the plain strided loop).  The per-thread summation order is the element order in both forms.
+template <typename E, int KIND, int EPT>
+__global__ __launch_bounds__(PGMB_THREADS) void pgmb_update_kernel(rls_pgmb D) {
+  constexpr bool POGM = KIND != RLS_PGMB_OPTISTA, RESTART = KIND == RLS_PGMB_POGM_RESTART;
+  __shared__ double sm[48];
+  const int b = blockIdx.x;
+  pgmb_scalars* sc = D.sc + b;
+  if (sc->done) return;  // a retired column keeps its vectors, its panel entry and its record
+  const int it = sc->iteration;
+  const int64_t n = D.N, off = (int64_t)b * D.ldv;
+  // OptISTA: a0 = x, a1 = y.  POGM: a0 = the buffer that holds x_k (v0 after an even number of iterations), a1 = y_{k-1};
+  // on exit a1 holds the new x (src/POGM.jl:203)
+  E* a0 = (E*)((POGM && (it & 1)) ? D.v1 : D.v0) + off;
+  E* a1 = (E*)((POGM && (it & 1)) ? D.v0 : D.v1) + off;
+  E* z = (E*)D.v2 + off;
+  E* o0 = (E*)D.o0 + off;
+  E* res = (E*)D.res + off;
+  E* w = RESTART ? (E*)D.v3 + off : nullptr;
+  const E* x0 = (const E*)D.x0 + off;
+  const E* Vpart = (const E*)D.Vpart;
+  const panel_col<E> pc = panel_column<E>((E*)D.panel, n, b, D.half);
+  optista_coefs oc = {};
+  pogm_coefs gc = {};
+  pogm_auto_coefs au = {};
+  float tho = 0.f, sigma = 0.f;
+  if constexpr (KIND == RLS_PGMB_OPTISTA) {  // the row of THIS column's iteration (rls_pgm_coefs)
+    const float* r = D.table + 8 * (int64_t)it;
+    oc = optista_coefs{r[0], r[1], r[2], r[3], r[4], r[5], r[6], D.reg_kind};
+  } else if constexpr (KIND == RLS_PGMB_POGM) {
+    const float* r = D.table + 8 * (int64_t)it;
+    gc = pogm_coefs{r[0], r[2], r[3], r[4], r[5], r[1], 0.f, D.reg_kind, D.proj_kind};
+  } else {  // the record's theta, sigma, gamma (pogm_auto_kernel)
+    tho = sc->theta;
+    sigma = sc->sigma;
+    au = pogm_auto_form(tho, sigma, sc->gamma, it == D.max_iter - 1, D.rho, D.lambda);
+    gc = pogm_coefs{D.rho, -au.alpha, au.c_x1, au.c_xo, au.c_z, au.thr, au.rg, D.reg_kind, D.proj_kind};
+  }
+  double rn = 0.0, dwx = 0.0, dwz = 0.0, dwr = 0.0;
+  for (int64_t base = 0; base < n; base += (int64_t)EPT * PGMB_THREADS) {
+    E raw[EPT], x0v[EPT], p0[EPT], p1[EPT], zv[EPT], wv[EPT];
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) {
+      const int64_t i = base + threadIdx.x + (int64_t)e * PGMB_THREADS;
+      const int64_t ic = i < n ? i : n - 1;
+      raw[e] = pgmb_parts<E>(Vpart, D.S, D.nrhs_pad, b, n, ic);
+      x0v[e] = x0[ic];
+      p0[e] = a0[ic];
+      p1[e] = a1[ic];
+      zv[e] = z[ic];
+      wv[e] = elem<E>::zero();
+      if constexpr (RESTART) wv[e] = w[ic];
+    }
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) {
+      const int64_t i = base + threadIdx.x + (int64_t)e * PGMB_THREADS;
+      if (i >= n) continue;
+      E r, xn;
+      if constexpr (!POGM) {
+        E yn, zn;
+        optista_elem<E>(oc, raw[e], x0v[e], zv[e], p1[e], p0[e], r, yn, zn, xn);
+        o0[i] = zv[e];
+        a1[i] = yn;
+        z[i] = zn;
+        a0[i] = xn;
+      } else {
+        E x1, zn, wn;
+        pogm_elem<E, RESTART>(gc, raw[e], x0v[e], p0[e], p1[e], zv[e], wv[e], r, x1, xn, zn, wn, dwx, dwz, dwr);
+        o0[i] = p0[e];
+        z[i] = zn;
+        a0[i] = x1;
+        a1[i] = xn;
+        if constexpr (RESTART) w[i] = wn;
+      }
+      res[i] = r;
+      rn += redot<E>(r, r);
+      pc.put(i, xn);  // the next gradient point: the new x
+    }
+  }
+  rn = block_sum_n<PGMB_THREADS / 64>(rn, sm);
+  if constexpr (RESTART) block_sum3_n<PGMB_THREADS / 64>(dwx, dwz, dwr, sm);
+  if (threadIdx.x == 0) {
+    if constexpr (RESTART) {
+      const bool restart = pogm_auto_restart(au.gamma, dwx, dwz, dwr);
+      sc->theta_old = tho;
+      sc->theta = restart ? 1.f : au.th;
+      sc->sigma = restart ? 1.f : f32_mul(sigma, D.sigma_fac);
+      sc->gamma = au.gamma;
+    }
+    const float rnorm = (float)sqrt(rn);
+    const double rel = (double)rnorm / sc->norm_x0;  // the quotient in double (pgm_state_step)
+    sc->res_norm = rnorm;
+    sc->rel_res_norm = (float)rel;
+    sc->iteration = it + 1;
+    sc->done = (rel < (double)D.rel_tol) || (it + 1 >= D.max_iter);
+  }
+}
+
+template <typename E, int KIND>
+static void pgmb_launch_update_typed(rls_ctx* ctx, const rls_pgmb& D) {
+  const dim3 grid((unsigned)D.nrhs), block(PGMB_THREADS);
+  const int64_t n = D.N;
+  if (ctx->tune.pgm_batched_reg && n > PGMB_THREADS && n <= 2 * PGMB_THREADS)
+    hipLaunchKernelGGL((pgmb_update_kernel<E, KIND, 2>), grid, block, 0, ctx->stream, D);
+  else if (ctx->tune.pgm_batched_reg && n > 2 * PGMB_THREADS && n <= 4 * PGMB_THREADS)
+    hipLaunchKernelGGL((pgmb_update_kernel<E, KIND, 4>), grid, block, 0, ctx->stream, D);
+  else
+    hipLaunchKernelGGL((pgmb_update_kernel<E, KIND, 1>), grid, block, 0, ctx->stream, D);
+}
+
+static bool pgmb_desc_ok(const rls_pgmb& D) {
+  return D.kind >= RLS_PGMB_OPTISTA && D.kind <= RLS_PGMB_POGM_RESTART && D.N > 0 && D.ldv >= D.N && D.nrhs >= 1 && D.v0 && D.v1 &&
+         D.v2 && D.o0 && D.res && D.x0 && D.Vpart && D.panel && D.sc && D.S >= 1 && D.nrhs_pad >= D.nrhs &&
+         (D.kind != RLS_PGMB_POGM_RESTART || D.v3) && (D.kind == RLS_PGMB_POGM_RESTART || D.table) &&
+         D.reg_kind >= RLS_REG_NONE && D.reg_kind <= RLS_REG_L2 && D.proj_kind >= RLS_PROJ_NONE && D.proj_kind <= RLS_PROJ_POSITIVE;
+}
+
+int32_t rls_pgmb_launch_init(rls_ctx* ctx, int32_t dtype, const rls_pgmb& D) {
+  if (!rls_dtype_ok(dtype) || !pgmb_desc_ok(D)) return rls_fail(ctx, RLS_E_INVALID, "batched OptISTA / POGM init: bad argument");
+  if (dtype == RLS_F32)
+    hipLaunchKernelGGL(pgmb_init_kernel<float>, dim3((unsigned)D.nrhs), dim3(PGMB_THREADS), 0, ctx->stream, D);
+  else
+    hipLaunchKernelGGL(pgmb_init_kernel<float2>, dim3((unsigned)D.nrhs), dim3(PGMB_THREADS), 0, ctx->stream, D);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return rls_fail(ctx, (int32_t)e, hipGetErrorString(e));
+  return 0;
+}
+
+int32_t rls_pgmb_launch_update(rls_ctx* ctx, int32_t dtype, const rls_pgmb& D) {
+  if (!rls_dtype_ok(dtype) || !pgmb_desc_ok(D)) return rls_fail(ctx, RLS_E_INVALID, "batched OptISTA / POGM update: bad argument");
+#define RLS_PGMB(EE)                                                                             \
+  do {                                                                                           \
+    if (D.kind == RLS_PGMB_OPTISTA) pgmb_launch_update_typed<EE, RLS_PGMB_OPTISTA>(ctx, D);      \
+    else if (D.kind == RLS_PGMB_POGM) pgmb_launch_update_typed<EE, RLS_PGMB_POGM>(ctx, D);       \
+    else pgmb_launch_update_typed<EE, RLS_PGMB_POGM_RESTART>(ctx, D);                            \
+  } while (0)
+  if (dtype == RLS_F32) RLS_PGMB(float);
+  else RLS_PGMB(float2);
+#undef RLS_PGMB
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return rls_fail(ctx, (int32_t)e, hipGetErrorString(e));
+  return 0;
 }
 
 static int32_t pgm_fetch(rls_ctx* ctx, float* out_h, int nfloats) {

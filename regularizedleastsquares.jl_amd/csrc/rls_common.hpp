@@ -54,6 +54,7 @@ struct rls_tuning {
   int skinny_t_waves = 4, skinny_t_u = 4, skinny_v_waves = 4, skinny_v_u = 1, skinny_v_splits = 0;  // skinny.hip (tools/skinny_probe.py)
   int skinny_t_roll = 8, skinny_v_roll = 2, skinny_g_roll = 8;  // rolling-window depth of the complex T / V / Gram products (0 = two-set pipeline)
   int skinny_half = 1;         // the (re | im) operand packing for <= 8 complex right-hand sides
+  int pgm_batched_reg = 1;     // batched OptISTA / POGM update: 1 = the column's vectors in registers where N allows, 0 = strided loop (measurement)
   int gram_lds = 96 * 1024;    // dynamic LDS requested by the Gram tile kernel as an occupancy limiter
   int64_t tv_fused_max_n = 2048;  // tv.hip: larger images run 2 chip-wide launches per FGP iteration instead of one CU
   int tv_fused_2d = 1;         // the register-resident 2-D FGP kernel (n <= 8192 pixels)
@@ -945,6 +946,36 @@ struct rls_pgm_desc {
 bool rls_pgm_resident_ok(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* A, int64_t lda);
 int32_t rls_pgm_resident_launch(rls_ctx* ctx, int32_t dtype, const rls_pgm_desc& D, const rls_pgm_coefs& C, void* sync,
                                 int n_steps, unsigned spin_limit);
+
+// ---- batched OptISTA / POGM (K right-hand sides sharing A): kernels in pgm.hip, plan in solvers.hip ----------------------
+// one column's scalar record
+struct pgmb_scalars {
+  double norm_x0;                          // ||A^H b||
+  float res_norm, rel_res_norm;
+  float theta, theta_old, sigma, gamma;    // POGM with restart = :gradient (pogm_auto_state's four)
+  int iteration, done;
+};
+constexpr int RLS_PGMB_OPTISTA = 0, RLS_PGMB_POGM = 1, RLS_PGMB_POGM_RESTART = 2;
+struct rls_pgmb {
+  int kind;                  // RLS_PGMB_*
+  int64_t N, ldv;
+  int nrhs;
+  void *v0, *v1, *v2;        // N x nrhs, columns ldv apart.  OptISTA: x, y, z.  POGM: the two x / y buffers (roles by the column's
+                             // iteration parity: x is v0 when it is even), z
+  void* v3;                  // POGM with restart: w
+  void *o0, *res, *x0;       // OptISTA zold / POGM xold; state.res; A^H b
+  const void* Vpart;         // the skinny product's partial rows [S][nrhs_pad][N]
+  int S, nrhs_pad;
+  float* panel;              // operand panel of the next gradient points
+  int half;
+  pgmb_scalars* sc;          // [nrhs]
+  const float* table;        // [max_iter][8] index-only coefficients (rls_pgm_coefs' rows); unused by RLS_PGMB_POGM_RESTART
+  int reg_kind, proj_kind, max_iter;
+  float lambda, rho, rel_tol, sigma_fac;
+  float theta, gamma0;       // init only
+};
+int32_t rls_pgmb_launch_init(rls_ctx* ctx, int32_t dtype, const rls_pgmb& D);
+int32_t rls_pgmb_launch_update(rls_ctx* ctx, int32_t dtype, const rls_pgmb& D);
 
 // Gram-mode CGNR pipeline (normal.hip): one launch per iteration, every buffer in two parities
 struct rls_gram_pipe {

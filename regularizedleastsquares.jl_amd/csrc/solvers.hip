@@ -4142,6 +4142,207 @@ int32_t rls_pgm_lost(rls_pgm* s, int32_t* lost, int32_t* fallbacks_total) {
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Batched OptISTA / POGM: K right-hand sides sharing A (solve!(solver, B) of src/MultiThreading.jl:30-79), shaped like
+// the batched FISTA plan: the K gradient points as an MFMA operand panel, T = A X and the partial rows of A^H T (or one
+// product over an explicit AHA) on the matrix cores, then one workgroup per column (pgm.hip, pgmb_update_kernel).
+// ---------------------------------------------------------------------------------------------
+struct rls_pgm_batched {
+  rls_operator* op;
+  rls_ctx* actx;
+  uint64_t actx_id = 0;
+  int device;
+  int kind;  // 0 = OptISTA, 1 = POGM
+  rls_pgmb D;
+  float *panel = nullptr, *Tpack = nullptr;
+  void* Vpart = nullptr;
+  int splits = 1, half = 0;
+  pgmb_scalars *sc = nullptr, *sc_h = nullptr;  // [nrhs], pinned mirror
+  step_graph graph;
+  bool initialised = false;
+};
+
+static rls_skinny pgmb_skinny_desc(const rls_pgm_batched* s) {
+  rls_skinny K;
+  K.A = s->op->A;
+  K.lda = s->op->lda;
+  K.M = s->op->M;
+  K.N = s->op->N;
+  K.G = s->op->G;
+  K.ldg = s->op->ldg;
+  K.nrhs = s->D.nrhs;
+  K.half = s->half;
+  K.ngroups = rls_skinny_groups(s->D.nrhs, s->half);
+  K.splits = s->splits;
+  K.X = K.R = K.P = K.V = nullptr;
+  K.ldv = s->D.ldv;
+  K.Ppack = s->panel;  // the T kernel's right operand: the gradient points
+  K.Tpack = s->Tpack;
+  K.Vpart = s->Vpart;
+  K.ldvp = s->op->N;
+  K.sc = nullptr;
+  return K;
+}
+
+int32_t rls_pgm_create_batched(rls_operator* op, int32_t kind, int32_t nrhs, void* v0, void* v1, void* z, void* w, void* old,
+                               void* res, void* x0, int64_t ldv, rls_pgm_batched** out) {
+  if (!op) return RLS_E_INVALID;
+  rls_ctx* ctx = op->ctx;
+  if ((kind != 0 && kind != 1) || !v0 || !v1 || !z || !old || !res || !x0 || !out || nrhs < 1 || ldv < op->N)
+    return rls_fail(ctx, RLS_E_INVALID, "pgm_create_batched: bad argument");
+  *out = nullptr;
+  if (!op->A || !ctx->tune.batched_mfma || !rls_skinny_ok(op->dtype, op->M, op->N, op->A, op->lda) ||
+      (op->G && !rls_skinny_ok(op->dtype, op->N, op->N, op->G, op->ldg)))
+    return rls_fail(ctx, RLS_E_UNSUPPORTED, "batched OptISTA / POGM needs A (and AHA, when explicit) with 16-aligned M, N (matrix-core path)");
+  RLS_HIP(ctx, rls_enter(ctx));
+  rls_alloc_scope alloc_scope(ctx);
+  rls_pgm_batched* s = new rls_pgm_batched();
+  s->op = op;
+  s->actx = ctx;
+  s->actx_id = ctx->id;
+  s->device = ctx->device;
+  s->kind = kind;
+  size_t pb, tb, vb;
+  rls_skinny_sizes(ctx, op->dtype, op->M, op->N, nrhs, &pb, &tb, &vb, &s->splits);
+  s->half = rls_skinny_half(ctx, op->dtype, nrhs);
+  hipError_t e = dmalloc(&s->panel, pb);
+  if (e == hipSuccess) e = hipMemsetAsync(s->panel, 0, pb, ctx->stream);  // the padding columns of the last group stay zero
+  if (e == hipSuccess) e = dmalloc(&s->Tpack, tb);
+  if (e == hipSuccess) e = dmalloc(&s->Vpart, vb);
+  if (e == hipSuccess) e = dmalloc(&s->sc, sizeof(pgmb_scalars) * nrhs);
+  if (e == hipSuccess) e = hipMemsetAsync(s->sc, 0, sizeof(pgmb_scalars) * nrhs, ctx->stream);
+  if (e == hipSuccess) e = hmalloc(&s->sc_h, sizeof(pgmb_scalars) * nrhs);
+  if (e != hipSuccess) {
+    if (s->panel) dfree(s->panel);
+    if (s->Tpack) dfree(s->Tpack);
+    if (s->Vpart) dfree(s->Vpart);
+    if (s->sc) dfree(s->sc);
+    if (s->sc_h) hfree(s->sc_h);
+    delete s;
+    (void)hipGetLastError();
+    return rls_fail(ctx, (int32_t)e, "pgm_create_batched: allocation failed");
+  }
+  rls_pgmb& D = s->D;
+  D = rls_pgmb();
+  D.kind = kind == 0 ? RLS_PGMB_OPTISTA : RLS_PGMB_POGM;
+  D.N = op->N;
+  D.ldv = ldv;
+  D.nrhs = nrhs;
+  D.v0 = v0;
+  D.v1 = v1;
+  D.v2 = z;
+  D.v3 = w;
+  D.o0 = old;
+  D.res = res;
+  D.x0 = x0;
+  D.Vpart = s->Vpart;
+  D.S = s->splits;
+  D.nrhs_pad = rls_skinny_pad(nrhs, s->half);
+  D.panel = s->panel;
+  D.half = s->half;
+  D.sc = s->sc;
+  D.table = nullptr;
+  D.reg_kind = RLS_REG_L1;
+  D.proj_kind = RLS_PROJ_NONE;
+  D.lambda = 0.f;
+  *out = s;
+  return 0;
+}
+
+int32_t rls_pgm_destroy_batched(rls_pgm_batched* s) {
+  if (!s) return RLS_E_INVALID;
+  hipSetDevice(s->device);
+  rls_alloc_scope alloc_scope(alloc_ctx_of(s->actx, s->actx_id));
+  s->graph.drop();
+  dfree(s->panel);
+  dfree(s->Tpack);
+  dfree(s->Vpart);
+  dfree(s->sc);
+  hfree(s->sc_h);
+  delete s;
+  return 0;
+}
+
+int32_t rls_pgm_set_reg_batched(rls_pgm_batched* s, int32_t reg_kind, float lambda, int32_t proj_kind) {
+  if (!s) return RLS_E_INVALID;
+  rls_ctx* ctx = s->op->ctx;
+  if (reg_kind < RLS_REG_NONE || reg_kind > RLS_REG_L2 || proj_kind < RLS_PROJ_NONE || proj_kind > RLS_PROJ_POSITIVE ||
+      (s->kind == 0 && proj_kind != RLS_PROJ_NONE))
+    return rls_fail(ctx, RLS_E_INVALID, "pgm_set_reg_batched: regulariser / projection not covered by the batched update");
+  if (reg_kind != s->D.reg_kind || lambda != s->D.lambda || proj_kind != s->D.proj_kind) s->graph.drop();  // (kernel arguments)
+  s->D.reg_kind = reg_kind;
+  s->D.lambda = lambda;
+  s->D.proj_kind = proj_kind;
+  return 0;
+}
+
+int32_t rls_pgm_init_batched(rls_pgm_batched* s, const void* B, int64_t ldb, float rho, float theta, float sigma_fac, float gamma0,
+                             float rel_tol, int32_t iterations, int32_t restart_gradient, const void* table_d, int32_t table_rows) {
+  if (!s) return RLS_E_INVALID;
+  rls_operator* op = s->op;
+  rls_ctx* ctx = op->ctx;
+  const bool restart = restart_gradient != 0;
+  if (!B || ldb < op->M || iterations < 0 || (restart && (s->kind != 1 || !s->D.v3)) ||
+      (!restart && iterations > 0 && (!table_d || table_rows < iterations)))
+    return rls_fail(ctx, RLS_E_INVALID, "pgm_init_batched: bad argument");
+  RLS_HIP(ctx, rls_enter(ctx));
+  rls_pgmb D = s->D;
+  D.kind = s->kind == 0 ? RLS_PGMB_OPTISTA : restart ? RLS_PGMB_POGM_RESTART : RLS_PGMB_POGM;
+  D.table = restart ? nullptr : (const float*)table_d;
+  D.max_iter = iterations;
+  D.rho = rho;
+  D.rel_tol = rel_tol;
+  D.sigma_fac = sigma_fac;
+  D.theta = theta;
+  D.gamma0 = gamma0;
+  if (!restart && !D.table) D.table = (const float*)s->sc;  // iterations == 0: never read
+  // every one of these is an argument of the captured kernels
+  if (D.kind != s->D.kind || D.table != s->D.table || D.max_iter != s->D.max_iter || D.rho != s->D.rho || D.rel_tol != s->D.rel_tol ||
+      D.sigma_fac != s->D.sigma_fac)
+    s->graph.drop();
+  s->D = D;
+  RLS_TRY(rls_skinny_atb(ctx, op->dtype, pgmb_skinny_desc(s), B, ldb));  // partial rows of A^H B
+  RLS_TRY(rls_pgmb_launch_init(ctx, op->dtype, s->D));
+  s->initialised = true;
+  return 0;
+}
+
+int32_t rls_pgm_step_batched(rls_pgm_batched* s, int32_t n_steps) {
+  if (!s) return RLS_E_INVALID;
+  rls_ctx* ctx = s->op->ctx;
+  if (!s->initialised) return rls_fail(ctx, RLS_E_STATE, "pgm_step_batched before pgm_init_batched");
+  if (n_steps < 0) return rls_fail(ctx, RLS_E_INVALID, "pgm_step_batched: n_steps < 0");
+  RLS_HIP(ctx, rls_enter(ctx));
+  const int32_t dtype = s->op->dtype;
+  return run_steps(ctx, &s->graph, n_steps, [s, ctx, dtype]() {
+    RLS_TRY(rls_skinny_launch(ctx, dtype, pgmb_skinny_desc(s), 1 | 2));
+    return rls_pgmb_launch_update(ctx, dtype, s->D);
+  });
+}
+
+int32_t rls_pgm_get_status_batched(rls_pgm_batched* s, rls_pgm_status* out) {
+  if (!s || !out) return RLS_E_INVALID;
+  rls_ctx* ctx = s->op->ctx;
+  if (!s->initialised) return rls_fail(ctx, RLS_E_STATE, "pgm_get_status_batched before pgm_init_batched");
+  RLS_HIP(ctx, rls_enter(ctx));
+  static_assert(sizeof(pgmb_scalars) % 4 == 0, "status structs are copied dword by dword");
+  RLS_TRY(rls_fetch_add(ctx, s->sc, s->sc_h, sizeof(pgmb_scalars) * (size_t)s->D.nrhs));
+  RLS_TRY(rls_fetch_wait(ctx));
+  for (int b = 0; b < s->D.nrhs; ++b) {
+    const pgmb_scalars& h = s->sc_h[b];
+    out[b].iteration = h.iteration;
+    out[b].done = h.done;
+    out[b].res_norm = h.res_norm;
+    out[b].rel_res_norm = h.rel_res_norm;
+    out[b].norm_x0 = (float)h.norm_x0;
+    out[b].theta = h.theta;
+    out[b].theta_old = h.theta_old;
+    out[b].sigma = h.sigma;
+    out[b].gamma = h.gamma;
+  }
+  return 0;
+}
+
 int32_t rls_cg_path(rls_cg* s, int32_t* out) {
   if (!s || !out) return RLS_E_INVALID;
   const rls_ctx* ctx = s->op->ctx;

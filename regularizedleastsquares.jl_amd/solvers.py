@@ -21,7 +21,7 @@ import numpy as np
 from . import _lib
 from ._lib import (PROJ_NONE, PROJ_POSITIVE, PROJ_REAL, REG_L1, REG_L2, REG_L21, REG_NONE, REG_TV, AdmmParams,
                    AdmmStatus, CgnrStatus, CgStatus,
-                   FistaStatus, check)
+                   FistaStatus, PgmStatus, check)
 from .arrays import DeviceMatrix, DeviceVector, NormalOperator, OperatorHandle, is_double
 from .regularization import (AbstractParameterizedRegularization, AbstractProjectionRegularization, GradientOp,
                              L1Regularization, L2Regularization, findsink, findsinks, is_projection, sink,
@@ -1247,13 +1247,18 @@ class OptISTA(AbstractProximalGradientSolver):
         for v in (st.y, st.z, st.zold):
             v.copy_from(st.x)
         st.res.fill_(math.inf)
+        self._set_theta(st, theta)
+        st.rel_res_norm = math.inf
+        st.iteration = 0
+
+    def _set_theta(self, st, theta):
+        """theta and theta_n as init! leaves them (src/OptISTA.jl:142-150)"""
+        f32 = _rt_of(self._op)
         st.theta = st.thetaold = float(theta)
         tn = f32(theta)
         for _ in range(self.iterations - 1):
             tn = (f32(1) + np.sqrt(f32(1) + f32(4) * tn * tn)) / f32(2)
         st.theta_n = float((f32(1) + np.sqrt(f32(1) + f32(8) * tn * tn)) / f32(2))
-        st.rel_res_norm = math.inf
-        st.iteration = 0
 
     def _coefficients(self, st):
         """the index-only scalars of one iteration (src/OptISTA.jl:170-175,196-204), advancing theta"""
@@ -1269,11 +1274,20 @@ class OptISTA(AbstractProximalGradientSolver):
         alpha, beta = (th - f32(1)) / thn, th / thn
         return rho, gamma, alpha, beta
 
-    def _update_args(self, st, fus, rho, gamma, alpha, beta):
+    def _update_coefs(self, rho, gamma, alpha, beta):
+        """(step, thr, c_z, c_y, c_x, c_zn, c_zo): the float arguments of the fused update, a table row's first seven"""
         f32 = _rt_of(self._op)
-        return (st.x.ctx.handle, st.x.code, st.x.n, st.res.ptr, st.x0.ptr, st.x.ptr, st.y.ptr, st.z.ptr, st.zold.ptr,
-                float(rho * gamma), fus[0], float(rho * gamma * f32(self.reg.lam)), float(f32(-1) / gamma),
+        return (float(rho * gamma), float(rho * gamma * f32(self.reg.lam)), float(f32(-1) / gamma),
                 float(f32(1) / gamma), float(-beta), float(f32(1) + alpha + beta), float(-alpha))
+
+    def _update_args(self, st, fus, rho, gamma, alpha, beta):
+        c = self._update_coefs(rho, gamma, alpha, beta)
+        return (st.x.ctx.handle, st.x.code, st.x.n, st.res.ptr, st.x0.ptr, st.x.ptr, st.y.ptr, st.z.ptr, st.zold.ptr,
+                c[0], fus[0]) + c[1:]
+
+    def _table_row(self, st):
+        """advance `st` by one iteration: (its row of the coefficient table, (theta, thetaold) after it)"""
+        return self._update_coefs(*self._coefficients(st)), (st.theta, st.thetaold)
 
     def iterate(self, st=None):
         st = st or self.state
@@ -1321,10 +1335,7 @@ class OptISTA(AbstractProximalGradientSolver):
         lib, h = ctx.lib, ctx.handle
         if _pgm_plan(self) is not None:
             # whole blocks of iterations as single launches, A in the register files (rls_pgm_step_resident)
-            def row(st):
-                a = self._update_args(st, fus, *self._coefficients(st))
-                return (a[9], a[11]) + a[12:17], (st.theta, st.thetaold)
-            _pgm_resident(self, st, 0, row, ("theta", "thetaold"), (st.x, st.y, st.z, st.zold), fus)
+            _pgm_resident(self, st, 0, self._table_row, ("theta", "thetaold"), (st.x, st.y, st.z, st.zold), fus)
             if st.rel_res_norm < st.relTol or st.iteration >= self.iterations:
                 return
         rec = _pgm_record(st, ctx)
@@ -1576,6 +1587,27 @@ class POGM(AbstractProximalGradientSolver):
         st.iteration += 1
         return st.x, st
 
+    def _coefficients(self, st):
+        """(rho, c_y, c_x1, c_xo, c_z, thr) of one iteration, advancing theta / gamma   (src/POGM.jl:183-201, restart == :none)"""
+        f32 = _rt_of(self._op)
+        rho = f32(st.rho)
+        tho = f32(st.theta)
+        st.thetaold = float(tho)
+        th = (f32(1) + np.sqrt(f32(1) + f32(4) * tho * tho)) / f32(2)
+        st.theta = float(th)
+        alpha = (tho - f32(1)) / th
+        beta = f32(st.sigma) * tho / th
+        gamma_old = f32(st.gamma)
+        gamma = rho * (f32(2) * tho + th - f32(1)) / th
+        st.gamma = float(gamma)
+        return (float(rho), float(-alpha), float(f32(1) + alpha + beta), -float(beta + rho * alpha / gamma_old),
+                float(rho * alpha / gamma_old), float(gamma * f32(self.reg.lam)))
+
+    def _table_row(self, st):
+        """advance `st` by one iteration: (its row of the coefficient table, (theta, thetaold, gamma) after it)"""
+        c = self._coefficients(st)
+        return (c[0], c[5]) + c[1:5], (st.theta, st.thetaold, st.gamma)
+
     def _run(self, st):
         """restart = :none without callbacks: all remaining iterations enqueued at once (index-only coefficients),
         the stopping test on the device, ONE read-back at the end; otherwise iteration by iteration"""
@@ -1639,29 +1671,12 @@ class POGM(AbstractProximalGradientSolver):
                 st.rel_res_norm = float(raw[2]) / st.norm_x0
                 st.theta, st.thetaold, st.sigma, st.gamma = (float(v) for v in raw[4:8])
             return
-        rho = f32(st.rho)
-
-        def coefficients(st):
-            """(rho, c_y, c_x1, c_xo, c_z, thr) of one iteration, advancing theta / gamma   (src/POGM.jl:183-201, restart == :none)"""
-            tho = f32(st.theta)
-            st.thetaold = float(tho)
-            th = (f32(1) + np.sqrt(f32(1) + f32(4) * tho * tho)) / f32(2)
-            st.theta = float(th)
-            alpha = (tho - f32(1)) / th
-            beta = f32(st.sigma) * tho / th
-            gamma_old = f32(st.gamma)
-            gamma = rho * (f32(2) * tho + th - f32(1)) / th
-            st.gamma = float(gamma)
-            return (float(rho), float(-alpha), float(f32(1) + alpha + beta), -float(beta + rho * alpha / gamma_old),
-                    float(rho * alpha / gamma_old), float(gamma * f32(self.reg.lam)))
+        coefficients = self._coefficients
 
         if _pgm_plan(self) is not None:
             # whole blocks of iterations as single launches, A in the register files (rls_pgm_step_resident)
-            def row(st):
-                c = coefficients(st)
-                return (c[0], c[5]) + c[1:5], (st.theta, st.thetaold, st.gamma)
             bufs = (st.x, st.y)
-            done_its = _pgm_resident(self, st, 1, row, ("theta", "thetaold", "gamma"), (st.x, st.y, st.z, st.xold), fus)
+            done_its = _pgm_resident(self, st, 1, self._table_row, ("theta", "thetaold", "gamma"), (st.x, st.y, st.z, st.xold), fus)
             st.x, st.y = bufs if done_its % 2 == 0 else bufs[::-1]
             if st.rel_res_norm < st.relTol or st.iteration >= self.iterations:
                 return
@@ -2152,6 +2167,125 @@ class FistaBatchedState(BatchedState):
         self._plan = None
 
 
+def _pgm_batched_table(solver, theta):
+    """The index-only coefficients of a whole OptISTA / POGM (restart = :none) solve that starts from a fresh per-column
+    state (solver._new_state(): POGM's gamma as it stands) with the init! keyword `theta`: (float32 table [iterations, 8],
+    row k = iteration k in the layout of rls_pgm_step_resident; the solver scalars after 0, 1, ... iterations).
+    Stepped with the solver's own _coefficients, so a column of a batch sees what its own solve would compute."""
+    st = solver._new_state()
+    if isinstance(solver, OptISTA):
+        solver._set_theta(st, theta)
+        hist = [(st.theta, st.thetaold)]
+    else:
+        st.theta = st.thetaold = float(theta)
+        st.sigma = 1.0
+        hist = [(st.theta, st.thetaold, st.gamma)]
+    st.iteration = 0
+    rows = []
+    for _ in range(solver.iterations):
+        r, after = solver._table_row(st)
+        st.iteration += 1
+        rows.append(tuple(r) + (0.0,) * (8 - len(r)))
+        hist.append(after)
+    return np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 8), hist
+
+
+class PgmBatchedState(BatchedState):
+    """BatchedState for OptISTA and POGM: the K gradient points share one pass over A per product (rls_pgm_*_batched);
+    prox, momentum, POGM's gradient restart and `done` are per column, exactly as K independent solves.  POGM swaps its x / y
+    buffers every iteration and columns retire at different iterations: column j's x is in X when its own iteration count
+    is even, in Y when it is odd."""
+
+    def __init__(self, solver, B: DeviceMatrix):
+        self.states = []
+        self.active = [True] * B.N
+        self.solver = solver
+        self.K = B.N
+        op, ctx, N = solver._op, B.ctx, solver._op.N
+        self.kind = 0 if isinstance(solver, OptISTA) else 1
+        self.restart = self.kind == 1 and solver.restart == "gradient"
+        self.X, self.Y, self.Z, self.OLD, self.RES, self.X0 = (DeviceMatrix(N, B.N, B.dtype, ctx) for _ in range(6))
+        self.W = DeviceMatrix(N, B.N, B.dtype, ctx) if self.restart else None
+        plan = C.c_void_p()
+        check(ctx.handle, ctx.lib.rls_pgm_create_batched(op.handle, self.kind, B.N, self.X.ptr, self.Y.ptr, self.Z.ptr,
+                                                         self.W.ptr if self.W is not None else None, self.OLD.ptr,
+                                                         self.RES.ptr, self.X0.ptr, N, C.byref(plan)), "rls_pgm_create_batched")
+        self._plan = plan
+        self._keep = (op, ctx)
+        self.iteration = 0
+        self._hist = None
+
+    def init(self, B: DeviceMatrix, ref, fus, theta):
+        """init! of every column.  `ref`: the plain state the solver's scalars come from (rho, relTol, POGM's gamma / sigma_fac)"""
+        solver, ctx = self.solver, B.ctx
+        lib, h = ctx.lib, ctx.handle
+        f32 = np.float32
+        self.rho, self.relTol = ref.rho, ref.relTol
+        self.gamma0 = getattr(ref, "gamma", 1.0)
+        self.sigma_fac = getattr(ref, "sigma_fac", 1.0)
+        check(h, lib.rls_pgm_set_reg_batched(self._plan, fus[0], float(f32(solver.reg.lam)), fus[1]), "rls_pgm_set_reg_batched")
+        table, rows = None, 0
+        if not self.restart:
+            # the table depends on these scalars only: a repeated solve reuses it (and the graph captured with its address)
+            key = (self.kind, solver.iterations, float(theta), float(self.rho), float(solver.reg.lam), float(self.gamma0), ctx)
+            cached = getattr(solver, "_pgmb_table", None)
+            if cached is None or cached[0] != key:
+                coefs, hist = _pgm_batched_table(solver, theta)
+                dev = DeviceVector.from_host(coefs.reshape(-1), ctx) if len(coefs) else None
+                solver._pgmb_table = cached = (key, dev, hist)
+            table, self._hist, rows = cached[1], cached[2], solver.iterations
+        self._table = table  # (keeps the device array alive as long as the plan may read it)
+        check(h, lib.rls_pgm_init_batched(self._plan, B.ptr, B.lda, float(f32(self.rho)), float(f32(theta)),
+                                          float(f32(self.sigma_fac)), float(f32(self.gamma0)), float(self.relTol),
+                                          solver.iterations, int(self.restart), table.ptr if table is not None else None,
+                                          rows), "rls_pgm_init_batched")
+        self.iteration = 0
+        self.active = [True] * self.K
+
+    def _step(self, n):
+        ctx = self.X.ctx
+        check(ctx.handle, ctx.lib.rls_pgm_step_batched(self._plan, int(n)), "rls_pgm_step_batched")
+
+    def status(self):
+        st = (PgmStatus * self.K)()
+        ctx = self.X.ctx
+        check(ctx.handle, ctx.lib.rls_pgm_get_status_batched(self._plan, st), "rls_pgm_get_status_batched")
+        out = list(st)
+        if self._hist is not None:  # index-only scalars: the host's recurrence at the column's own count
+            for s_ in out:
+                hv = self._hist[s_.iteration]
+                s_.theta, s_.theta_old = hv[0], hv[1]
+                s_.gamma = hv[2] if len(hv) > 2 else 0.0
+        return out
+
+    def convergence(self):
+        return [{"residual": s.res_norm} for s in self.status()]
+
+    def solutions(self) -> List[DeviceVector]:
+        if self.kind == 0:
+            return [self.X.column(j) for j in range(self.K)]
+        return [(self.Y if s.iteration & 1 else self.X).column(j) for j, s in enumerate(self.status())]
+
+    def _plain(self):
+        """the solver's state for a vector right-hand side again (init_ restores it): rho, relTol and, POGM, sigma_fac and the
+        gamma column 0 ended with -- init! does not reset gamma in the reference, and column 0's state is the one the
+        per-column schedulers hand on as well"""
+        names = ("x", "x0", "y", "z", "zold", "res") if self.kind == 0 else ("x", "x0", "xold", "y", "z", "w", "res")
+        st = _ProxGradState(self.rho, 1.0, self.relTol, names)
+        if self.kind == 1:
+            st.gamma = float(self.status()[0].gamma)
+            st.sigma, st.sigma_fac = 1.0, self.sigma_fac
+        return st
+
+    def __del__(self):
+        try:
+            if self._plan and self.X.ctx.handle:
+                self.X.ctx.lib.rls_pgm_destroy_batched(self._plan)
+        except Exception:
+            pass
+        self._plan = None
+
+
 class AdmmBatchedState(BatchedState):
     """BatchedState for ADMM (one regulariser, identity regTrafo, vary_rho = :none): the K columns' cg! iterations share
     one pass over A per product (rls_cg_create_batched + rls_admm_step on N x K matrices); prox, z / u updates, the
@@ -2253,6 +2387,8 @@ def _check_eltype(solver, b):
 def init_(solver: AbstractLinearSolver, b, scheduler=SequentialState, **kw):
     """init!(solver, b; kwargs...)   src/RegularizedLeastSquares.jl:190, src/MultiThreading.jl:30-43"""
     _check_eltype(solver, b)
+    if isinstance(solver.state, PgmBatchedState):
+        solver.state = solver.state._plain()  # (a matrix right-hand side below builds its state from this one)
     if isinstance(b, DeviceVector):
         if isinstance(solver.state, AdmmBatchedState):
             ref = solver.state
@@ -2303,6 +2439,19 @@ def init_(solver: AbstractLinearSolver, b, scheduler=SequentialState, **kw):
                 check(h, lib.rls_fista_init_batched(st._plan, b.ptr, b.lda, float(st.rho), float(kw.get("theta", 1)),
                                                     float(st.relTol), solver.iterations,
                                                     1 if solver.restart == "gradient" else 0), "rls_fista_init_batched")
+                solver.state = st
+                return
+            except _lib.RLSError:
+                pass  # e.g. M or N not a multiple of 16: independent per-column plans instead
+        if (type(solver) in (OptISTA, POGM) and isinstance(b, DeviceMatrix) and b.N > 1 and solver.A is not None
+                and isinstance(solver._op, OperatorHandle) and not solver._op.double
+                and _fusable_kinds(solver.reg, solver.proj if type(solver) is POGM else []) is not None
+                and not isinstance(solver.normalizeReg, MeasurementBasedNormalization)
+                and kw_fista_ok):
+            ref = solver.state.states[0] if isinstance(solver.state, AbstractMatrixSolverState) and solver.state.states else solver.state
+            try:
+                st = PgmBatchedState(solver, b)
+                st.init(b, ref, _fusable_kinds(solver.reg, solver.proj if type(solver) is POGM else []), kw.get("theta", 1))
                 solver.state = st
                 return
             except _lib.RLSError:
@@ -2379,7 +2528,7 @@ def solve_(solver: AbstractLinearSolver, b, callbacks=None, **kw):
         cb(solver, 0)
     if not cbs and isinstance(solver.state, BatchedState):
         st = solver.state
-        st._step(solver.iterations if isinstance(st, FistaBatchedState) else min(solver.iterations, solver._op.N))
+        st._step(solver.iterations if isinstance(st, (FistaBatchedState, PgmBatchedState)) else min(solver.iterations, solver._op.N))
         while iterate(solver) is not None:  # normally returns None at once
             pass
         return solversolution(solver)
