@@ -36,9 +36,10 @@ typedef struct rls_fista rls_fista;       /* fused FISTA plan                   
 typedef struct rls_cg rls_cg;             /* fused cg! plan (ADMM x-update)                        */
 
 enum { RLS_F32 = 0, RLS_C32 = 1 };                 /* Float32, ComplexF32                          */
-/* Float64 / ComplexF64: accepted by the rls_*_d entry points ONLY (the L1 protocol with double scalars, at the end of the
- * vector section); every other entry point -- the fused plans, the resident and matrix-core kernels -- is Float32 / ComplexF32
- * (north_star) and answers RLS_E_INVALID for these codes. */
+/* Float64 / ComplexF64: accepted by the entry points whose names end in _d -- the L1 protocol with double scalars (rls_fill_d ...
+ * rls_kaczmarz_sweep_d, at the end of the vector section) and the double-precision CGNR / FISTA device plans (rls_cgnr_*_d,
+ * rls_fista_*_d, behind the fused FISTA section).  Every other entry point -- the Float32 plans, the resident and matrix-core
+ * kernels, the batched and row-sharded plans -- is Float32 / ComplexF32 and answers RLS_E_INVALID for these codes. */
 enum { RLS_F64 = 2, RLS_C64 = 3 };
 enum { RLS_OP_N = 0, RLS_OP_T = 1, RLS_OP_C = 2 }; /* A, transpose(A), adjoint(A)                  */
 enum { RLS_NORMAL_MATRIXFREE = 0, RLS_NORMAL_GRAM = 1 };
@@ -519,6 +520,58 @@ int32_t rls_fista_path(rls_fista* s, int32_t* out);
 int32_t rls_fista_get_status(rls_fista* s, rls_fista_status* out_h); /* synchronises; recovers lost resident launches as rls_cgnr_get_status */
 int32_t rls_fista_step_status(rls_fista* s, int32_t n_steps, rls_fista_status* out_h); /* step + status, one synchronisation */
 int32_t rls_fista_solution(rls_fista* s, void** x_out); /* device pointer currently holding state.x */
+
+/* ---------------------------------------------------------------------------------------------
+ * CGNR / FISTA device plans for Float64 / ComplexF64 (dtype RLS_F64 / RLS_C64; anything else: RLS_E_INVALID).
+ * The reference runs every solver in Float32 AND Float64 (test/testSolvers.jl:242); these are init! / iterate / done of
+ * src/CGNR.jl:107-185 and src/FISTA.jl:110-185 with double scalars.  The plans take raw pointers (no rls_operator):
+ * A is M x N column-major with leading dimension lda, AHA (the explicit Gram matrix) N x N with ldg; either may be null,
+ * not both.  With only AHA, b has length N and is A^H b; with both, the iterations run on AHA and init uses A -- as the
+ * Float32 plans.  A streaming pipeline: per iteration t = A p, v = A^H t (one product v = AHA p in Gram mode) and one
+ * update kernel, FISTA one more for the extrapolated point; every scalar, `iteration` and `done` live in a device record,
+ * a launch that finds `done` set changes nothing, and no call but *_get_status_d / *_step_status_d / rls_fista_solution_d
+ * synchronises.  Reductions are fixed-order in double: results are bit-identical run to run.
+ * The state vectors are the caller's, length N; their roles are those of rls_cgnr_create / rls_fista_create.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct rls_cgnr_d rls_cgnr_d;   /* CGNR plan in double precision  */
+typedef struct rls_fista_d rls_fista_d; /* FISTA plan in double precision */
+typedef struct rls_cgnr_status_d {
+  int32_t iteration, done;   /* done = converged || iteration >= min(iterations, N)   src/CGNR.jl:181-185 */
+  double alpha_re, alpha_im; /* state.alphal */
+  double beta_re, beta_im;
+  double zeta;     /* ||r||^2 at the start of the last iteration */
+  double residual; /* ||r|| now   src/CGNR.jl:136 */
+  double z0;       /* ||A^H b|| */
+} rls_cgnr_status_d;
+typedef struct rls_fista_status_d {
+  int32_t iteration, done;
+  double theta, theta_old;
+  double rel_res_norm; /* ||res|| / ||x0||   src/FISTA.jl:156 */
+  double residual;     /* ||res||   src/FISTA.jl:131 */
+  double norm_x0;
+} rls_fista_status_d;
+int32_t rls_cgnr_create_d(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* A, int64_t lda, const void* AHA, int64_t ldg,
+                          void* x, void* r, void* p, void* v, rls_cgnr_d** out);
+int32_t rls_cgnr_destroy_d(rls_cgnr_d* s);
+int32_t rls_cgnr_init_d(rls_cgnr_d* s, const void* b, double lambda, double rel_tol, int32_t iterations);
+int32_t rls_cgnr_step_d(rls_cgnr_d* s, int32_t n_steps); /* enqueues n_steps iterations on the context's stream; asynchronous */
+int32_t rls_cgnr_get_status_d(rls_cgnr_d* s, rls_cgnr_status_d* out_h); /* synchronises */
+int32_t rls_cgnr_step_status_d(rls_cgnr_d* s, int32_t n_steps, rls_cgnr_status_d* out_h); /* step + ONE read of the record: one `iterate` under callbacks */
+int32_t rls_cgnr_path_d(rls_cgnr_d* s, int32_t* out); /* the codes of rls_cgnr_path: 0 = two products + update, 2 = Gram mode */
+int32_t rls_fista_create_d(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* A, int64_t lda, const void* AHA, int64_t ldg,
+                           void* x, void* x0, void* xold, void* res, rls_fista_d** out);
+int32_t rls_fista_destroy_d(rls_fista_d* s);
+/* RLS_REG_NONE / L1 / L2 / L21 (with l21_slices) and one projection; RLS_REG_TV or an unknown kind: RLS_E_UNSUPPORTED with
+ * nothing changed -- the host then drives FISTA from the rls_*_d primitives.  Call ahead of rls_fista_init_d. */
+int32_t rls_fista_set_reg_d(rls_fista_d* s, int32_t reg_kind, double lambda, int64_t l21_slices, int32_t proj_kind);
+int32_t rls_fista_init_d(rls_fista_d* s, const void* b, double rho, double theta, double rel_tol, int32_t iterations,
+                         int32_t restart_gradient);
+int32_t rls_fista_set_start_d(rls_fista_d* s, const void* x_init, int64_t n); /* x0 != 0, right after init (as rls_fista_set_start) */
+int32_t rls_fista_step_d(rls_fista_d* s, int32_t n_steps);
+int32_t rls_fista_get_status_d(rls_fista_d* s, rls_fista_status_d* out_h); /* synchronises */
+int32_t rls_fista_step_status_d(rls_fista_d* s, int32_t n_steps, rls_fista_status_d* out_h);
+int32_t rls_fista_solution_d(rls_fista_d* s, void** x_out); /* device pointer currently holding state.x: x for an even iteration count, xold for an odd one; answers from the last status read when nothing was enqueued since, else synchronises */
+int32_t rls_fista_path_d(rls_fista_d* s, int32_t* out);
 
 /* ---------------------------------------------------------------------------------------------
  * fused cg!   replaces IterativeSolvers.cg!(x, AHA + rho*I, b; maxiter, reltol, statevars)

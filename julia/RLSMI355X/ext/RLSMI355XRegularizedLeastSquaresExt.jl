@@ -271,6 +271,177 @@ function iterate(solver::FISTA, state::FISTAState{rT,<:RLSVector}) where {rT<:Fl
   return state.x, state
 end
 
+# ---- Float64 / ComplexF64: CGNR and FISTA as device plans (rls_cgnr_*_d, rls_fista_*_d) --------------------------------
+# The plans take raw pointers (a double-precision RLSMatrix carries no rls_operator): A, and AHA when it is an explicit matrix
+# (the iterations then run on it).  Scalars, `iteration` and `done` live on the device; iterate is one step_status_d call.
+struct CgnrStatusD   # rls_cgnr_status_d, field for field
+  iteration::Int32; done::Int32; alpha_re::Float64; alpha_im::Float64; beta_re::Float64; beta_im::Float64
+  zeta::Float64; residual::Float64; z0::Float64
+end
+struct FistaStatusD   # rls_fista_status_d, field for field
+  iteration::Int32; done::Int32; theta::Float64; theta_old::Float64; rel_res_norm::Float64; residual::Float64; norm_x0::Float64
+end
+
+"(A pointer, lda, AHA pointer, ldg, M, N) of a solver's operands for the double-precision plans, or nothing"
+function operands_d(A, AHA)
+  a = A isa RLSMatrix ? A : nothing
+  g = AHA isa RLSMatrix ? AHA : nothing
+  (a === nothing && g === nothing) && return nothing
+  (a === nothing || AHA isa RLSNormalOp || g !== nothing) || return nothing   # another operator type behind AHA: the reference's own loop
+  N = a === nothing ? g.N : a.N
+  (a === nothing ? C_NULL : a.ptr, a === nothing ? 0 : a.lda, g === nothing ? C_NULL : g.ptr, g === nothing ? 0 : g.lda,
+   a === nothing ? 0 : a.M, N)
+end
+
+function plan_for(solver::CGNR, state::CGNRState{T,Tc,<:RLSVector}) where {T,Tc<:RLSDouble}
+  get!(cgnr_plans, state) do
+    ops = operands_d(solver.A, solver.AHA)
+    ops === nothing && return C_NULL
+    pa, lda, pg, ldg, M, N = ops
+    ctx = state.x.ctx
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ctx, ccall((:rls_cgnr_create_d, librls[]), Int32,
+                     (Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
+                     ctx.handle, dtypecode(Tc), M, N, pa, lda, pg, ldg, state.x.ptr, state.x₀.ptr, state.pl.ptr, state.vl.ptr, p), "rls_cgnr_create_d")
+    finalizer(_ -> ccall((:rls_cgnr_destroy_d, librls[]), Int32, (Ptr{Cvoid},), p[]), state)
+    p[]
+  end
+end
+
+function cgnr_take!(state::CGNRState{T,Tc}, st::CgnrStatusD) where {T,Tc}
+  state.iteration = st.iteration; state.z0 = st.z0
+  state.αl = Tc <: Complex ? Tc(st.alpha_re, st.alpha_im) : Tc(st.alpha_re)
+  state.βl = Tc(st.beta_re); state.ζl = Tc(st.zeta)
+  cgnr_done[state] = st.done != 0
+  st
+end
+
+function init!(solver::CGNR, state::CGNRState{T,Tc,vecTc}, b::vecTc; x0 = 0) where {T,Tc<:RLSDouble,vecTc<:RLSVector{Tc}}
+  all(x0 .== 0) || error("CGNR: x0 != 0 is unsupported (the reference's branch throws as well, src/CGNR.jl:119)")
+  plan = plan_for(solver, state)
+  plan == C_NULL && return invoke(init!, Tuple{CGNR,CGNRState{T,Tc,V},V} where {V<:AbstractVector{Tc}}, solver, state, b; x0)
+  solver.L2 = normalize(solver, solver.normalizeReg, solver.L2, solver.A, b)
+  check(b.ctx, ccall((:rls_cgnr_init_d, librls[]), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Int32),
+                     plan, b.ptr, Float64(λ(solver.L2)), Float64(state.relTol), solver.iterations), "rls_cgnr_init_d")
+  state.iteration = 0
+  delete!(cgnr_done, state)
+  nothing
+end
+
+function iterate(solver::CGNR, state::CGNRState{T,Tc,<:RLSVector}) where {T,Tc<:RLSDouble}
+  plan = plan_for(solver, state)
+  plan == C_NULL && return invoke(iterate, Tuple{CGNR,CGNRState}, solver, state)
+  st = Ref{CgnrStatusD}()
+  if !haskey(cgnr_done, state)
+    check(state.x.ctx, ccall((:rls_cgnr_get_status_d, librls[]), Int32, (Ptr{Cvoid}, Ref{CgnrStatusD}), plan, st), "rls_cgnr_get_status_d")
+    cgnr_take!(state, st[])
+  end
+  if cgnr_done[state]
+    for r in solver.constr
+      prox!(r, state.x)
+    end
+    return nothing
+  end
+  check(state.x.ctx, ccall((:rls_cgnr_step_status_d, librls[]), Int32, (Ptr{Cvoid}, Int32, Ref{CgnrStatusD}), plan, 1, st), "rls_cgnr_step_status_d")
+  cgnr_take!(state, st[])
+  return state.x, state
+end
+
+"enqueue n iterations of a double-precision CGNR plan without a read-back (rls_cgnr_step_d)"
+function cgnr_step_d!(solver::CGNR, state::CGNRState, n::Integer)
+  check(state.x.ctx, ccall((:rls_cgnr_step_d, librls[]), Int32, (Ptr{Cvoid}, Int32), plan_for(solver, state), n), "rls_cgnr_step_d")
+end
+"which kernel sequence a double-precision CGNR plan runs: 0 = two products + update, 2 = Gram mode (rls_cgnr_path_d)"
+function cgnr_path_d(solver::CGNR, state::CGNRState)
+  out = Ref{Int32}(-1)
+  check(state.x.ctx, ccall((:rls_cgnr_path_d, librls[]), Int32, (Ptr{Cvoid}, Ref{Int32}), plan_for(solver, state), out), "rls_cgnr_path_d")
+  out[]
+end
+
+function fista_plan_for(solver::FISTA, state::FISTAState{rT,<:RLSVector}) where {rT<:Float64}
+  haskey(fista_plans, state) && return fista_plans[state]
+  ops = operands_d(solver.A, solver.AHA)
+  kind = fused_reg(solver.reg)
+  (ops === nothing || kind === nothing || kind[1] == RLS_REG_TV || fused_proj(solver.proj) === nothing) && return C_NULL
+  pa, lda, pg, ldg, M, N = ops
+  ctx = state.x.ctx
+  p = Ref{Ptr{Cvoid}}(C_NULL)
+  check(ctx, ccall((:rls_fista_create_d, librls[]), Int32,
+                   (Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
+                   ctx.handle, dtypecode(eltype(state.x)), M, N, pa, lda, pg, ldg, state.x.ptr, state.x₀.ptr, state.xᵒˡᵈ.ptr, state.res.ptr, p),
+        "rls_fista_create_d")
+  finalizer(_ -> ccall((:rls_fista_destroy_d, librls[]), Int32, (Ptr{Cvoid},), p[]), state)
+  fista_plans[state] = p[]
+end
+
+function fista_status_d(state, plan)
+  st = Ref{FistaStatusD}()
+  check(state.x.ctx, ccall((:rls_fista_get_status_d, librls[]), Int32, (Ptr{Cvoid}, Ref{FistaStatusD}), plan, st), "rls_fista_get_status_d")
+  st[]
+end
+
+function fista_refresh_d!(state, plan, st = fista_status_d(state, plan))
+  state.iteration = st.iteration; state.theta = st.theta; state.thetaᵒˡᵈ = st.theta_old
+  st.iteration > 0 && (state.rel_res_norm = st.rel_res_norm)
+  sol = Ref{Ptr{Cvoid}}(C_NULL)
+  check(state.x.ctx, ccall((:rls_fista_solution_d, librls[]), Int32, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), plan, sol), "rls_fista_solution_d")
+  if state.x.ptr != sol[]
+    state.x, state.xᵒˡᵈ = state.xᵒˡᵈ, state.x
+  end
+  st
+end
+
+function init!(solver::FISTA, state::FISTAState{rT,vecT}, b::vecT; x0 = 0, theta = 1) where {rT<:Float64,vecT<:RLSVector}
+  plan = fista_plan_for(solver, state)
+  generic = Tuple{FISTA,FISTAState{rT,V},V} where {V<:Union{AbstractVector{rT},AbstractVector{Complex{rT}}}}
+  plan == C_NULL && return invoke(init!, generic, solver, state, b; x0, theta)
+  ctx = state.x.ctx
+  if !(solver.normalizeReg isa NoNormalization)
+    solver.A === nothing ? copyto!(state.x₀, b) : mul!(state.x₀, adjoint(solver.A), b)
+    solver.reg = normalize(solver, solver.normalizeReg, solver.reg, solver.A, state.x₀)
+  end
+  kind, slices = fused_reg(solver.reg)
+  rc = ccall((:rls_fista_set_reg_d, librls[]), Int32, (Ptr{Cvoid}, Int32, Float64, Int64, Int32),
+             plan, kind, Float64(λ(solver.reg)), slices, fused_proj(solver.proj))
+  if rc == -2                                          # RLS_E_UNSUPPORTED: the reference's loop on the primitives
+    fista_plans[state] = C_NULL
+    return invoke(init!, generic, solver, state, b; x0, theta)
+  end
+  check(ctx, rc, "rls_fista_set_reg_d")
+  check(ctx, ccall((:rls_fista_init_d, librls[]), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Int32, Int32),
+                   plan, b.ptr, Float64(state.ρ), Float64(theta), Float64(state.relTol), solver.iterations, solver.restart == :gradient), "rls_fista_init_d")
+  if !all(x0 .== 0)
+    xs = x0 isa RLSVector ? x0 : fill!(similar(state.x), x0)
+    length(xs) == length(state.x) || throw(DimensionMismatch("x0 has length $(length(xs)), the solution $(length(state.x))"))
+    check(ctx, ccall((:rls_fista_set_start_d, librls[]), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64), plan, xs.ptr, length(xs)), "rls_fista_set_start_d")
+  end
+  st = fista_refresh_d!(state, plan)
+  state.iteration = 0; state.norm_x₀ = st.norm_x0; state.theta = theta; state.thetaᵒˡᵈ = theta; state.rel_res_norm = rT(Inf)
+  nothing
+end
+
+function iterate(solver::FISTA, state::FISTAState{rT,<:RLSVector}) where {rT<:Float64}
+  plan = get(fista_plans, state, C_NULL)
+  plan == C_NULL && return invoke(iterate, Tuple{FISTA,FISTAState}, solver, state)
+  done(solver, state) && return nothing
+  st = Ref{FistaStatusD}()
+  check(state.x.ctx, ccall((:rls_fista_step_status_d, librls[]), Int32, (Ptr{Cvoid}, Int32, Ref{FistaStatusD}), plan, 1, st), "rls_fista_step_status_d")
+  fista_refresh_d!(state, plan, st[])
+  solver.verbose && println("Iteration $(state.iteration); rel. residual = $(state.rel_res_norm)")
+  return state.x, state
+end
+
+"enqueue n iterations of a double-precision FISTA plan without a read-back (rls_fista_step_d)"
+function fista_step_d!(state::FISTAState, n::Integer)
+  check(state.x.ctx, ccall((:rls_fista_step_d, librls[]), Int32, (Ptr{Cvoid}, Int32), fista_plans[state], n), "rls_fista_step_d")
+end
+"rls_fista_path_d: 0 = two products + update, 2 = Gram mode"
+function fista_path_d(state::FISTAState)
+  out = Ref{Int32}(-1)
+  check(state.x.ctx, ccall((:rls_fista_path_d, librls[]), Int32, (Ptr{Cvoid}, Ref{Int32}), fista_plans[state], out), "rls_fista_path_d")
+  out[]
+end
+
 # ---- fused ADMM: whole outer iterations as a device plan (src/ADMM.jl:191-220, :230-322) -----------------------
 struct AdmmParams
   x::Ptr{Cvoid}; xold::Ptr{Cvoid}; beta::Ptr{Cvoid}; beta_y::Ptr{Cvoid}; z0::Ptr{Cvoid}; z1::Ptr{Cvoid}; u::Ptr{Cvoid}

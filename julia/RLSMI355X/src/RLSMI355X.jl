@@ -12,7 +12,7 @@ using LinearAlgebra, Libdl
 const librls = Ref{String}(get(ENV, "RLS_MI355X_LIB", "librls_mi355x.so"))
 
 const RLS_F32 = Int32(0); const RLS_C32 = Int32(1)
-const RLS_F64 = Int32(2); const RLS_C64 = Int32(3)   # the rls_*_d entry points only: the L1 protocol with double scalars
+const RLS_F64 = Int32(2); const RLS_C64 = Int32(3)   # the *_d entry points only: the L1 protocol with double scalars and the CGNR / FISTA plans rls_cgnr_*_d / rls_fista_*_d
 "element types of the tuned path (fused plans, resident kernels, matrix cores) / of the double-precision L1 protocol"
 const RLSSingle = Union{Float32, ComplexF32}
 const RLSDouble = Union{Float64, ComplexF64}

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librls_mi355x.so")
 
 F32, C32 = 0, 1
-F64, C64 = 2, 3   # the rls_*_d entry points only (the L1 protocol with double scalars)
+F64, C64 = 2, 3   # the *_d entry points only: the L1 protocol with double scalars and the double-precision CGNR / FISTA plans
 OP_N, OP_T, OP_C = 0, 1, 2
 REG_NONE, REG_L1, REG_L2, REG_L21, REG_TV = 0, 1, 2, 3, 4
 PROJ_NONE, PROJ_REAL, PROJ_POSITIVE = 0, 1, 2
@@ -32,6 +32,17 @@ class CgnrStatus(C.Structure):
 class FistaStatus(C.Structure):
     _fields_ = [("iteration", C.c_int32), ("done", C.c_int32), ("theta", C.c_float), ("theta_old", C.c_float),
                 ("rel_res_norm", C.c_float), ("residual", C.c_float), ("norm_x0", C.c_float), ("fallbacks", C.c_int32)]
+
+
+class CgnrStatusD(C.Structure):
+    _fields_ = [("iteration", C.c_int32), ("done", C.c_int32), ("alpha_re", C.c_double), ("alpha_im", C.c_double),
+                ("beta_re", C.c_double), ("beta_im", C.c_double), ("zeta", C.c_double), ("residual", C.c_double),
+                ("z0", C.c_double)]
+
+
+class FistaStatusD(C.Structure):
+    _fields_ = [("iteration", C.c_int32), ("done", C.c_int32), ("theta", C.c_double), ("theta_old", C.c_double),
+                ("rel_res_norm", C.c_double), ("residual", C.c_double), ("norm_x0", C.c_double)]
 
 
 class PgmStatus(C.Structure):
@@ -193,6 +204,24 @@ PROTOTYPES = {
     "rls_fista_get_status": (_i32, [_vp, C.POINTER(FistaStatus)]),
     "rls_fista_step_status": (_i32, [_vp, _i32, C.POINTER(FistaStatus)]),
     "rls_fista_solution": (_i32, [_vp, _pvp]),
+    # ---- Float64 / ComplexF64 device plans (csrc/plans_f64.hip) ----
+    "rls_cgnr_create_d": (_i32, [_vp, _i32, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _pvp]),
+    "rls_cgnr_destroy_d": (_i32, [_vp]),
+    "rls_cgnr_init_d": (_i32, [_vp, _vp, _d, _d, _i32]),
+    "rls_cgnr_step_d": (_i32, [_vp, _i32]),
+    "rls_cgnr_get_status_d": (_i32, [_vp, C.POINTER(CgnrStatusD)]),
+    "rls_cgnr_step_status_d": (_i32, [_vp, _i32, C.POINTER(CgnrStatusD)]),
+    "rls_cgnr_path_d": (_i32, [_vp, C.POINTER(C.c_int32)]),
+    "rls_fista_create_d": (_i32, [_vp, _i32, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _pvp]),
+    "rls_fista_destroy_d": (_i32, [_vp]),
+    "rls_fista_set_reg_d": (_i32, [_vp, _i32, _d, _i64, _i32]),
+    "rls_fista_init_d": (_i32, [_vp, _vp, _d, _d, _d, _i32, _i32]),
+    "rls_fista_set_start_d": (_i32, [_vp, _vp, _i64]),
+    "rls_fista_step_d": (_i32, [_vp, _i32]),
+    "rls_fista_get_status_d": (_i32, [_vp, C.POINTER(FistaStatusD)]),
+    "rls_fista_step_status_d": (_i32, [_vp, _i32, C.POINTER(FistaStatusD)]),
+    "rls_fista_solution_d": (_i32, [_vp, _pvp]),
+    "rls_fista_path_d": (_i32, [_vp, C.POINTER(C.c_int32)]),
     "rls_cg_create": (_i32, [_vp, _vp, _vp, _vp, _pvp]),
     "rls_cg_create_batched": (_i32, [_vp, _i32, _vp, _vp, _vp, C.c_int64, _pvp]),
     "rls_cg_destroy": (_i32, [_vp]),

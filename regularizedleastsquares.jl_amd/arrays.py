@@ -29,7 +29,9 @@ def dtype_code(dt) -> int:
 
 
 def is_double(code: int) -> bool:
-    """Float64 / ComplexF64: the rls_*_d entry points (the L1 protocol with double scalars); no fused plans, no resident kernels"""
+    """Float64 / ComplexF64: the *_d entry points -- the L1 protocol with double scalars (rls_fill_d ... rls_gemv_d, the prox maps)
+    and, for CGNR and FISTA, the streaming device plans rls_cgnr_*_d / rls_fista_*_d (scalars on the device, no read-back inside a
+    solve without callbacks).  No resident or matrix-core kernels; every other solver runs its loop on the primitives."""
     return code in (F64, C64)
 
 
@@ -436,8 +438,8 @@ class OperatorHandle:
         self.double = is_double(self.code)
         self._t = None
         if self.double:
-            # Float64 / ComplexF64: no rls_operator (the fused plans are Float32 / ComplexF32): v = AHA p is the explicit Gram GEMV or
-            # the two GEMVs of the matrix-free normal operator, through rls_gemv_d
+            # Float64 / ComplexF64: no rls_operator (the double-precision plans take raw pointers): v = AHA p is the explicit Gram GEMV
+            # or the two GEMVs of the matrix-free normal operator, through rls_gemv_d
             self.handle = None
             return
         o = C.c_void_p()

@@ -20,8 +20,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import (PROJ_NONE, PROJ_POSITIVE, PROJ_REAL, REG_L1, REG_L2, REG_L21, REG_NONE, REG_TV, AdmmParams,
-                   AdmmStatus, CgnrStatus, CgStatus,
-                   FistaStatus, PgmStatus, check)
+                   AdmmStatus, CgnrStatus, CgnrStatusD, CgStatus,
+                   FistaStatus, FistaStatusD, PgmStatus, check)
 from .arrays import DeviceMatrix, DeviceVector, NormalOperator, OperatorHandle, is_double
 from .regularization import (AbstractParameterizedRegularization, AbstractProjectionRegularization, GradientOp,
                              L1Regularization, L2Regularization, findsink, findsinks, is_projection, sink,
@@ -147,18 +147,32 @@ class CGNRState(AbstractSolverState):
         self.relTol = float(relTol)
         self.z0 = 0.0
         self._plan = None
+        self._plan_d = False   # the plan is a Float64 / ComplexF64 one (rls_cgnr_*_d)
         self._done = False
 
     def _refresh(self, lib):
+        if self._plan_d:
+            st = CgnrStatusD()
+            check(self.x.ctx.handle, lib.rls_cgnr_get_status_d(self._plan, C.byref(st)), "rls_cgnr_get_status_d")
+            return self._take(st)
         st = CgnrStatus()
         check(self.x.ctx.handle, lib.rls_cgnr_get_status(self._plan, C.byref(st)), "rls_cgnr_get_status")
         return self._take(st)
 
     def _step_status(self, lib, n):
         """advance n iterations and read the status back in ONE call (one host synchronisation): rls_cgnr_step_status"""
+        if self._plan_d:
+            st = CgnrStatusD()
+            check(self.x.ctx.handle, lib.rls_cgnr_step_status_d(self._plan, int(n), C.byref(st)), "rls_cgnr_step_status_d")
+            return self._take(st)
         st = CgnrStatus()
         check(self.x.ctx.handle, lib.rls_cgnr_step_status(self._plan, int(n), C.byref(st)), "rls_cgnr_step_status")
         return self._take(st)
+
+    def _drop_plan(self, lib):
+        if self._plan:
+            (lib.rls_cgnr_destroy_d if self._plan_d else lib.rls_cgnr_destroy)(self._plan)
+        self._plan, self._plan_d = None, False
 
     def _take(self, st):
         cplx = self.x.dtype.kind == "c"
@@ -169,7 +183,7 @@ class CGNRState(AbstractSolverState):
         self.z0 = st.z0
         self._done = bool(st.done)
         self._residual = st.residual
-        self.fallbacks = int(st.fallbacks)  # resident launches lost to a co-tenant and re-run on the pipeline
+        self.fallbacks = int(getattr(st, "fallbacks", 0))  # resident launches lost to a co-tenant and re-run on the pipeline
         self._status_valid = True
         return st
 
@@ -181,7 +195,7 @@ class CGNRState(AbstractSolverState):
     def __del__(self):
         try:
             if self._plan and self.x is not None and self.x.ctx.handle:
-                self.x.ctx.lib.rls_cgnr_destroy(self._plan)
+                self._drop_plan(self.x.ctx.lib)
         except Exception:
             pass
         self._plan = None
@@ -189,6 +203,10 @@ class CGNRState(AbstractSolverState):
 
 class CGNR(AbstractKrylovSolver):
     """src/CGNR.jl:48-89"""
+
+    # Float64 / ComplexF64 operators: True = the device plan (rls_cgnr_*_d: scalars on the device, no read-back inside a solve
+    # without callbacks); False = the reference's loop on the rls_*_d primitives (kept for A/B measurement)
+    use_device_plan_f64 = True
 
     def __init__(self, A=None, *, AHA=None, reg=None, normalizeReg=None, iterations: int = 10, relTol=None):
         self.A, self._op = _resolve_operator(A, AHA)
@@ -217,11 +235,15 @@ class CGNR(AbstractKrylovSolver):
             # the reference's x0 != 0 branch reads a field that does not exist (src/CGNR.jl:119)
             raise NotImplementedError("CGNR: x0 != 0 is unsupported (it throws in the reference as well)")
         lib = b.ctx.lib
-        if self._op.double:
+        if self._op.double and not self.use_device_plan_f64:
             return self._init_from_primitives(state, b)
         self._prepare(state, b)
-        check(b.ctx.handle, lib.rls_cgnr_init(state._plan, b.ptr, float(self.L2.lam), state.relTol, self.iterations),
-              "rls_cgnr_init")
+        if state._plan_d:
+            check(b.ctx.handle, lib.rls_cgnr_init_d(state._plan, b.ptr, float(self.L2.lam), state.relTol, self.iterations),
+                  "rls_cgnr_init_d")
+        else:
+            check(b.ctx.handle, lib.rls_cgnr_init(state._plan, b.ptr, float(self.L2.lam), state.relTol, self.iterations),
+                  "rls_cgnr_init")
         self._after_init(state)
 
     # ---- Float64 / ComplexF64: the reference's loop on the L1 protocol (rls_*_d), statement by statement ----------------------------
@@ -229,6 +251,7 @@ class CGNR(AbstractKrylovSolver):
         """init!  src/CGNR.jl:107-130 on the primitives"""
         N = self._op.N
         self.L2 = normalize(self.normalizeReg, self.L2, self.A, b, in_solver=True)  # :129
+        state._drop_plan(b.ctx.lib)   # (a plan of an earlier solve with use_device_plan_f64 = True)
         if state.x is None or state.x.ctx is not b.ctx or state.x.dtype != b.dtype or state.x.n != N:
             state.x, state.x0, state.pl, state.vl = (b.similar(N) for _ in range(4))
         expect = self._op.M if self.A is not None else N
@@ -287,14 +310,23 @@ class CGNR(AbstractKrylovSolver):
         N = self._op.N
         lib = b.ctx.lib
         self.L2 = normalize(self.normalizeReg, self.L2, self.A, b, in_solver=True)  # :129
-        if state.x is None or state.x.ctx is not b.ctx or state.x.dtype != b.dtype or state.x.n != N:
+        fresh = state.x is None or state.x.ctx is not b.ctx or state.x.dtype != b.dtype or state.x.n != N
+        if fresh:
             state.x, state.x0, state.pl, state.vl = (b.similar(N) for _ in range(4))  # similar(b, ...) :92-95
-            if state._plan:
-                lib.rls_cgnr_destroy(state._plan)
+        if fresh or not state._plan:
+            state._drop_plan(lib)
             plan = C.c_void_p()
-            check(b.ctx.handle, lib.rls_cgnr_create(self._op.handle, state.x.ptr, state.x0.ptr, state.pl.ptr,
-                                                    state.vl.ptr, C.byref(plan)), "rls_cgnr_create")
-            state._plan = plan
+            if self._op.double:
+                # Float64 / ComplexF64: the plan takes the raw pointers (no rls_operator); with both A and AHA it iterates on AHA
+                A, G = self._op.A, self._op.gram
+                check(b.ctx.handle, lib.rls_cgnr_create_d(b.ctx.handle, self._op.code, self._op.M, N, A.ptr if A is not None else None,
+                                                          A.lda if A is not None else 0, G.ptr if G is not None else None,
+                                                          G.lda if G is not None else 0, state.x.ptr, state.x0.ptr, state.pl.ptr,
+                                                          state.vl.ptr, C.byref(plan)), "rls_cgnr_create_d")
+            else:
+                check(b.ctx.handle, lib.rls_cgnr_create(self._op.handle, state.x.ptr, state.x0.ptr, state.pl.ptr,
+                                                        state.vl.ptr, C.byref(plan)), "rls_cgnr_create")
+            state._plan, state._plan_d = plan, self._op.double
             state._keep = (self._op, b.ctx)  # destruction order: plan before operator before context
         expect = self._op.M if self.A is not None else N
         if b.n != expect:
@@ -311,7 +343,7 @@ class CGNR(AbstractKrylovSolver):
         """iterate(solver, state)  src/CGNR.jl:143-178; returns None when done.  One library call per iteration: the step
         and the status read-back (`done`, the convergence record) travel together (rls_cgnr_step_status)"""
         state = state or self.state
-        if self._op.double:
+        if self._op.double and not state._plan:
             return self._iterate_from_primitives(state)
         lib = state.x.ctx.lib
         if not getattr(state, "_status_valid", False):
@@ -327,7 +359,7 @@ class CGNR(AbstractKrylovSolver):
 
     def _run(self, state: CGNRState):
         """no callbacks: enqueue every remaining iteration (no-ops once done) and finalise"""
-        if self._op.double:
+        if self._op.double and not state._plan:
             while self.iterate(state) is not None:
                 pass
             return
@@ -466,20 +498,34 @@ class FISTAState(AbstractSolverState):
         self.norm_x0 = 1.0
         self.rel_res_norm = math.inf
         self._plan = None
+        self._plan_d = False   # the plan is a Float64 / ComplexF64 one (rls_fista_*_d)
         self._bufs = None
         self._done = False
 
     def _refresh(self, lib):
-        st = FistaStatus()
         h = self._bufs[0].ctx.handle
+        if self._plan_d:
+            st = FistaStatusD()
+            check(h, lib.rls_fista_get_status_d(self._plan, C.byref(st)), "rls_fista_get_status_d")
+            return self._take(st)
+        st = FistaStatus()
         check(h, lib.rls_fista_get_status(self._plan, C.byref(st)), "rls_fista_get_status")
         return self._take(st)
 
     def _step_status(self, lib, n):
         """advance n iterations and read the status back in ONE call (rls_fista_step_status)"""
+        if self._plan_d:
+            st = FistaStatusD()
+            check(self._bufs[0].ctx.handle, lib.rls_fista_step_status_d(self._plan, int(n), C.byref(st)), "rls_fista_step_status_d")
+            return self._take(st)
         st = FistaStatus()
         check(self._bufs[0].ctx.handle, lib.rls_fista_step_status(self._plan, int(n), C.byref(st)), "rls_fista_step_status")
         return self._take(st)
+
+    def _drop_plan(self, lib):
+        if self._plan:
+            (lib.rls_fista_destroy_d if self._plan_d else lib.rls_fista_destroy)(self._plan)
+        self._plan, self._plan_d = None, False
 
     def _take(self, st):
         self.theta, self.thetaold = st.theta, st.theta_old
@@ -488,7 +534,7 @@ class FISTAState(AbstractSolverState):
         self.norm_x0 = st.norm_x0
         self._residual = st.residual
         self._done = bool(st.done)
-        self.fallbacks = int(st.fallbacks)
+        self.fallbacks = int(getattr(st, "fallbacks", 0))
         # the reference swaps x / xold by pointer every iteration (src/FISTA.jl:144-146)
         self.x, self.xold = (self._bufs[st.iteration & 1], self._bufs[(st.iteration + 1) & 1])
         self._status_valid = True
@@ -503,7 +549,7 @@ class FISTAState(AbstractSolverState):
     def __del__(self):
         try:
             if self._plan and self._bufs and self._bufs[0].ctx.handle:
-                self._bufs[0].ctx.lib.rls_fista_destroy(self._plan)
+                self._drop_plan(self._bufs[0].ctx.lib)
         except Exception:
             pass
         self._plan = None
@@ -512,6 +558,11 @@ class FISTAState(AbstractSolverState):
 class FISTA(AbstractProximalGradientSolver):
     """src/FISTA.jl:57-92.  `rho` defaults to 0.95 / power_iterations(AHA) as in the reference; pass it
     explicitly for reproducible runs (the reference's default depends on the global RNG)."""
+
+    # Float64 / ComplexF64 operators: True = the device plan (rls_fista_*_d) whenever it applies the regulariser (none / L1 / L2 / L21
+    # and at most one projection); False = the reference's loop on the rls_*_d primitives, which TV, nested, transformed and
+    # plug-and-play terms take in any case
+    use_device_plan_f64 = True
 
     def __init__(self, A=None, *, AHA=None, reg=None, normalizeReg=None, iterations: int = 50, verbose: bool = False,
                  rho=None, theta=1, relTol=None, restart: str = "none"):
@@ -541,8 +592,8 @@ class FISTA(AbstractProximalGradientSolver):
 
     def _fused_kinds(self):
         """(reg_kind, lambda, slices, proj_kind) when the update is fusable, else None"""
-        if self._op.double:
-            return None  # Float64 / ComplexF64: the reference's loop on the primitives (rls_*_d); the plans are Float32 / ComplexF32
+        if self._op.double and (not self.use_device_plan_f64 or getattr(self, "_refused_f64", None) is self.reg):
+            return None  # Float64 / ComplexF64 without a plan: the reference's loop on the primitives (rls_*_d)
         r = self.reg
         if type(r) is L1Regularization:
             kind, slices = REG_L1, 1
@@ -583,33 +634,52 @@ class FISTA(AbstractProximalGradientSolver):
         if fresh:
             state._bufs = [b.similar(N), b.similar(N)]
             state.x0, state.res = b.similar(N), b.similar(N)
-            if state._plan:
-                lib.rls_fista_destroy(state._plan)
-                state._plan = None
-            if fused is not None:
-                plan = C.c_void_p()
+        dbl = self._op.double
+        if fresh or fused is None:
+            state._drop_plan(lib)
+        if fused is not None and not state._plan:
+            plan = C.c_void_p()
+            if dbl:
+                A, G = self._op.A, self._op.gram   # raw pointers, no rls_operator; with both, the iterations run on AHA
+                check(h, lib.rls_fista_create_d(h, self._op.code, self._op.M, N, A.ptr if A is not None else None,
+                                                A.lda if A is not None else 0, G.ptr if G is not None else None,
+                                                G.lda if G is not None else 0, state._bufs[0].ptr, state.x0.ptr, state._bufs[1].ptr,
+                                                state.res.ptr, C.byref(plan)), "rls_fista_create_d")
+            else:
                 check(h, lib.rls_fista_create(self._op.handle, state._bufs[0].ptr, state.x0.ptr, state._bufs[1].ptr,
                                               state.res.ptr, C.byref(plan)), "rls_fista_create")
-                state._plan = plan
-                state._keep = (self._op, b.ctx)
+            state._plan, state._plan_d = plan, dbl
+            state._keep = (self._op, b.ctx)
         state.x, state.xold = state._bufs
-        if fused is not None and fused[0] == REG_TV:
+        if fused is not None and dbl:
+            kind, lam_, slices, pk = fused
+            st_d = lib.rls_fista_set_reg_d(state._plan, kind, lam_, slices, pk)
+            if st_d == -2:   # RLS_E_UNSUPPORTED (TV): this regulariser runs on the primitives
+                self._refused_f64 = self.reg
+                state._drop_plan(lib)
+                fused = None
+            else:
+                check(h, st_d, "rls_fista_set_reg_d")
+        if fused is not None and not dbl and fused[0] == REG_TV:
             from .regularization import _tv_geometry
             shape, d0, cs, cd = _tv_geometry(self.reg.shape, self.reg.dims)
             st_tv = lib.rls_fista_set_reg_tv(state._plan, fused[1], len(shape), cs, len(d0), cd, self.reg.iterationsTV, fused[3])
             if st_tv == -2:  # RLS_E_UNSUPPORTED: the image does not fit the plan's single-workgroup FGP launch -- primitives
                 self._tv_unfused = (tuple(np.atleast_1d(self.reg.shape)), self.reg.dims)   # (THIS geometry: another one is tried afresh)
-                lib.rls_fista_destroy(state._plan)
-                state._plan = None
+                state._drop_plan(lib)
                 fused = None
             else:
                 check(h, st_tv, "rls_fista_set_reg_tv")
         if fused is not None:
             kind, lam_, slices, pk = fused
-            if kind != REG_TV:
-                check(h, lib.rls_fista_set_reg(state._plan, kind, lam_, slices, pk), "rls_fista_set_reg")
-            check(h, lib.rls_fista_init(state._plan, b.ptr, state.rho, float(theta), state.relTol, self.iterations,
-                                        1 if self.restart == "gradient" else 0), "rls_fista_init")
+            if dbl:
+                check(h, lib.rls_fista_init_d(state._plan, b.ptr, state.rho, float(theta), state.relTol, self.iterations,
+                                              1 if self.restart == "gradient" else 0), "rls_fista_init_d")
+            else:
+                if kind != REG_TV:
+                    check(h, lib.rls_fista_set_reg(state._plan, kind, lam_, slices, pk), "rls_fista_set_reg")
+                check(h, lib.rls_fista_init(state._plan, b.ptr, state.rho, float(theta), state.relTol, self.iterations,
+                                            1 if self.restart == "gradient" else 0), "rls_fista_init")
             if not (np.ndim(x0) == 0 and not isinstance(x0, DeviceVector) and x0 == 0):
                 if isinstance(x0, DeviceVector):
                     xs = x0
@@ -619,7 +689,10 @@ class FISTA(AbstractProximalGradientSolver):
                     xs = DeviceVector.from_host(np.ascontiguousarray(np.asarray(x0, dtype=b.dtype).reshape(-1)), b.ctx)
                 if xs.n != N or xs.dtype != b.dtype:
                     raise ValueError(f"DimensionMismatch: x0 has length {xs.n} ({xs.dtype}), the solution {N} ({b.dtype})")
-                check(h, lib.rls_fista_set_start(state._plan, xs.ptr, xs.n), "rls_fista_set_start")
+                if dbl:
+                    check(h, lib.rls_fista_set_start_d(state._plan, xs.ptr, xs.n), "rls_fista_set_start_d")
+                else:
+                    check(h, lib.rls_fista_set_start(state._plan, xs.ptr, xs.n), "rls_fista_set_start")
         else:
             # generic path from primitives (TV prox etc.)
             if self.A is None:
@@ -2425,7 +2498,7 @@ def init_(solver: AbstractLinearSolver, b, scheduler=SequentialState, **kw):
                 return
             except _lib.RLSError:
                 pass  # shape not covered by the one-pass kernel: independent per-column plans instead
-        if (type(solver) is FISTA and isinstance(b, DeviceMatrix) and b.N > 1 and solver.A is not None
+        if (type(solver) is FISTA and isinstance(b, DeviceMatrix) and b.N > 1 and solver.A is not None and not solver._op.double
                 and solver._fused_kinds() is not None and solver._fused_kinds()[0] != REG_TV
                 and not isinstance(solver.normalizeReg, MeasurementBasedNormalization)
                 and kw_fista_ok):
