@@ -508,7 +508,9 @@ int32_t rls_fista_set_reg_tv(rls_fista* s, float lambda, int32_t ndims, const in
 int32_t rls_fista_init(rls_fista* s, const void* b, float rho, float theta, float rel_tol, int32_t iterations,
                        int32_t restart_gradient);
 /* optional warm start x0 != 0 (init!(solver, b; x0), src/FISTA.jl:110,120): call right after init.  x_init: n = N
- * elements (a scalar x0 is broadcast by the caller, as `state.x .= x0` does); RLS_E_INVALID on any other length */
+ * elements (a scalar x0 is broadcast by the caller, as `state.x .= x0` does); RLS_E_INVALID on any other length.
+ * x_init must not lie inside the plan's own x / xold vectors: rls_fista_init has reset them by now, so the vector a previous
+ * solve on this plan returned has to be copied by the caller BEFORE rls_fista_init (the Python binding does). */
 int32_t rls_fista_set_start(rls_fista* s, const void* x_init, int64_t n);
 int32_t rls_fista_step(rls_fista* s, int32_t n_steps);
 /* which kernel sequence the next rls_fista_step call takes (the codes of rls_cgnr_path): 0 = two GEMVs + update kernel,

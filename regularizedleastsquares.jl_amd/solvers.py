@@ -486,6 +486,45 @@ def power_iterations(AHA, b0: DeviceVector, rtol=1e-3, maxiter=30) -> float:
     return lam_
 
 
+def _state_vectors(state):
+    """every device vector a solver state owns: its attributes and one level of lists / tuples of them, which is where the
+    single-column states of this module keep their vectors (matrix-valued states and nested containers are not searched)"""
+    out = []
+    for v in vars(state).values():
+        for w in (v if isinstance(v, (list, tuple)) else [v]):
+            if isinstance(w, DeviceVector):
+                out.append(w)
+    return out
+
+
+def _start_vector(x0, b, N, state=None):
+    """the `x0` keyword of init!(solver, b; x0) (`state.x .= x0`, src/FISTA.jl:120, src/ADMM.jl:194, ...): a scalar (broadcast) is
+    returned as it is, anything else as a device vector of the solution's length and element type -- a wrong length or element
+    type is a DimensionMismatch.  A start that lies inside the state's own buffers (the vector the previous solve! on this
+    solver returned) is copied first: init! resets those buffers before it reads the start."""
+    if isinstance(x0, DeviceVector):
+        if x0.n != N or x0.dtype != b.dtype:
+            raise ValueError(f"DimensionMismatch: x0 has length {x0.n} ({x0.dtype}), the solution {N} ({b.dtype})")
+        lo, hi = x0.ptr, x0.ptr + x0.n * x0.dtype.itemsize
+        if state is not None and any(v.ptr < hi and lo < v.ptr + v.n * v.dtype.itemsize for v in _state_vectors(state)):
+            return x0.copy()
+        return x0
+    if np.ndim(x0) == 0:
+        return x0.item() if isinstance(x0, np.ndarray) else x0
+    a = np.asarray(x0).reshape(-1)   # (an N x 1 or 1 x N array is taken as the vector it holds)
+    if a.size != N or (a.dtype.kind == "c" and b.dtype.kind != "c"):
+        raise ValueError(f"DimensionMismatch: x0 has shape {a.shape} ({a.dtype}), the solution length {N} ({b.dtype})")
+    return DeviceVector.from_host(np.ascontiguousarray(a, dtype=b.dtype), b.ctx)
+
+
+def _set_start(x, start):
+    """x .= x0 for what _start_vector returned"""
+    if isinstance(start, DeviceVector):
+        x.copy_from(start)
+    else:
+        x.fill_(start)
+
+
 class FISTAState(AbstractSolverState):
     """src/FISTA.jl:15-27"""
 
@@ -630,6 +669,7 @@ class FISTA(AbstractProximalGradientSolver):
             x0n = b if self.A is None else self.A.mul_adj_(b.similar(N), b)
             self.reg = normalize(self.normalizeReg, self.reg, self.A, x0n, in_solver=True)
         fused = self._fused_kinds()
+        start = _start_vector(x0, b, N, state)   # (before the plan's init resets the buffers it may lie in)
         fresh = state._bufs is None or state._bufs[0].ctx is not b.ctx or state._bufs[0].dtype != b.dtype
         if fresh:
             state._bufs = [b.similar(N), b.similar(N)]
@@ -680,15 +720,9 @@ class FISTA(AbstractProximalGradientSolver):
                     check(h, lib.rls_fista_set_reg(state._plan, kind, lam_, slices, pk), "rls_fista_set_reg")
                 check(h, lib.rls_fista_init(state._plan, b.ptr, state.rho, float(theta), state.relTol, self.iterations,
                                             1 if self.restart == "gradient" else 0), "rls_fista_init")
-            if not (np.ndim(x0) == 0 and not isinstance(x0, DeviceVector) and x0 == 0):
-                if isinstance(x0, DeviceVector):
-                    xs = x0
-                elif np.ndim(x0) == 0:   # `state.x .= x0` broadcasts a scalar (src/FISTA.jl:120)
-                    xs = DeviceVector.from_host(np.full(N, x0, dtype=b.dtype), b.ctx)
-                else:
-                    xs = DeviceVector.from_host(np.ascontiguousarray(np.asarray(x0, dtype=b.dtype).reshape(-1)), b.ctx)
-                if xs.n != N or xs.dtype != b.dtype:
-                    raise ValueError(f"DimensionMismatch: x0 has length {xs.n} ({xs.dtype}), the solution {N} ({b.dtype})")
+            if isinstance(start, DeviceVector) or start != 0:
+                # (`state.x .= x0` broadcasts a scalar, src/FISTA.jl:120)
+                xs = start if isinstance(start, DeviceVector) else DeviceVector.from_host(np.full(N, start, dtype=b.dtype), b.ctx)
                 if dbl:
                     check(h, lib.rls_fista_set_start_d(state._plan, xs.ptr, xs.n), "rls_fista_set_start_d")
                 else:
@@ -700,10 +734,7 @@ class FISTA(AbstractProximalGradientSolver):
             else:
                 self.A.mul_adj_(state.x0, b)
             state.norm_x0 = state.x0.norm()
-            if np.isscalar(x0):
-                state.x.fill_(x0)
-            else:
-                state.x.copy_from(x0 if isinstance(x0, DeviceVector) else DeviceVector.from_host(np.asarray(x0, dtype=b.dtype), b.ctx))
+            _set_start(state.x, start)
             state.xold.fill_(0)
             state.res.fill_(math.inf)
             state.rel_res_norm = math.inf
@@ -887,6 +918,7 @@ class ADMM(AbstractPrimalDualSolver):
         """src/ADMM.jl:166-220"""
         N = self._op.N
         lib, h = b.ctx.lib, b.ctx.handle
+        start = _start_vector(x0, b, N, state)
         self.reg = normalize(self.normalizeReg, self.reg, self.A, b, in_solver=True)  # :219
         if state.x is None or state.x.ctx is not b.ctx or state.x.dtype != b.dtype:
             state.x, state.xold, state.beta, state.beta_y = (b.similar(N) for _ in range(4))
@@ -912,10 +944,7 @@ class ADMM(AbstractPrimalDualSolver):
             if state._zbufs is None:
                 state._zbufs = (state.z[0], state.zold[0])
             state.z[0], state.zold[0] = state._zbufs  # the device plan starts every solve with z in the first buffer
-        if np.isscalar(x0):
-            state.x.fill_(x0)
-        else:
-            state.x.copy_from(x0 if isinstance(x0, DeviceVector) else DeviceVector.from_host(np.asarray(x0, dtype=b.dtype), b.ctx))
+        _set_start(state.x, start)
         if self.A is None:
             state.beta_y.copy_from(b)
         else:
@@ -1306,6 +1335,7 @@ class OptISTA(AbstractProximalGradientSolver):
 
     def init_(self, st, b: DeviceVector, x0=0, theta=1):
         f32 = _rt_of(self._op)
+        start = _start_vector(x0, b, self._op.N, st)
         st._alloc(b, self._op.N)
         if self.A is None:
             st.x0.copy_from(b)
@@ -1313,10 +1343,7 @@ class OptISTA(AbstractProximalGradientSolver):
             self.A.mul_adj_(st.x0, b)
         st.norm_x0 = st.x0.norm()
         self.reg = normalize(self.normalizeReg, self.reg, self.A, st.x0, in_solver=True)  # src/OptISTA.jl:154
-        if np.isscalar(x0):
-            st.x.fill_(x0)
-        else:
-            st.x.copy_from(x0 if isinstance(x0, DeviceVector) else DeviceVector.from_host(np.asarray(x0, dtype=b.dtype), b.ctx))
+        _set_start(st.x, start)
         for v in (st.y, st.z, st.zold):
             v.copy_from(st.x)
         st.res.fill_(math.inf)
@@ -1561,6 +1588,7 @@ class POGM(AbstractProximalGradientSolver):
         return n
 
     def init_(self, st, b: DeviceVector, x0=0, theta=1):
+        start = _start_vector(x0, b, self._op.N, st)
         st._alloc(b, self._op.N)
         if self.A is None:
             st.x0.copy_from(b)
@@ -1568,10 +1596,7 @@ class POGM(AbstractProximalGradientSolver):
             self.A.mul_adj_(st.x0, b)
         st.norm_x0 = st.x0.norm()
         self.reg = normalize(self.normalizeReg, self.reg, self.A, st.x0, in_solver=True)  # src/POGM.jl:163
-        if np.isscalar(x0):
-            st.x.fill_(x0)
-        else:
-            st.x.copy_from(x0 if isinstance(x0, DeviceVector) else DeviceVector.from_host(np.asarray(x0, dtype=b.dtype), b.ctx))
+        _set_start(st.x, start)
         for v in (st.xold, st.y, st.z, st.w):
             v.fill_(0)
         st.res.fill_(math.inf)
@@ -2037,6 +2062,7 @@ class Kaczmarz(AbstractRowActionSolver):
     def init_(self, st: KaczmarzState, b, x0=0):
         """init!(solver, state, b; x0 = 0)   src/Kaczmarz.jl:178-217"""
         A = self.A_in
+        start = _start_vector(x0, b, A.N)   # (no alias check: st.x is allocated afresh below, a start never lies inside it)
         lam_prev = self._lam_used
         if self._lam_vec is None:
             self.L2 = normalize(self.normalizeReg, self.L2, A, b if isinstance(b, DeviceVector) else None, in_solver=True)
@@ -2065,15 +2091,12 @@ class Kaczmarz(AbstractRowActionSolver):
             else:
                 for j, uj in enumerate(st._views(st.u)):
                     uj.copy_from(b.column_view(j))
-        if st.matrix and np.isscalar(x0) and st.x.lda == st.x.M and st.vl.lda == st.vl.M:
-            for Mx, val in ((st.x, x0), (st.vl, 0)):
+        if st.matrix and not isinstance(start, DeviceVector) and st.x.lda == st.x.M and st.vl.lda == st.vl.M:
+            for Mx, val in ((st.x, start), (st.vl, 0)):
                 DeviceVector(Mx.M * Mx.N, Mx.dtype, Mx.ctx, _buf=Mx._buf, _offset=Mx.ptr - Mx._buf.ptr).fill_(val)
         else:
             for col in (st._views(st.x) if st.matrix else [st.x]):
-                if np.isscalar(x0):
-                    col.fill_(x0)
-                else:
-                    col.copy_from(x0 if isinstance(x0, DeviceVector) else DeviceVector.from_host(np.asarray(x0, dtype=b.dtype), b.ctx))
+                _set_start(col, start)
             for col in (st._views(st.vl) if st.matrix else [st.vl]):
                 col.fill_(0)
         if not self.randomized:

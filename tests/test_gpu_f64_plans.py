@@ -18,6 +18,8 @@ pytestmark = pytest.mark.gpu
 DT = [np.float64, np.complex128]
 PRIMS = ("rls_nrm2_d", "rls_dotc_d", "rls_asum_d", "rls_gemv_d", "rls_axpy_d")
 SCALAR_TOL = 1e-10   # alpha, beta, zeta, residual, theta, rel_res_norm: the bar test_gpu_float64.py holds alphal to
+ITER_TOL = 1e-12     # iterates against the float64 oracle ...
+GRAM_TOL = 1e-11     # ... and in Gram mode (the bars of test_gpu_float64.py; test_gpu_warm_start.py imports the three)
 
 
 def rel(a, b):
@@ -137,7 +139,7 @@ def test_parity_of_iterates_and_status_scalars(rls, ctx, dt, shape):
     """iterates at iterations 1, 5, 10 and at the end, and alpha / beta / zeta / residual / theta / rel_res_norm there"""
     _, M, N, pad, gram_only = shape
     A, b, rho, lam1 = problem(dt, M, N, 21)
-    tol = 1e-11 if gram_only else 1e-12
+    tol = GRAM_TOL if gram_only else ITER_TOL
     if gram_only:
         G = np.asfortranarray(A.conj().T @ A)
         rhs = A.conj().T @ b

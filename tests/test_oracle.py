@@ -583,3 +583,37 @@ def test_preconditioned_cg_iterates_equal_an_independent_pcg():
     O.cg_inplace(xu, lambda v: Aop @ v, b, maxiter=25, reltol=0.0)
     xt = np.linalg.solve(Aop, b)
     assert rel(xp, xt) < 0.2 * rel(xu, xt)
+
+
+# ---- warm starts: a certificate of the oracle's x0 semantics that restates nothing ------------------
+@pytest.mark.parametrize("name", ["FISTA", "OptISTA", "POGM", "ADMM"])
+def test_start_at_the_least_squares_solution_stays_there(name):
+    """init!(solver, b; x0 = x*) with lambda = 0 and x* = lstsq(A, b) of a full-rank tall A: the gradient A^H (A x* - b) vanishes, so
+    every iterate is x* again (tests/test_gpu_warm_start.py holds the device to this oracle).  The bound comes from the
+    reference solution itself -- each iteration moves x by at most rho ||A^H (A x* - b)||, and 10 x covers the summation orders."""
+    rng = np.random.default_rng(77)
+    M, N = 96, 40
+    A = rng.standard_normal((M, N)) + 1j * rng.standard_normal((M, N))
+    b = A @ (rng.standard_normal(N) + 1j * rng.standard_normal(N)) + 0.3 * (rng.standard_normal(M) + 1j * rng.standard_normal(M))
+    xs = np.linalg.lstsq(A, b, rcond=None)[0]
+    grad = np.linalg.norm(A.conj().T @ (A @ xs - b))
+    if name == "ADMM":
+        rho, its = 0.3, 10
+        S = O.ADMM(A, reg=O.L1Regularization(0.0), rho=rho, iterations=its, iterationsCG=10, absTol=0.0, relTol=0.0)
+        kw = {}
+    else:
+        rho, its = 0.9 / np.linalg.norm(A, 2) ** 2, 25
+        S = getattr(O, name)(A, reg=O.L1Regularization(0.0), rho=rho, iterations=its, relTol=0.0)
+        kw = {"theta": 1}
+    bound = 10 * its * rho * grad / np.linalg.norm(xs)
+    S.init(b, x0=xs, **kw)
+    drift, n = 0.0, 0
+    while S.iterate() is not None:
+        n += 1
+        drift = max(drift, rel(S.solution(), xs))
+    assert n == its
+    assert drift <= bound, f"{name}: drift {drift:.3e} from x* over {its} iterations, bound {bound:.3e}"
+    # and the start matters: from x0 = 0 the same iterations are nowhere near x* on this scale
+    S.init(b, **kw)
+    S.iterate()
+    assert rel(S.solution(), xs) > 1e6 * max(bound, 1e-300), f"{name}: drift {drift:.3e}, bound {bound:.3e}"
