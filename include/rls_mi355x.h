@@ -74,7 +74,7 @@ int32_t rls_device_count(int32_t* out);
  * plan is created): "slab_g", "slab_wv", "slab_order", "red_threads", "resident_barrier", "tv_fused_max_n",
  * "tv_fused_2d", "skinny_t_waves", "skinny_t_u", "skinny_v_waves", "skinny_v_u", "skinny_v_splits", "skinny_half"
  * (the (8 re | 8 im) operand layout for <= 8 complex right-hand sides), "skinny_t_roll", "skinny_v_roll", "skinny_g_roll" (rolling-window
- * depth of the batched kernels' load pipelines), "gram_lds_kib", "kaczmarz_nt".  Per context again: "small" (1: systems that
+ * depth of the batched kernels' load pipelines), "gram_lds_kib", "kaczmarz_nt", "kaczmarz_fused" (rls_kaczmarz_solve).  Per context again: "small" (1: systems that
  * fit one CU's registers run a step call as a single-workgroup launch), "resident_server" (1: rls_cgnr_step_status / rls_fista_step_status leave the resident kernel listening for the
  * next call, see there), "resident_server_idle_us", "status_mailbox" (>= 1: status read-backs through a kernel
  * that stores into pinned host memory + a host spin; 2, the default: rls_*_step_status has the call's last kernel do that store where
@@ -89,6 +89,9 @@ int32_t rls_device_count(int32_t* out);
  * next one streaming in under the products of the current one; 0: one workgroup per block, in rounds -- the partial sums are
  * added in a different order, so results differ in the last bits between the two settings, each being reproducible). */
 int32_t rls_tune_set(rls_ctx* ctx, const char* key, int32_t value);
+/* the current value of a switch that a solver binding has to act on itself: "kaczmarz_fused" (1: regularised / randomised
+ * Kaczmarz solves go through rls_kaczmarz_solve, 0: the binding runs its host loop).  Other keys: RLS_E_INVALID. */
+int32_t rls_tune_get(rls_ctx* ctx, const char* key, int32_t* value);
 /* Device memory is STREAM-ORDERED on the context's stream (a private hipMemPool per device; RLS_ALLOC=sync or a device without
  * memory pools: hipMalloc / hipFree): rls_free does not wait for the stream, the block is reused behind everything enqueued on
  * this context so far.  Memory that ANOTHER context's stream (or another library's) still uses must be synchronised by the
@@ -167,6 +170,12 @@ int32_t rls_scale_rows_d(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, cons
 int32_t rls_kaczmarz_sweep_d(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* At, int64_t ldat, int32_t nrhs, void* X,
                              int64_t ldx, const void* U, int64_t ldu, void* VL, int64_t ldvl, const int32_t* rows_d, const double* denom_d,
                              int32_t nused, double eps_w, int32_t n_sweeps);
+/* rls_kaczmarz_solve in double precision (double denominators, eps_w, reg_lambda).  This sweep keeps x in memory and fetches nothing
+ * ahead: no vl hazard, always one launch, nothing for the caller to split. */
+int32_t rls_kaczmarz_solve_d(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* At, int64_t ldat, int32_t nrhs, void* X,
+                             int64_t ldx, const void* U, int64_t ldu, void* VL, int64_t ldvl, const int32_t* rows_d, const double* denom_d,
+                             int32_t nused, int32_t order_stride, double eps_w, int32_t n_sweeps, int32_t proj_kind, int32_t reg_kind,
+                             double reg_lambda);
 
 int32_t rls_prox_l1(rls_ctx* ctx, int32_t dtype, int64_t n, void* x, float lambda);        /* src/proximalMaps/ProxL1.jl:18-22 */
 int32_t rls_prox_l2(rls_ctx* ctx, int32_t dtype, int64_t n, void* x, float lambda);        /* src/proximalMaps/ProxL2.jl:18-21 */
@@ -342,6 +351,35 @@ int32_t rls_transpose(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const v
 int32_t rls_kaczmarz_sweep(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* At, int64_t ldat,
                            int32_t nrhs, void* X, int64_t ldx, const void* U, int64_t ldu, void* VL, int64_t ldvl,
                            const int32_t* rows_d, const float* denom_d, int32_t nused, float eps_w, int32_t n_sweeps);
+/* A whole Kaczmarz solve in one call: rls_kaczmarz_sweep (which is this entry with order_stride = 0 and no maps) plus
+ *   - per-sweep row orders: order_stride == 0: every sweep walks rows_d[0 .. nused), denom_d[0 .. nused);
+ *     order_stride == nused: sweep s walks rows_d[s nused ..], denom_d[s nused ..] -- one table of nused * n_sweeps
+ *     entries for the samples of `randomized` (src/Kaczmarz.jl:286-288);
+ *   - the elementwise regularisers behind the last row step of EVERY sweep, on the registers that hold x: first the
+ *     projection (proj_kind: RLS_PROJ_NONE / REAL / POSITIVE), then the prox (reg_kind: RLS_REG_NONE / L1 / L2 with
+ *     lambda = reg_lambda) -- the order in which the reference applies its projection sinks and the one remaining
+ *     regulariser (src/Kaczmarz.jl:98-106, :275-277; FISTA has prox first).
+ * RLS_E_INVALID (X untouched): order_stride not in {0, nused}, another kind, reg_lambda < 0 (or NaN), more than 2^31 - 1
+ * table entries, and whatever rls_kaczmarz_sweep rejects.
+ * The vl hazard.  The sweep fetches u[row], vl[row] and the row of A up to 4 row steps ahead, and vl is the one array
+ * it also writes.  A row that is processed again within 4 steps of its last update would be given the vl from before
+ * that update.  Inside a sweep the rows are distinct.  Across sweeps:
+ *   - nused <= 16: every sweep is a launch of its own (the entry does that, for either order_stride);
+ *   - order_stride == 0, nused > 16: a row comes back after nused steps: one launch;
+ *   - order_stride == nused, nused > 16: one launch for the call, so THE CALLER splits its calls: where a row in the
+ *     last 4 positions of sweep s comes back in the first 4 positions of sweep s + 1 at a distance of at most 4 steps,
+ *     sweeps .. s and sweeps s + 1 .. go into different calls (rows_d / denom_d advanced by nused per sweep).  The
+ *     host built the table, so it knows; the Python solver does this in Kaczmarz._run.
+ *     (The rule is one step wider than the kernel needs: the stale read happens at a distance below the pipeline depth; at
+ *     exactly 4 steps thread 0 reads vl[row] behind its own store to it, which is in order.  The margin is deliberate.)
+ * The maps run at the end of every sweep whatever the split, a launch of exactly one sweep included.
+ * rls_tune_set(ctx, "kaczmarz_fused", 0): maps and per-sweep orders are RLS_E_UNSUPPORTED here, and the Python and Julia solvers,
+ * which read the switch with rls_tune_get, go back to one launch per sweep and per prox (the path before this entry existed; for
+ * A/B measurements and as an escape hatch). */
+int32_t rls_kaczmarz_solve(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* At, int64_t ldat,
+                           int32_t nrhs, void* X, int64_t ldx, const void* U, int64_t ldu, void* VL, int64_t ldvl,
+                           const int32_t* rows_d, const float* denom_d, int32_t nused, int32_t order_stride, float eps_w,
+                           int32_t n_sweeps, int32_t proj_kind, int32_t reg_kind, float reg_lambda);
 /* squared row norms of A, out_d[m] = rownorm²(A, m) (src/Utils.jl:20-23) for all rows at once -- the
  * mapreduce(abs2, +, A, dims = 2) of ext/RegularizedLeastSquaresGPUArraysExt/NormalizedRegularization.jl:1-5
  * that normalize(::SystemMatrixBasedNormalization, A, b) (src/Regularization/NormalizedRegularization.jl:47-58)

@@ -835,6 +835,24 @@ function kaczmarz_aux_for(solver::Kaczmarz, state::KaczmarzState{T,<:RLSVector})
   end
 end
 
+"(proj_kind, reg_kind, λ) when every term of `solver.reg` is a map rls_kaczmarz_solve applies at the end of the sweep (plain Real / Positive
+projections first -- Positive wins --, then at most one plain L1 / L2 term with a scalar λ >= 0), else nothing: the prox! loop stays"
+function kaczmarz_fused(regs)
+  pk, rk, lam = RLS_PROJ_NONE, RLS_REG_NONE, 0.0
+  for r in regs
+    if rk == RLS_REG_NONE && r isa PositiveRegularization
+      pk = RLS_PROJ_POSITIVE
+    elseif rk == RLS_REG_NONE && r isa RealRegularization
+      pk = max(pk, RLS_PROJ_REAL)
+    elseif rk == RLS_REG_NONE && (r isa L1Regularization || r isa L2Regularization) && λ(r) isa Real && λ(r) >= 0
+      rk, lam = (r isa L1Regularization ? RLS_REG_L1 : RLS_REG_L2), Float64(λ(r))
+    else
+      return nothing
+    end
+  end
+  return pk, rk, lam
+end
+
 function iterate(solver::Kaczmarz, state::KaczmarzState{T,<:RLSVector}) where {T}
   done(solver, state) && return nothing
   aux = kaczmarz_aux_for(solver, state)
@@ -850,21 +868,28 @@ function iterate(solver::Kaczmarz, state::KaczmarzState{T,<:RLSVector}) where {T
   end
   A = solver.A::RLSMatrix{T}
   M, N = size(A)
-  if T <: RLSDouble
-    check(A.ctx, ccall((:rls_kaczmarz_sweep_d, librls[]), Int32,
-                       (Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64,
-                        Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float64, Int32),
-                       A.ctx.handle, dtypecode(T), M, N, aux.At.ptr, N, 1, state.x.ptr, N, state.u.ptr, M, state.vl.ptr, M,
-                       aux.rows[].ptr, aux.den[].ptr, length(state.usedIndices), Float64(real(state.ɛw)), 1), "rls_kaczmarz_sweep_d")
+  fus = kaczmarz_fused(solver.reg)   # projection, then prox, inside the launch (src/Kaczmarz.jl:275-277); nothing: the loop below
+  sweep(pk, rk, lam) = if T <: RLSDouble
+    ccall((:rls_kaczmarz_solve_d, librls[]), Int32,
+          (Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64,
+           Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Float64, Int32, Int32, Int32, Float64),
+          A.ctx.handle, dtypecode(T), M, N, aux.At.ptr, N, 1, state.x.ptr, N, state.u.ptr, M, state.vl.ptr, M,
+          aux.rows[].ptr, aux.den[].ptr, length(state.usedIndices), 0, Float64(real(state.ɛw)), 1, pk, rk, Float64(lam))
   else
-    check(A.ctx, ccall((:rls_kaczmarz_sweep, librls[]), Int32,
-                       (Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64,
-                        Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float32, Int32),
-                       A.ctx.handle, dtypecode(T), M, N, aux.At.ptr, N, 1, state.x.ptr, N, state.u.ptr, M, state.vl.ptr, M,
-                       aux.rows[].ptr, aux.den[].ptr, length(state.usedIndices), Float32(real(state.ɛw)), 1), "rls_kaczmarz_sweep")
+    ccall((:rls_kaczmarz_solve, librls[]), Int32,
+          (Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64,
+           Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Float32, Int32, Int32, Int32, Float32),
+          A.ctx.handle, dtypecode(T), M, N, aux.At.ptr, N, 1, state.x.ptr, N, state.u.ptr, M, state.vl.ptr, M,
+          aux.rows[].ptr, aux.den[].ptr, length(state.usedIndices), 0, Float32(real(state.ɛw)), 1, pk, rk, Float32(lam))
   end
-  for r in solver.reg
-    prox!(r, state.x)
+  on = Ref{Int32}(1)   # rls_tune_set "kaczmarz_fused" = 0: the plain sweep, then the prox! loop
+  check(A.ctx, ccall((:rls_tune_get, librls[]), Int32, (Ptr{Cvoid}, Cstring, Ref{Int32}), A.ctx.handle, "kaczmarz_fused", on), "rls_tune_get")
+  on[] == 0 && (fus = nothing)
+  check(A.ctx, fus === nothing ? sweep(RLS_PROJ_NONE, RLS_REG_NONE, 0.0) : sweep(fus...), "rls_kaczmarz_solve")
+  if fus === nothing
+    for r in solver.reg
+      prox!(r, state.x)
+    end
   end
   state.iteration += 1
   return state.x, state

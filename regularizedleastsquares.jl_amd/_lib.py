@@ -89,6 +89,7 @@ PROTOTYPES = {
     "rls_last_error_string": (C.c_char_p, [_vp]),
     "rls_device_count": (_i32, [_pi32]),
     "rls_tune_set": (_i32, [_vp, C.c_char_p, _i32]),
+    "rls_tune_get": (_i32, [_vp, C.c_char_p, C.POINTER(_i32)]),
     "rls_malloc": (_i32, [_vp, _sz, _pvp]),
     "rls_free": (_i32, [_vp, _vp]),
     "rls_memcpy_h2d": (_i32, [_vp, _vp, _vp, _sz]),
@@ -126,6 +127,8 @@ PROTOTYPES = {
     "rls_rownorm2_d": (_i32, [_vp, _i32, _i64, _i64, _vp, _i64, _vp]),
     "rls_scale_rows_d": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _i64, _vp, _i64]),
     "rls_kaczmarz_sweep_d": (_i32, [_vp, _i32, _i64, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _d, _i32]),
+    "rls_kaczmarz_solve_d": (_i32, [_vp, _i32, _i64, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _d, _i32,
+                                    _i32, _i32, _d]),
     "rls_prox_l1": (_i32, [_vp, _i32, _i64, _vp, _f]),
     "rls_prox_l2": (_i32, [_vp, _i32, _i64, _vp, _f]),
     "rls_prox_l21": (_i32, [_vp, _i32, _i64, _i64, _vp, _f]),
@@ -171,6 +174,8 @@ PROTOTYPES = {
     "rls_transpose": (_i32, [_vp, _i32, _i64, _i64, _vp, _i64, _vp, _i64]),
     "rls_kaczmarz_sweep": (_i32, [_vp, _i32, _i64, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32,
                                   C.c_float, _i32]),
+    "rls_kaczmarz_solve": (_i32, [_vp, _i32, _i64, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32,
+                                  C.c_float, _i32, _i32, _i32, C.c_float]),
     "rls_rownorm2": (_i32, [_vp, _i32, _i64, _i64, _vp, _i64, _vp]),
     "rls_scale_rows": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _i64, _vp, _i64]),
     "rls_cgnr_create": (_i32, [_vp, _vp, _vp, _vp, _vp, _pvp]),

@@ -59,6 +59,12 @@ class Context:
         for k, v in kw.items():
             check(self.handle, self.lib.rls_tune_set(self.handle, k.encode(), int(v)), f"rls_tune_set({k})")
 
+    def tuned(self, key: str) -> int:
+        """the context's value of a switch the host side acts on (rls_tune_get)"""
+        v = C.c_int32()
+        check(self.handle, self.lib.rls_tune_get(self.handle, key.encode(), C.byref(v)), f"rls_tune_get({key})")
+        return v.value
+
     @property
     def stream(self) -> int:
         return self.lib.rls_ctx_stream(self.handle) or 0

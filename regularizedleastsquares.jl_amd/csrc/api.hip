@@ -305,6 +305,7 @@ int32_t rls_tune_set(rls_ctx* ctx, const char* key, int32_t value) {
   else if (!strcmp(key, "skinny_v_waves")) ctx->tune.skinny_v_waves = value;
   else if (!strcmp(key, "skinny_v_splits")) ctx->tune.skinny_v_splits = value;
   else if (!strcmp(key, "kaczmarz_nt")) ctx->tune.kaczmarz_nt = value;
+  else if (!strcmp(key, "kaczmarz_fused")) ctx->tune.kaczmarz_fused = value ? 1 : 0;
   else if (!strcmp(key, "skinny_t_u")) ctx->tune.skinny_t_u = value;
   else if (!strcmp(key, "skinny_v_u")) ctx->tune.skinny_v_u = value;
   else if (!strcmp(key, "skinny_half")) ctx->tune.skinny_half = value;
@@ -324,6 +325,14 @@ int32_t rls_tune_set(rls_ctx* ctx, const char* key, int32_t value) {
   else if (!strcmp(key, "slab_multi")) ctx->tune.slab_multi = value ? 1 : 0;
   else if (!strcmp(key, "resident_barrier")) ctx->tune.resident_barrier = value == 1 ? 1 : 2;
   else return rls_fail(ctx, RLS_E_INVALID, "tune_set: unknown key");
+  return 0;
+}
+
+int32_t rls_tune_get(rls_ctx* ctx, const char* key, int32_t* value) {
+  RLS_CHECK_CTX(ctx);
+  if (!key || !value) return rls_fail(ctx, RLS_E_INVALID, "tune_get: null argument");
+  if (!strcmp(key, "kaczmarz_fused")) *value = ctx->tune.kaczmarz_fused;
+  else return rls_fail(ctx, RLS_E_INVALID, "tune_get: not a key a binding reads");
   return 0;
 }
 

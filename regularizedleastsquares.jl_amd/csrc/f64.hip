@@ -266,11 +266,15 @@ __global__ void d_tv_dual_kernel(D* rs_pq, const D* xtmp, const D* pq_old, D* rs
 
 // ---- Kaczmarz in double precision (src/Kaczmarz.jl:283-308): one workgroup per right-hand side walks the rows in order; every thread
 // owns the x entries tid, tid + 1024, ... (read and written by it alone), the rows come from transpose(A) (contiguous), and the only
-// synchronisation of a row step is one workgroup barrier for tau = dot_with_matrix_row (src/Utils.jl:55-88, no conjugation)
+// synchronisation of a row step is one workgroup barrier for tau = dot_with_matrix_row (src/Utils.jl:55-88, no conjugation).
+// order_stride == nused: sweep s walks rows[s nused ..], den[s nused ..] (0: every sweep the same nused entries).  Behind the last row
+// step of every sweep each thread applies the projection, then the prox (src/Kaczmarz.jl:275-277) to the entries of x it owns.  Nothing
+// is fetched ahead here, so a row may recur at any distance.
 template <typename D>
 __global__ __launch_bounds__(1024) void d_kaczmarz_kernel(const D* __restrict__ At, int64_t ldat, D* X, int64_t ldx, const D* __restrict__ U,
                                                           int64_t ldu, D* VL, int64_t ldvl, const int32_t* __restrict__ rows,
-                                                          const double* __restrict__ den, int nused, int n_sweeps, double eps_w, int64_t N) {
+                                                          const double* __restrict__ den, int nused, int n_sweeps, int order_stride, double eps_w,
+                                                          int proj_kind, int reg_kind, double thr, int64_t N) {
   __shared__ double red[2][16][2];
   __shared__ double scal[2][4];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -278,7 +282,7 @@ __global__ __launch_bounds__(1024) void d_kaczmarz_kernel(const D* __restrict__ 
   const D* u = U + (int64_t)blockIdx.x * ldu;
   D* vl = VL + (int64_t)blockIdx.x * ldvl;
   int64_t j = 0;
-  for (int sw = 0; sw < n_sweeps; ++sw) {
+  for (int sw = 0; sw < n_sweeps; ++sw, rows += order_stride, den += order_stride) {
     for (int k = 0; k < nused; ++k, ++j) {
       const int row = rows[k];
       const D* ar = At + (int64_t)row * ldat;
@@ -317,6 +321,8 @@ __global__ __launch_bounds__(1024) void d_kaczmarz_kernel(const D* __restrict__ 
       for (int64_t i = tid; i < N; i += 1024) x[i] = del<D>::add(x[i], del<D>::mulc(ar[i], alpha));  // x += alpha conj(A[row, :])   :306
       if (tid == 0) vl[row] = del<D>::make(scal[par][2] + are * eps_w, scal[par][3] + aim * eps_w);      // vl[row] += alpha eps_w      :307
     }
+    if (proj_kind | reg_kind)
+      for (int64_t i = tid; i < N; i += 1024) x[i] = dp_prox_elem(dp_proj_elem(x[i], proj_kind), reg_kind, thr);
   }
 }
 
@@ -612,22 +618,36 @@ int32_t rls_scale_rows_d(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, cons
     hipLaunchKernelGGL(d_scale_rows_kernel<double2>, dim3(dgrid(M * N)), dim3(DT), 0, ctx->stream, (const double2*)w, (const double2*)A, lda, (double2*)B, ldb, M, N);
   return d_status(ctx);
 }
-int32_t rls_kaczmarz_sweep_d(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* At, int64_t ldat, int32_t nrhs, void* X,
+int32_t rls_kaczmarz_solve_d(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* At, int64_t ldat, int32_t nrhs, void* X,
                              int64_t ldx, const void* U, int64_t ldu, void* VL, int64_t ldvl, const int32_t* rows_d, const double* denom_d,
-                             int32_t nused, double eps_w, int32_t n_sweeps) {
+                             int32_t nused, int32_t order_stride, double eps_w, int32_t n_sweeps, int32_t proj_kind, int32_t reg_kind,
+                             double reg_lambda) {
   RLS_CHECK_CTX(ctx);
   if (!d_dtype_ok(dtype) || M <= 0 || N <= 0 || !At || !X || !U || !VL || nrhs < 1 || ldat < N || ldx < N || ldu < M || ldvl < M || nused < 0 ||
       n_sweeps < 0 || (nused > 0 && (!rows_d || !denom_d)))
-    return rls_fail(ctx, RLS_E_INVALID, "kaczmarz_sweep_d: bad argument");
+    return rls_fail(ctx, RLS_E_INVALID, "kaczmarz_solve_d: bad argument");
+  if ((order_stride != 0 && order_stride != nused) || proj_kind < RLS_PROJ_NONE || proj_kind > RLS_PROJ_POSITIVE ||
+      (reg_kind != RLS_REG_NONE && reg_kind != RLS_REG_L1 && reg_kind != RLS_REG_L2) || !(reg_lambda >= 0.0))
+    return rls_fail(ctx, RLS_E_INVALID, "kaczmarz_solve_d: bad order_stride, kind or lambda");
+  if (!ctx->tune.kaczmarz_fused && (order_stride != 0 || proj_kind != RLS_PROJ_NONE || reg_kind != RLS_REG_NONE))
+    return rls_fail(ctx, RLS_E_UNSUPPORTED, "kaczmarz_solve_d: switched off (rls_tune_set kaczmarz_fused = 0)");
   if (nused == 0 || n_sweeps == 0) return 0;
   RLS_HIP(ctx, rls_enter(ctx));
   if (dtype == RLS_F64)
     hipLaunchKernelGGL(d_kaczmarz_kernel<double>, dim3((unsigned)nrhs), dim3(1024), 0, ctx->stream, (const double*)At, ldat, (double*)X, ldx,
-                       (const double*)U, ldu, (double*)VL, ldvl, rows_d, denom_d, nused, n_sweeps, eps_w, N);
+                       (const double*)U, ldu, (double*)VL, ldvl, rows_d, denom_d, nused, n_sweeps, order_stride, eps_w, proj_kind, reg_kind,
+                       reg_lambda, N);
   else
     hipLaunchKernelGGL(d_kaczmarz_kernel<double2>, dim3((unsigned)nrhs), dim3(1024), 0, ctx->stream, (const double2*)At, ldat, (double2*)X, ldx,
-                       (const double2*)U, ldu, (double2*)VL, ldvl, rows_d, denom_d, nused, n_sweeps, eps_w, N);
+                       (const double2*)U, ldu, (double2*)VL, ldvl, rows_d, denom_d, nused, n_sweeps, order_stride, eps_w, proj_kind, reg_kind,
+                       reg_lambda, N);
   return d_status(ctx);
+}
+int32_t rls_kaczmarz_sweep_d(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* At, int64_t ldat, int32_t nrhs, void* X,
+                             int64_t ldx, const void* U, int64_t ldu, void* VL, int64_t ldvl, const int32_t* rows_d, const double* denom_d,
+                             int32_t nused, double eps_w, int32_t n_sweeps) {
+  return rls_kaczmarz_solve_d(ctx, dtype, M, N, At, ldat, nrhs, X, ldx, U, ldu, VL, ldvl, rows_d, denom_d, nused, 0, eps_w, n_sweeps,
+                              RLS_PROJ_NONE, RLS_REG_NONE, 0.0);
 }
 
 }  // extern "C"

@@ -29,14 +29,44 @@ struct kz_vec {
   static constexpr int NV = VEC ? elem<E>::vec : 1;
 };
 
-// rows[i], den[i]: the rows of this sweep in processing order (rowindex[usedIndices[i]]) and their
-// 1 / (rownorm² + lambda).  total = nused * n_sweeps row steps.
-template <typename E, bool VEC, int CPT, int NT, int D, bool FULL>
+// end of a sweep: the projection, then the parameterised prox, on the register copy of x -- the reference puts its projection
+// sinks in front of the one remaining regulariser (src/Kaczmarz.jl:98-106, applied :275-277; FISTA has them the other way round).
+// All three maps send 0 to 0, so the lanes beyond N stay zero; the !FULL kernels re-zero them all the same.
+template <typename E, int NV, int CPT, bool FULL>
+__device__ static inline void kz_sweep_end(chunk<E, NV> (&xv)[CPT], const bool (&valid)[CPT], int proj_kind, int reg_kind,
+                                           float thr) {
+  // once per sweep: keep what depends on the threshold (1 / (1 + 2 lambda) in double, ...) out of the registers of the row loop
+  asm volatile("" : "+s"(thr));
+#pragma unroll
+  for (int c = 0; c < CPT; ++c) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+      xv[c].e[i] = fista_prox_elem<E>(fista_proj_elem<E>(xv[c].e[i], proj_kind), reg_kind, thr);
+    if constexpr (!FULL) {
+      if (!valid[c]) xv[c] = zero_chunk<E, NV>();
+    }
+  }
+}
+
+// rows[i], den[i]: the rows in processing order (rowindex[usedIndices[i]]) and their 1 / (rownorm² + lambda).
+// total = nused * n_sweeps row steps.  order_stride == 0: every sweep walks rows[0 .. nused); order_stride == nused: sweep s
+// walks rows[s nused .. (s + 1) nused), one table for the whole launch (`randomized`: a fresh sample per sweep).
+// proj_kind / reg_kind / thr: the elementwise maps applied to x behind the last row step of EVERY sweep (kz_sweep_end).
+//
+// vl hazard: the pipeline reads vl[row] of step j + D right behind step j, and only thread 0 reads and writes vl.  A row that
+// comes back within D steps would get the vl from before its last update.  Inside a sweep the rows are distinct; across a sweep
+// boundary the host guarantees it (rls_kaczmarz_solve: the rule, and who splits the launch).
+// MAPS = false is the plain sweep: no position counter and no boundary branch in the row loop, the code of the sweep before the
+// maps existed.  With the branch in every instantiation 10 plain sweeps at 4096 x 2048 ComplexF32 took 19.07 - 19.28 ms over two
+// runs of 5 against 18.52 ms without it; in another session the kernel with maps ran 1 % behind the plain one
+// (profiles/kaczmarz_solve_branch.txt).  The branch splits the trip into scheduling regions.
+template <typename E, bool VEC, int CPT, int NT, int D, bool FULL, bool MAPS>
 __global__ __launch_bounds__(NT) void kaczmarz_sweep_kernel(const E* __restrict__ At, int64_t ldat, E* __restrict__ X,
                                                             int64_t ldx, const E* __restrict__ U, int64_t ldu,
                                                             E* VL, int64_t ldvl, const int32_t* __restrict__ rows,
                                                             const float* __restrict__ den, int nused, int n_sweeps,
-                                                            float eps_w, int64_t N) {
+                                                            int order_stride, float eps_w, int proj_kind, int reg_kind,
+                                                            float thr, int64_t N) {
   constexpr int NV = kz_vec<E, VEC>::NV;
   constexpr int NW = NT / 64;
   __shared__ float red[2][NW][2];
@@ -65,18 +95,22 @@ __global__ __launch_bounds__(NT) void kaczmarz_sweep_kernel(const E* __restrict_
   E uu[D], vv[D];
   float dd[D];
   int rcur[D], rnext[D], knext[D];
-  int kq = 0;  // position of the next row id to request (step index mod nused)
+  // kq: table position of the next row id to request.  It runs over the whole table (nused entries, or nused * n_sweeps with
+  // per-sweep orders) and wraps only at its end: the requests run 2 D steps ahead of the last row step, and what they fetch
+  // behind it is never used.  pos: position of the current row step inside its sweep (a running counter, no 64-bit modulo).
+  const int tab = order_stride ? nused * n_sweeps : nused;
+  int kq = 0, pos = 0;
 #pragma unroll
   for (int s = 0; s < D; ++s) {
     rcur[s] = rows[kq];
     dd[s] = den[kq];
-    kq = kq + 1 == nused ? 0 : kq + 1;
+    kq = kq + 1 == tab ? 0 : kq + 1;
   }
 #pragma unroll
   for (int s = 0; s < D; ++s) {
     knext[s] = kq;
     rnext[s] = rows[kq];
-    kq = kq + 1 == nused ? 0 : kq + 1;
+    kq = kq + 1 == tab ? 0 : kq + 1;
   }
 #pragma unroll
   for (int s = 0; s < D; ++s) {
@@ -157,6 +191,14 @@ __global__ __launch_bounds__(NT) void kaczmarz_sweep_kernel(const E* __restrict_
       }
       // vl[row] += alpha * eps_w                                                    src/Kaczmarz.jl:307
       if (tid == 0) vl[rcur[s]] = elem<E>::make(scal[par][2] + are * eps_w, scal[par][3] + aim * eps_w);
+      // sweep boundary: a wave-uniform branch with no load inside (the counted waits of the trip survive).  It sits in front
+      // of the refill, where the registers of slot s are free for what the maps need
+      if constexpr (MAPS) {
+        if (++pos == nused) {
+          pos = 0;
+          kz_sweep_end<E, NV, CPT, FULL>(xv, valid, proj_kind, reg_kind, thr);
+        }
+      }
       // refill the slot with row step j + D, request the row id of step j + 2 D
       rcur[s] = rnext[s];
       dd[s] = den[knext[s]];
@@ -167,7 +209,7 @@ __global__ __launch_bounds__(NT) void kaczmarz_sweep_kernel(const E* __restrict_
       vv[s] = vl[rcur[s]];
       knext[s] = kq;
       rnext[s] = rows[kq];
-      kq = kq + 1 == nused ? 0 : kq + 1;
+      kq = kq + 1 == tab ? 0 : kq + 1;
     }
   }
   {
@@ -238,6 +280,12 @@ __global__ __launch_bounds__(NT) void kaczmarz_sweep_kernel(const E* __restrict_
         }
         // vl[row] += alpha * eps_w                                                    src/Kaczmarz.jl:307
         if (tid == 0) vl[rcur[s]] = elem<E>::make(scal[par][2] + are * eps_w, scal[par][3] + aim * eps_w);
+        if constexpr (MAPS) {
+          if (++pos == nused) {
+            pos = 0;
+            kz_sweep_end<E, NV, CPT, FULL>(xv, valid, proj_kind, reg_kind, thr);
+          }
+        }
         // refill the slot with row step j + D, request the row id of step j + 2 D
         rcur[s] = rnext[s];
         dd[s] = den[knext[s]];
@@ -248,7 +296,7 @@ __global__ __launch_bounds__(NT) void kaczmarz_sweep_kernel(const E* __restrict_
         vv[s] = vl[rcur[s]];
         knext[s] = kq;
         rnext[s] = rows[kq];
-        kq = kq + 1 == nused ? 0 : kq + 1;
+        kq = kq + 1 == tab ? 0 : kq + 1;
       }
     }
   }
@@ -289,20 +337,36 @@ static int32_t kz_status(rls_ctx* ctx) {
   return 0;
 }
 
+// the arguments of one launch, as the entry points validated them
+struct kz_args {
+  const int32_t* rows;
+  const float* den;
+  int nused, n_sweeps, order_stride;
+  float eps_w;
+  int proj_kind, reg_kind;
+  float thr;
+};
+
 template <typename E, bool VEC>
 static int32_t kz_launch(rls_ctx* ctx, int64_t N, const E* At, int64_t ldat, int nrhs, E* X, int64_t ldx, const E* U,
-                         int64_t ldu, E* VL, int64_t ldvl, const int32_t* rows, const float* den, int nused, int n_sweeps,
-                         float eps_w) {
+                         int64_t ldu, E* VL, int64_t ldvl, const kz_args& a) {
   constexpr int NV = kz_vec<E, VEC>::NV;
   const int64_t chunks = (N + NV - 1) / NV;
+#define KZ_GO(CPT, NT, DD, FULL, MAPS)                                                                               \
+  hipLaunchKernelGGL((kaczmarz_sweep_kernel<E, VEC, CPT, NT, DD, FULL, MAPS>), dim3((unsigned)nrhs), dim3(NT), 0,    \
+                     ctx->stream, At, ldat, X, ldx, U, ldu, VL, ldvl, a.rows, a.den, a.nused, a.n_sweeps,            \
+                     a.order_stride, a.eps_w, a.proj_kind, a.reg_kind, a.thr, N)
 #define KZ(CPT, NT, DD)                                                                                              \
   do {                                                                                                               \
-    if (chunks == (int64_t)(CPT) * (NT))                                                                             \
-      hipLaunchKernelGGL((kaczmarz_sweep_kernel<E, VEC, CPT, NT, DD, true>), dim3((unsigned)nrhs), dim3(NT), 0,      \
-                         ctx->stream, At, ldat, X, ldx, U, ldu, VL, ldvl, rows, den, nused, n_sweeps, eps_w, N);      \
+    const bool full = chunks == (int64_t)(CPT) * (NT), maps = (a.proj_kind | a.reg_kind) != 0;                       \
+    if (full && maps)                                                                                                \
+      KZ_GO(CPT, NT, DD, true, true);                                                                                \
+    else if (full)                                                                                                   \
+      KZ_GO(CPT, NT, DD, true, false);                                                                               \
+    else if (maps)                                                                                                   \
+      KZ_GO(CPT, NT, DD, false, true);                                                                               \
     else                                                                                                             \
-      hipLaunchKernelGGL((kaczmarz_sweep_kernel<E, VEC, CPT, NT, DD, false>), dim3((unsigned)nrhs), dim3(NT), 0,     \
-                         ctx->stream, At, ldat, X, ldx, U, ldu, VL, ldvl, rows, den, nused, n_sweeps, eps_w, N);      \
+      KZ_GO(CPT, NT, DD, false, false);                                                                              \
   } while (0)
   // measured at 4096 x 2048 ComplexF32 (tools/bench_kaczmarz.py): 512 threads x 2 chunks 0.453 us per row
   // step, 256 x 4 0.499, 1024 x 1 0.616, 256 x 4 with an 8-deep pipeline 0.493
@@ -322,6 +386,7 @@ static int32_t kz_launch(rls_ctx* ctx, int64_t N, const E* At, int64_t ldat, int
     return rls_fail(ctx, RLS_E_UNSUPPORTED, "kaczmarz_sweep: N too large for the register-resident sweep");
   }
 #undef KZ
+#undef KZ_GO
   return kz_status(ctx);
 }
 
@@ -343,36 +408,55 @@ int32_t rls_transpose(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const v
   return kz_status(ctx);
 }
 
-int32_t rls_kaczmarz_sweep(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* At, int64_t ldat,
+int32_t rls_kaczmarz_solve(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* At, int64_t ldat,
                            int32_t nrhs, void* X, int64_t ldx, const void* U, int64_t ldu, void* VL, int64_t ldvl,
-                           const int32_t* rows_d, const float* denom_d, int32_t nused, float eps_w, int32_t n_sweeps) {
+                           const int32_t* rows_d, const float* denom_d, int32_t nused, int32_t order_stride, float eps_w,
+                           int32_t n_sweeps, int32_t proj_kind, int32_t reg_kind, float reg_lambda) {
   RLS_CHECK_CTX(ctx);
   if (!rls_dtype_ok(dtype) || M <= 0 || N <= 0 || !At || !X || !U || !VL || nrhs < 1 || ldat < N || ldx < N ||
       ldu < M || ldvl < M || nused < 0 || n_sweeps < 0 || (nused > 0 && (!rows_d || !denom_d)))
-    return rls_fail(ctx, RLS_E_INVALID, "kaczmarz_sweep: bad argument");
+    return rls_fail(ctx, RLS_E_INVALID, "kaczmarz_solve: bad argument");
+  if ((order_stride != 0 && order_stride != nused) || proj_kind < RLS_PROJ_NONE || proj_kind > RLS_PROJ_POSITIVE ||
+      (reg_kind != RLS_REG_NONE && reg_kind != RLS_REG_L1 && reg_kind != RLS_REG_L2) || !(reg_lambda >= 0.f) ||
+      (order_stride != 0 && (int64_t)nused * n_sweeps > INT32_MAX))
+    return rls_fail(ctx, RLS_E_INVALID, "kaczmarz_solve: bad order_stride, kind or lambda");
+  if (!ctx->tune.kaczmarz_fused && (order_stride != 0 || proj_kind != RLS_PROJ_NONE || reg_kind != RLS_REG_NONE))
+    return rls_fail(ctx, RLS_E_UNSUPPORTED, "kaczmarz_solve: switched off (rls_tune_set kaczmarz_fused = 0)");
   if (nused == 0 || n_sweeps == 0) return 0;
   RLS_HIP(ctx, rls_enter(ctx));
   const int V = dtype == RLS_C32 ? 2 : 4;
   const bool vec = (N % V == 0) && (ldat % V == 0) && (ldx % V == 0) && ((uintptr_t)At % 16 == 0) &&
                    ((uintptr_t)X % 16 == 0);
-  // several sweeps in one launch re-use the row order: the pipeline may prefetch vl[row] of the next
-  // sweep before this sweep's update of the same row unless the sweep is longer than the pipeline
+  // several sweeps in one launch: the pipeline may prefetch vl[row] of the next sweep before this sweep's update of
+  // the same row unless a row comes back only after more steps than the pipeline is deep.  A repeated order
+  // (order_stride == 0) longer than 16 rows is safe; shorter sweeps go one per launch.  With per-sweep orders the
+  // caller splits its calls where a row recurs within 4 steps across a boundary (see the header).
   const int per_launch = nused > 16 ? n_sweeps : 1;
   for (int done = 0; done < n_sweeps; done += per_launch) {
+    const kz_args a{rows_d + (int64_t)done * order_stride, denom_d + (int64_t)done * order_stride, nused, per_launch,
+                    order_stride, eps_w, proj_kind, reg_kind, reg_lambda};
     int32_t st;
     if (dtype == RLS_F32)
       st = vec ? kz_launch<float, true>(ctx, N, (const float*)At, ldat, nrhs, (float*)X, ldx, (const float*)U, ldu,
-                                        (float*)VL, ldvl, rows_d, denom_d, nused, per_launch, eps_w)
+                                        (float*)VL, ldvl, a)
                : kz_launch<float, false>(ctx, N, (const float*)At, ldat, nrhs, (float*)X, ldx, (const float*)U, ldu,
-                                         (float*)VL, ldvl, rows_d, denom_d, nused, per_launch, eps_w);
+                                         (float*)VL, ldvl, a);
     else
       st = vec ? kz_launch<float2, true>(ctx, N, (const float2*)At, ldat, nrhs, (float2*)X, ldx, (const float2*)U, ldu,
-                                         (float2*)VL, ldvl, rows_d, denom_d, nused, per_launch, eps_w)
+                                         (float2*)VL, ldvl, a)
                : kz_launch<float2, false>(ctx, N, (const float2*)At, ldat, nrhs, (float2*)X, ldx, (const float2*)U,
-                                          ldu, (float2*)VL, ldvl, rows_d, denom_d, nused, per_launch, eps_w);
+                                          ldu, (float2*)VL, ldvl, a);
     if (st != 0) return st;
   }
   return 0;
+}
+
+// the unregularised sweep with one repeated order: rls_kaczmarz_solve without the end-of-sweep maps
+int32_t rls_kaczmarz_sweep(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* At, int64_t ldat,
+                           int32_t nrhs, void* X, int64_t ldx, const void* U, int64_t ldu, void* VL, int64_t ldvl,
+                           const int32_t* rows_d, const float* denom_d, int32_t nused, float eps_w, int32_t n_sweeps) {
+  return rls_kaczmarz_solve(ctx, dtype, M, N, At, ldat, nrhs, X, ldx, U, ldu, VL, ldvl, rows_d, denom_d, nused, 0, eps_w,
+                            n_sweeps, RLS_PROJ_NONE, RLS_REG_NONE, 0.f);
 }
 
 }  // extern "C"

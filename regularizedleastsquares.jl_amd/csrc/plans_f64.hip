@@ -348,24 +348,6 @@ __global__ void dp_fista_extrapolate_kernel(D* __restrict__ y, const D* __restri
     y[i] = dl<D>::add(dl<D>::scale(c1, y[i]), dl<D>::scale(c2, xprev[i]));
 }
 
-template <typename D>
-__device__ static inline D dp_prox_elem(D v, int kind, double thr) {  // the formulas of f64.hip (ProxL1.jl:18-22, ProxL2.jl:18-21)
-  if (kind == RLS_REG_L1) {
-    const double eps = 2.220446049250313e-16;
-    const double a = dl<D>::absv(v), sh = fmax(a - thr, 0.0), den = a + eps;
-    return dl<D>::make((sh * (dl<D>::re(v) + eps)) / den, (sh * dl<D>::im(v)) / den);
-  }
-  if (kind == RLS_REG_L2) return dl<D>::scale(1.0 / (1.0 + 2.0 * thr), v);
-  return v;
-}
-template <typename D>
-__device__ static inline D dp_proj_elem(D v, int proj) {
-  if (proj == RLS_PROJ_NONE) return v;
-  double re = dl<D>::re(v);
-  if (proj == RLS_PROJ_POSITIVE && re < 0.0) re = 0.0;
-  return dl<D>::make(re, 0.0);
-}
-
 // src/FISTA.jl:153-185 behind res = AHA y: res -= x0, x = y - rho res, ||res||, prox, projection, gradient restart, theta, done.
 // x holds y on entry and the new iterate on exit.
 template <typename D>

@@ -59,6 +59,8 @@ struct rls_tuning {
   int64_t tv_fused_max_n = 2048;  // tv.hip: larger images run 2 chip-wide launches per FGP iteration instead of one CU
   int tv_fused_2d = 1;         // the register-resident 2-D FGP kernel (n <= 8192 pixels)
   int kaczmarz_nt = 0;         // kaczmarz.hip: workgroup size override (0 = heuristic)
+  int kaczmarz_fused = 1;      // 0: rls_kaczmarz_solve takes neither end-of-sweep maps nor per-sweep orders (RLS_E_UNSUPPORTED); the
+                               // solver bindings then run their host loop (a launch per sweep and per prox): measurement / escape hatch
   int resident_spin = 100000;  // bound of every in-kernel wait, in polls (~1 us each: a wall-clock bound of ~0.1 s per
                                // wait); a launch that runs into it is a no-op and the host re-runs its iterations on the
                                // per-iteration pipeline (solvers.hip, *_recover)
@@ -706,6 +708,44 @@ __device__ static inline E fista_proj_elem(E v, int proj_kind) {
   float re = elem<E>::re(v);
   if (proj_kind == RLS_PROJ_POSITIVE && re < 0.f) re = 0.f;
   return elem<E>::make(re, 0.f);
+}
+
+// the same maps for D = double / double2 (the double-precision FISTA plan of plans_f64.hip and the sweep of f64.hip)
+template <typename D>
+__device__ static inline D dp_make(double re, double im) {
+  if constexpr (sizeof(D) == sizeof(double2)) return make_double2(re, im);
+  else return re;
+}
+template <typename D>
+__device__ static inline D dp_prox_elem(D v, int kind, double thr) {  // ProxL1.jl:18-22, ProxL2.jl:18-21
+  double re, im = 0.0, a;
+  if constexpr (sizeof(D) == sizeof(double2)) {
+    re = v.x;
+    im = v.y;
+    a = hypot(re, im);
+  } else {
+    re = v;
+    a = fabs(re);
+  }
+  if (kind == RLS_REG_L1) {
+    const double eps = 2.220446049250313e-16;
+    const double sh = fmax(a - thr, 0.0), den = a + eps;
+    return dp_make<D>((sh * (re + eps)) / den, (sh * im) / den);
+  }
+  if (kind == RLS_REG_L2) {
+    const double f = 1.0 / (1.0 + 2.0 * thr);
+    return dp_make<D>(f * re, f * im);
+  }
+  return v;
+}
+template <typename D>
+__device__ static inline D dp_proj_elem(D v, int proj) {
+  if (proj == RLS_PROJ_NONE) return v;
+  double re;
+  if constexpr (sizeof(D) == sizeof(double2)) re = v.x;
+  else re = v;
+  if (proj == RLS_PROJ_POSITIVE && re < 0.0) re = 0.0;
+  return dp_make<D>(re, 0.0);
 }
 
 // 16-byte (or element-sized) register chunks of a matrix column

@@ -1950,6 +1950,56 @@ def _i32_device(a, ctx) -> DeviceVector:
     return DeviceVector.from_host(np.ascontiguousarray(a, dtype=np.int32).view(np.float32), ctx)
 
 
+def _kaczmarz_fused_kinds(regs):
+    """(proj_kind, reg_kind, lambda) when every term of a Kaczmarz solver's `reg` -- the projections, then at most one other
+    term, as the constructor orders them (src/Kaczmarz.jl:98-106) -- is an elementwise map that rls_kaczmarz_solve applies to x
+    in registers at the end of a sweep; None for anything else: nested terms (masked, transformed, scaled, plug-and-play), L21,
+    TV, LLR, Nuclear, a vector lambda.  Those keep the host loop of `iterate`.  Plain Real / Positive projections in any mix
+    are one kind: Positive includes Real, and either order gives Positive's result."""
+    pk, rk, lam = PROJ_NONE, REG_NONE, 0.0
+    for r in regs:
+        if type(r) is PositiveRegularization:
+            pk = PROJ_POSITIVE
+        elif type(r) is RealRegularization:
+            pk = max(pk, PROJ_REAL)
+        elif rk == REG_NONE and type(r) is L1Regularization:
+            rk, lam = REG_L1, float(r.lam)
+        elif rk == REG_NONE and type(r) is L2Regularization and getattr(r, "lam_vector", None) is None:
+            rk, lam = REG_L2, float(r.lam)
+        else:
+            return None
+    if not lam >= 0.0:  # (negative or NaN: the entry point would refuse it)
+        return None
+    return pk, rk, lam
+
+
+_KACZMARZ_DEPTH = 4  # the deepest row pipeline kaczmarz.hip instantiates
+
+
+def _kaczmarz_launch_splits(rows, nused, n_sweeps):
+    """[(first sweep, number of sweeps)]: the rls_kaczmarz_solve calls that cover a table of per-sweep row orders
+    (`rows`: n_sweeps * nused row ids, sweep after sweep; None: every sweep walks the same nused distinct rows).  The sweep kernel reads vl[row] up to 4 row steps ahead of the step
+    that uses it, so a row that comes back within 4 steps of its last update would see the vl from before that update
+    (include/rls_mi355x.h, rls_kaczmarz_solve): a boundary across which that happens ends a call, and sweeps of at most 16 rows
+    are a call each."""
+    if n_sweeps <= 0:
+        return []
+    if nused <= 16:
+        return [(s, 1) for s in range(n_sweeps)]
+    if rows is None:
+        return [(0, n_sweeps)]
+    D = _KACZMARZ_DEPTH
+    t = np.asarray(rows).reshape(n_sweeps, nused)
+    cuts = [0]
+    for s in range(1, n_sweeps):
+        tail, head = t[s - 1, nused - D:], t[s, :D]
+        # tail[D - 1 - i] runs i + 1 steps before the boundary, head[k] k steps behind it
+        if any(tail[D - 1 - i] == head[k] for i in range(D) for k in range(D - i)):
+            cuts.append(s)
+    cuts.append(n_sweeps)
+    return [(c0, c1 - c0) for c0, c1 in zip(cuts[:-1], cuts[1:])]
+
+
 class KaczmarzState(AbstractSolverState):
     """src/Kaczmarz.jl:23-32.  nrhs > 1: the columns of a matrix right-hand side advance in ONE launch, one
     workgroup per column (backend scheduler, same per-column results as MultiThreadingState)."""
@@ -1991,7 +2041,13 @@ class Kaczmarz(AbstractRowActionSolver):
     the registers of one workgroup, the rows of A stream through from a transposed copy of A (the
     row-access layout of :391).  `shuffleRows` / `randomized` draw the row order from a NumPy generator
     seeded with `seed` (the reference seeds Julia's global RNG, so the orders differ, not the method);
-    `greedy_randomized` is CPU-only in the reference (test/testKaczmarz.jl:114) and raises here."""
+    `greedy_randomized` is CPU-only in the reference (test/testKaczmarz.jl:114) and raises here.
+
+    Without callbacks a whole solve is one rls_kaczmarz_solve call when every term of `reg` is elementwise (plain Real /
+    Positive, at most one plain L1 / L2: _kaczmarz_fused_kinds): the maps run on the registers that hold x at the end of every
+    sweep -- projection first, then the prox (:275-277) -- and `randomized` walks one table with all its samples
+    (one launch per stretch without a vl hazard, _kaczmarz_launch_splits).  Other regularisers, and
+    ctx.tune(kaczmarz_fused=0), keep a launch per sweep and per prox and column."""
 
     def __init__(self, A=None, *, reg=None, normalizeReg=None, randomized: bool = False, subMatrixFraction=0.15,
                  shuffleRows: bool = False, seed: int = 1234, iterations: int = 10, greedy_randomized: bool = False,
@@ -2104,37 +2160,76 @@ class Kaczmarz(AbstractRowActionSolver):
         st.eps_w = 1.0 if self._lam_vec is not None else float(np.sqrt(self._rt(self._lam_used)))
         st.iteration = 0
 
-    def _sweep(self, st, n_sweeps):
+    def _fused(self):
+        """(proj_kind, reg_kind, lambda) of `reg` for rls_kaczmarz_solve, or None: the host loop (a term the kernel does not
+        apply, or rls_tune_set "kaczmarz_fused" = 0 -- the context owns the switch, whoever set it)"""
+        if not self.A_in.ctx.tuned("kaczmarz_fused"):
+            return None
+        return _kaczmarz_fused_kinds(self.reg)
+
+    def _sweep(self, st, n_sweeps, fus=None, first=0, stride=0):
+        """n_sweeps sweeps in one call.  fus: the end-of-sweep maps; stride = nused: st._rows / st._den hold one order per sweep
+        and this call starts at sweep `first` of them.  Without either it is the plain sweep entry."""
         A, ctx = self.A_in, self.A_in.ctx
         ldx = st.x.lda if st.matrix else A.N
         ldu = st.u.lda if st.matrix else A.M
         ldvl = st.vl.lda if st.matrix else A.M
-        sweep = ctx.lib.rls_kaczmarz_sweep_d if is_double(A.code) else ctx.lib.rls_kaczmarz_sweep
-        check(ctx.handle, sweep(ctx.handle, A.code, A.M, A.N, self.At.ptr, self.At.lda, st.nrhs, st.x.ptr, ldx, st.u.ptr, ldu,
-                                st.vl.ptr, ldvl, st._rows.ptr, st._den.ptr, len(st.usedIndices), float(st.eps_w), int(n_sweeps)),
-              "rls_kaczmarz_sweep")
+        dbl = is_double(A.code)
+        nused = len(st.usedIndices)
+        head = (ctx.handle, A.code, A.M, A.N, self.At.ptr, self.At.lda, st.nrhs, st.x.ptr, ldx, st.u.ptr, ldu, st.vl.ptr, ldvl)
+        if fus in (None, (PROJ_NONE, REG_NONE, 0.0)) and not stride:
+            sweep = ctx.lib.rls_kaczmarz_sweep_d if dbl else ctx.lib.rls_kaczmarz_sweep
+            check(ctx.handle, sweep(*head, st._rows.ptr, st._den.ptr, nused, float(st.eps_w), int(n_sweeps)), "rls_kaczmarz_sweep")
+            return
+        pk, rk, lam = fus or (PROJ_NONE, REG_NONE, 0.0)
+        solve = ctx.lib.rls_kaczmarz_solve_d if dbl else ctx.lib.rls_kaczmarz_solve
+        off = int(first) * int(stride)
+        check(ctx.handle, solve(*head, st._rows.ptr + 4 * off, st._den.ptr + (8 if dbl else 4) * off, nused, int(stride),
+                                float(st.eps_w), int(n_sweeps), pk, rk, lam), "rls_kaczmarz_solve")
+
+    def _draw(self):
+        """sample!(rowIndexCycle, weights(probabilities), usedIndices, replace = false)  :286-288"""
+        p = self.probabilities / self.probabilities.sum()
+        return self._rng.choice(len(self.rowindex), size=self.subMatrixSize, replace=False, p=p)
 
     def iterate(self, st: Optional[KaczmarzState] = None):
         st = st or self.state
         if st.iteration >= self.iterations:  # done (:320)
             return None
-        if self.randomized:  # sample!(rowIndexCycle, weights(probabilities), usedIndices, replace = false)  :286-288
-            p = self.probabilities / self.probabilities.sum()
-            self._upload_order(st, self._rng.choice(len(self.rowindex), size=self.subMatrixSize, replace=False, p=p))
-        self._sweep(st, 1)
-        for r in self.reg:
-            for col in (st._views(st.x) if st.matrix else [st.x]):
-                r.prox_(col) if is_projection(r) else r.prox_(col, r.lam)
+        if self.randomized:
+            self._upload_order(st, self._draw())
+        fus = self._fused()
+        self._sweep(st, 1, fus)
+        if fus is None:
+            for r in self.reg:
+                for col in (st._views(st.x) if st.matrix else [st.x]):
+                    r.prox_(col) if is_projection(r) else r.prox_(col, r.lam)
         st.iteration += 1
         return st.x, st
 
     def _run(self, st):
-        if not self.reg and not self.randomized and st.iteration < self.iterations:
-            self._sweep(st, self.iterations - st.iteration)  # every remaining sweep in one launch
-            st.iteration = self.iterations
+        left = self.iterations - st.iteration
+        fus = self._fused()
+        if left > 0 and not self.randomized and not self.reg:
+            self._sweep(st, left)  # every remaining sweep in one launch
+        elif left > 0 and fus is not None and not self.randomized:
+            # the maps run inside the launch, at the end of every sweep; sweeps of <= 16 rows are a launch each (the vl hazard)
+            for _, n in _kaczmarz_launch_splits(None, len(st.usedIndices), left):
+                self._sweep(st, n, fus)
+        elif left > 0 and fus is not None:
+            # every sample is known before the first sweep: the generator is seeded up front.  The same calls as `iterate` makes,
+            # so iteration k walks the order it would have drawn there; one table, one launch per stretch without a vl hazard
+            orders = np.stack([self._draw() for _ in range(left)])
+            self._upload_order(st, orders.reshape(-1))
+            table = self.rowindex[st.usedIndices]
+            st.usedIndices = orders[-1].astype(np.int64)
+            for first, n in _kaczmarz_launch_splits(table, self.subMatrixSize, left):
+                self._sweep(st, n, fus, first, self.subMatrixSize)
+        else:
+            while self.iterate(st) is not None:
+                pass
             return
-        while self.iterate(st) is not None:
-            pass
+        st.iteration = self.iterations
 
     def _solution(self, st):
         """solversolution(solver::Kaczmarz)  :262-265 (Tikhonov matrix: x .* 1 ./ sqrt.(lambda))"""
