@@ -205,6 +205,11 @@ size_t rls_prox_tv_workspace_bytes(int32_t dtype, int32_t ndims, const int64_t* 
 int32_t rls_prox_tv_fgp(rls_ctx* ctx, int32_t dtype, int32_t ndims, const int64_t* shape, int32_t ntv,
                         const int32_t* dims, void* x, float lambda, int32_t iterations, void* workspace,
                         size_t workspace_bytes);
+/* which kernels rls_prox_tv_fgp (and the TV launch inside the FISTA / ADMM / SplitBregman plans) runs for this geometry under the
+ * context's current "tv_fused_max_n" / "tv_fused_2d": 0 = two chip-wide launches per FGP iteration (captured into a graph),
+ * 1 = the single-workgroup kernel with the image and both duals in LDS, 21 / 22 / 24 / 28 = the register-resident 2-D kernel
+ * with 1 / 2 / 4 / 8 pixels per thread.  Read-only: the launcher's own selector (csrc/tv.hip, fgp_variant).  < 0: RLS_E_*. */
+int32_t rls_tv_variant(rls_ctx* ctx, int32_t dtype, int32_t ndims, const int64_t* shape, int32_t ntv, const int32_t* dims);
 
 /* ---------------------------------------------------------------------------------------------
  * operator handle: the backend's operator type for A (SURVEY 3.1 "two operator modes").

@@ -56,6 +56,14 @@ function proxTV!(reg, x::V{T}, lam::T, shape, dims; iterationsTV = 10, kwargs...
                      x.ctx.handle, dt, length(sh), sh, length(d0), d0, x.ptr, lam, iterationsTV, ws.ptr, need), "rls_prox_tv_fgp")
   x
 end
+"which kernels proxTV! runs for an image of this eltype, shape and (1-based) dims on `ctx` (rls_tv_variant): 0 = two launches per
+FGP iteration, 1 = the single-workgroup LDS kernel, 21 / 22 / 24 / 28 = the register-resident 2-D kernel at 1 / 2 / 4 / 8 pixels per thread"
+function tv_variant(ctx, ::Type{T}, shape, dims = 1:length(shape)) where {T}
+  sh = collect(Int64, shape); d0 = collect(Int32, dims) .- Int32(1)
+  v = ccall((:rls_tv_variant, librls[]), Int32, (Ptr{Cvoid}, Int32, Int32, Ptr{Int64}, Int32, Ptr{Int32}), ctx.handle, dtypecode(T), length(sh), sh, length(d0), d0)
+  v < 0 && check(ctx, v, "rls_tv_variant")
+  Int(v)
+end
 # ---- the same maps on Float64 / ComplexF64 vectors (test/testProxMaps.jl:47,78,106 run them in ComplexF64): double scalars ----------
 function prox!(::L1Regularization, x::V{Float64}, lam::Float64)
   check(x.ctx, ccall((:rls_prox_l1_d, librls[]), Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Cvoid}, Float64), x.ctx.handle, dtypecode(eltype(x)), length(x), x.ptr, lam), "rls_prox_l1_d"); x

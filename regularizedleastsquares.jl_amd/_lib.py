@@ -142,6 +142,7 @@ PROTOTYPES = {
     "rls_tv_lincomb": (_i32, [_vp, _i32, _i64, _vp, _f, _vp, _f, _vp]),
     "rls_prox_tv_workspace_bytes": (_sz, [_i32, _i32, _pi64, _i32, _pi32]),
     "rls_prox_tv_fgp": (_i32, [_vp, _i32, _i32, _pi64, _i32, _pi32, _vp, _f, _i32, _vp, _sz]),
+    "rls_tv_variant": (_i32, [_vp, _i32, _i32, _pi64, _i32, _pi32]),
     "rls_operator_create": (_i32, [_vp, _i32, _i64, _i64, _vp, _i64, _pvp]),
     "rls_operator_set_gram": (_i32, [_vp, _vp, _i64]),
     "rls_operator_destroy": (_i32, [_vp]),

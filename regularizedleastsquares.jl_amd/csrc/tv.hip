@@ -502,6 +502,18 @@ static void fgp2d_launch(rls_ctx* ctx, unsigned nx, unsigned ny, int use0, int u
                      use0, use1, lam, iters, skip, Bt);
 }
 
+// Which code path the FGP loop of an image takes: 0 = multi-launch (fgp_typed), 1 = fgp_fused_kernel, 20 + PPT =
+// fgp2d_kernel<E, PPT> (its geometry in nx, ny, use0, use1).  THE statement of the selection rules: fgp_single_launch
+// dispatches on it, tv_single_ok and rls_tv_variant report it.
+static int fgp_variant(const rls_ctx* ctx, const tv_geom& G, size_t es, unsigned* nx, unsigned* ny, int* use0, int* use1) {
+  if (fgp2d_geom(ctx, G, es, nx, ny, use0, use1)) {
+    const unsigned n = *nx * *ny;
+    return n <= 1024 ? 21 : n <= 2048 ? 22 : n <= 4096 ? 24 : 28;  // (fgp2d_geom: complex images stop at 4 pixels per thread)
+  }
+  const size_t lds = (size_t)(2 * G.goff[G.ntv] + 2 * G.n) * es;
+  return lds <= FGP_LDS_BUDGET && G.n <= ctx->tune.tv_fused_max_n ? 1 : 0;
+}
+
 // single-workgroup FGP (either kernel) when the geometry allows: out = prox_TV(xin [+ add]).  Returns false
 // (nothing launched) otherwise.
 template <typename E>
@@ -509,28 +521,30 @@ static bool fgp_single_launch(rls_ctx* ctx, const tv_geom& G, const E* xin, cons
                               const int* skip, const tv_batch& Bt = tv_batch()) {
   unsigned nx, ny;
   int use0, use1;
-  if (fgp2d_geom(ctx, G, sizeof(E), &nx, &ny, &use0, &use1)) {
-    const unsigned n = nx * ny;
-    if (n <= 1024)
+  switch (fgp_variant(ctx, G, sizeof(E), &nx, &ny, &use0, &use1)) {
+    case 21:
       fgp2d_launch<E, 1>(ctx, nx, ny, use0, use1, xin, add, out, lam, iters, skip, Bt);
-    else if (n <= 2048)
+      return true;
+    case 22:
       fgp2d_launch<E, 2>(ctx, nx, ny, use0, use1, xin, add, out, lam, iters, skip, Bt);
-    else if (n <= 4096)
+      return true;
+    case 24:
       fgp2d_launch<E, 4>(ctx, nx, ny, use0, use1, xin, add, out, lam, iters, skip, Bt);
-    else if constexpr (sizeof(E) == 4)  // (fgp2d_geom: complex images stop at 4 pixels per thread)
-      fgp2d_launch<E, 8>(ctx, nx, ny, use0, use1, xin, add, out, lam, iters, skip, Bt);
-    return true;
+      return true;
+    case 28:
+      if constexpr (sizeof(E) == 4) fgp2d_launch<E, 8>(ctx, nx, ny, use0, use1, xin, add, out, lam, iters, skip, Bt);
+      return true;
+    case 1: {
+      const size_t lds = (size_t)(2 * G.goff[G.ntv] + 2 * G.n) * sizeof(E);
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&fgp_fused_kernel<E>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)lds);
+      hipLaunchKernelGGL(fgp_fused_kernel<E>, dim3((unsigned)Bt.count), dim3(1024), lds, ctx->stream, xin, add, out,
+                         narrow_geom(G), lam, iters, skip, Bt);
+      return true;
+    }
+    default:
+      return false;
   }
-  const int64_t ng = G.goff[G.ntv], n = G.n;
-  const size_t lds = (size_t)(2 * ng + 2 * n) * sizeof(E);
-  if (lds <= FGP_LDS_BUDGET && n <= ctx->tune.tv_fused_max_n) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&fgp_fused_kernel<E>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                        (int)lds);
-    hipLaunchKernelGGL(fgp_fused_kernel<E>, dim3((unsigned)Bt.count), dim3(1024), lds, ctx->stream, xin, add, out,
-                       narrow_geom(G), lam, iters, skip, Bt);
-    return true;
-  }
-  return false;
 }
 
 template <typename E>
@@ -612,8 +626,7 @@ int32_t fgp_typed(rls_ctx* ctx, const tv_geom& G, E* x, float lam, int iters, E*
 static bool tv_single_ok(const rls_ctx* ctx, const tv_geom& G, size_t es) {
   unsigned nx, ny;
   int u0, u1;
-  if (fgp2d_geom(ctx, G, es, &nx, &ny, &u0, &u1)) return true;
-  return (size_t)(2 * G.goff[G.ntv] + 2 * G.n) * es <= FGP_LDS_BUDGET && G.n <= ctx->tune.tv_fused_max_n;
+  return fgp_variant(ctx, G, es, &nx, &ny, &u0, &u1) != 0;
 }
 
 bool rls_tv_single_ok(const rls_ctx* ctx, int32_t dtype, int32_t ndims, const int64_t* shape, int32_t ntv, const int32_t* dims) {
@@ -640,6 +653,15 @@ int32_t rls_tv_single_launch(rls_ctx* ctx, int32_t dtype, int32_t ndims, const i
 }
 
 extern "C" {
+
+int32_t rls_tv_variant(rls_ctx* ctx, int32_t dtype, int32_t ndims, const int64_t* shape, int32_t ntv, const int32_t* dims) {
+  RLS_CHECK_CTX(ctx);
+  tv_geom G;
+  if (!rls_dtype_ok(dtype) || !make_geom(ndims, shape, ntv, dims, &G)) return rls_fail(ctx, RLS_E_INVALID, "tv_variant: bad argument");
+  unsigned nx, ny;
+  int u0, u1;
+  return fgp_variant(ctx, G, rls_elem_size(dtype), &nx, &ny, &u0, &u1);
+}
 
 int64_t rls_tv_grad_len(int32_t ndims, const int64_t* shape, int32_t ntv, const int32_t* dims) {
   tv_geom G;
