@@ -14,6 +14,7 @@
 //     reductions of an iteration then need no second launch.  Every thread owns the same indices in every pass.
 // All reductions are fixed-order: results are bit-identical run to run.  No kernel here uses scratch.
 #include "rls_common.hpp"
+#include "plan_buffers.hpp"
 
 namespace {
 
@@ -415,8 +416,19 @@ static inline bool dp_dtype_ok(int32_t dtype) { return dtype == RLS_F64 || dtype
 static inline size_t dp_elem(int32_t dtype) { return dtype == RLS_C64 ? 16 : 8; }
 static inline bool dp_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// The owner of a plan's blocks (plan_buffers.hpp) on `ctx`'s pool; a block freed after that context is gone goes back through the
+// synchronous hipFree (rls_dev_free with a null context).
+static plan_buffers dp_memory(rls_ctx* ctx) {
+  const uint64_t id = ctx->id;
+  return plan_buffers([ctx](void** p, size_t bytes) { return (int)rls_dev_alloc(ctx, p, bytes); },
+                      [ctx, id](void* p) { (void)rls_dev_free(rls_ctx_alive(ctx, id) ? ctx : nullptr, p); },
+                      [](void** p, size_t bytes) { return (int)rls_pinned_alloc(p, bytes); }, [](void* p) { rls_pinned_free(p); },
+                      [ctx](void* p, size_t bytes) { return (int)hipMemsetAsync(p, 0, bytes, ctx->stream); });
+}
+
 // what both plans share: the operands, the products' scratch and the launch geometry
 struct dp_base {
+  plan_buffers mem;  // t, part, and the plan's record with its pinned mirror
   rls_ctx* ctx = nullptr;
   uint64_t ctx_id = 0;
   int32_t dtype = 0;
@@ -506,19 +518,23 @@ static int32_t dp_base_create(dp_base& B, rls_ctx* ctx, int32_t dtype, int64_t M
     parts = dp_gn_parts(dtype, AHA, ldg, N);
   } else {
     parts = dp_gn_parts(dtype, A, lda, M);
-    RLS_HIP(ctx, rls_dev_alloc(ctx, &B.t, (size_t)M * dp_elem(dtype)));
+    B.mem.dev(&B.t, (size_t)M * dp_elem(dtype), false);
   }
   B.npart = (int)parts;
-  RLS_HIP(ctx, rls_dev_alloc(ctx, (void**)&B.part, (size_t)parts * sizeof(double)));
+  B.mem.dev(&B.part, (size_t)parts * sizeof(double), false);
   return 0;
 }
-static void dp_base_destroy(dp_base& B, void* rec_d, void* rec_h) {
-  rls_ctx* ctx = rls_ctx_alive(B.ctx, B.ctx_id) ? B.ctx : nullptr;
-  if (ctx) (void)rls_enter(ctx);
-  (void)rls_dev_free(ctx, B.t);
-  (void)rls_dev_free(ctx, B.part);
-  (void)rls_dev_free(ctx, rec_d);
-  if (rec_h) rls_pinned_free(rec_h);
+// the record and its pinned mirror, behind dp_base_create; the status of everything the plan has asked for
+template <typename R>
+static int32_t dp_rec_create(dp_base& B, R** rec_d, R** rec_h, const char* who) {
+  B.mem.dev(rec_d, sizeof(R), false);
+  B.mem.pinned(rec_h, sizeof(R), false);
+  const int e = B.mem.error();
+  return e ? rls_fail(B.ctx, e, who) : 0;
+}
+static void dp_base_destroy(dp_base& B) {
+  if (rls_ctx_alive(B.ctx, B.ctx_id)) (void)rls_enter(B.ctx);
+  B.mem.release();
 }
 // one synchronising read of the device record
 template <typename R>
@@ -532,13 +548,13 @@ static int32_t dp_fetch(rls_ctx* ctx, const R* rec_d, R* rec_h) {
 
 struct rls_cgnr_d {
   dp_base B;
-  void *x, *r, *p, *v;
+  void *x = nullptr, *r = nullptr, *p = nullptr, *v = nullptr;
   dcg_rec *rec = nullptr, *rec_h = nullptr;
 };
 struct rls_fista_d {
   dp_base B;
-  void* buf[2];
-  void *x0, *res;
+  void* buf[2] = {nullptr, nullptr};
+  void *x0 = nullptr, *res = nullptr;
   dfi_rec *rec = nullptr, *rec_h = nullptr;
   int32_t reg_kind = RLS_REG_NONE, proj_kind = RLS_PROJ_NONE;
   int64_t l21_slices = 1;
@@ -611,16 +627,11 @@ int32_t rls_cgnr_create_d(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, con
   RLS_CHECK_CTX(ctx);
   if (!out || !x || !r || !p || !v) return rls_fail(ctx, RLS_E_INVALID, "cgnr_create_d: null pointer");
   *out = nullptr;
-  rls_cgnr_d* s = new rls_cgnr_d();
+  rls_cgnr_d* s = new rls_cgnr_d{{dp_memory(ctx)}};
   int32_t st = dp_base_create(s->B, ctx, dtype, M, N, A, lda, AHA, ldg, "cgnr_create_d: bad argument");
-  if (st == 0) {
-    hipError_t e = rls_dev_alloc(ctx, (void**)&s->rec, sizeof(dcg_rec));
-    if (e == hipSuccess) e = rls_pinned_alloc((void**)&s->rec_h, sizeof(dcg_rec));
-    if (e != hipSuccess) st = rls_fail(ctx, (int32_t)e, "cgnr_create_d: allocation failed");
-  }
+  if (st == 0) st = dp_rec_create(s->B, &s->rec, &s->rec_h, "cgnr_create_d: allocation failed");
   if (st != 0) {
-    if (s->B.ctx) dp_base_destroy(s->B, s->rec, s->rec_h);
-    delete s;
+    rls_cgnr_destroy_d(s);
     return st;
   }
   s->x = x;
@@ -632,7 +643,7 @@ int32_t rls_cgnr_create_d(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, con
 }
 int32_t rls_cgnr_destroy_d(rls_cgnr_d* s) {
   if (!s) return RLS_E_INVALID;
-  dp_base_destroy(s->B, s->rec, s->rec_h);
+  dp_base_destroy(s->B);
   delete s;
   return 0;
 }
@@ -688,16 +699,11 @@ int32_t rls_fista_create_d(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, co
   RLS_CHECK_CTX(ctx);
   if (!out || !x || !x0 || !xold || !res) return rls_fail(ctx, RLS_E_INVALID, "fista_create_d: null pointer");
   *out = nullptr;
-  rls_fista_d* s = new rls_fista_d();
+  rls_fista_d* s = new rls_fista_d{{dp_memory(ctx)}};
   int32_t st = dp_base_create(s->B, ctx, dtype, M, N, A, lda, AHA, ldg, "fista_create_d: bad argument");
-  if (st == 0) {
-    hipError_t e = rls_dev_alloc(ctx, (void**)&s->rec, sizeof(dfi_rec));
-    if (e == hipSuccess) e = rls_pinned_alloc((void**)&s->rec_h, sizeof(dfi_rec));
-    if (e != hipSuccess) st = rls_fail(ctx, (int32_t)e, "fista_create_d: allocation failed");
-  }
+  if (st == 0) st = dp_rec_create(s->B, &s->rec, &s->rec_h, "fista_create_d: allocation failed");
   if (st != 0) {
-    if (s->B.ctx) dp_base_destroy(s->B, s->rec, s->rec_h);
-    delete s;
+    rls_fista_destroy_d(s);
     return st;
   }
   s->buf[0] = x;
@@ -709,7 +715,7 @@ int32_t rls_fista_create_d(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, co
 }
 int32_t rls_fista_destroy_d(rls_fista_d* s) {
   if (!s) return RLS_E_INVALID;
-  dp_base_destroy(s->B, s->rec, s->rec_h);
+  dp_base_destroy(s->B);
   delete s;
   return 0;
 }

@@ -9,6 +9,7 @@
 // reference's "stop at the first iteration where done() holds" exactly while letting the host
 // enqueue iterations in hipGraph-captured chunks.
 #include "rls_common.hpp"
+#include "plan_buffers.hpp"
 
 #include <algorithm>
 #include <mutex>
@@ -17,12 +18,13 @@
 
 // ---- allocation: the plans' scratch comes from the stream-ordered pool of the context named by the innermost
 // rls_alloc_scope of the calling thread; the pinned status mirrors from the process-wide free list (rls_common.hpp) ----
-template <typename T>
-static hipError_t dmalloc(T** p, size_t bytes) { return rls_scoped_malloc(reinterpret_cast<void**>(p), bytes); }
-static hipError_t dfree(void* p) { return rls_scoped_free(p); }
-template <typename T>
-static hipError_t hmalloc(T** p, size_t bytes) { return rls_pinned_alloc(reinterpret_cast<void**>(p), bytes); }
-static void hfree(void* p) { rls_pinned_free(p); }
+// Every plan's blocks have one owner (plan_buffers.hpp): the plan's FIRST member `mem`, so that `new T{plan_memory(ctx)}`
+// initialises every member after it from its default initialiser.  Requests and release() run inside the plan's rls_alloc_scope.
+static plan_buffers plan_memory(rls_ctx* ctx) {
+  return plan_buffers([](void** p, size_t bytes) { return (int)rls_scoped_malloc(p, bytes); }, [](void* p) { (void)rls_scoped_free(p); },
+                      [](void** p, size_t bytes) { return (int)rls_pinned_alloc(p, bytes); }, [](void* p) { rls_pinned_free(p); },
+                      [ctx](void* p, size_t bytes) { return (int)hipMemsetAsync(p, 0, bytes, ctx->stream); });
+}
 // the context a plan allocated from, if it still exists (plans may outlive their context in a garbage-collected host)
 // (pointer AND generation id: a destroyed context's address can be handed out again to a new one, possibly on another device)
 static rls_ctx* alloc_ctx_of(rls_ctx* ctx, uint64_t id) { return rls_ctx_alive(ctx, id) ? ctx : nullptr; }
@@ -31,16 +33,17 @@ static rls_ctx* alloc_ctx_of(rls_ctx* ctx, uint64_t id) { return rls_ctx_alive(c
 // operator
 // ---------------------------------------------------------------------------------------------
 struct rls_operator {
-  rls_ctx* ctx;
+  plan_buffers mem;
+  rls_ctx* ctx = nullptr;
   uint64_t ctx_id = 0;  // ctx->id at creation (alloc_ctx_of)
-  int32_t dtype;
-  int64_t M, N;
-  const void* A;  // may be null (Gram-only operator)
-  int64_t lda;
-  const void* G;  // Gram matrix (N x N) or null
-  int64_t ldg;
-  void* t;        // length-M scratch for the matrix-free normal operator
-  void* slab;     // per-workgroup partial-v slab of the fused one-pass normal operator (or null)
+  int32_t dtype = 0;
+  int64_t M = 0, N = 0;
+  const void* A = nullptr;  // may be null (Gram-only operator)
+  int64_t lda = 0;
+  const void* G = nullptr;  // Gram matrix (N x N) or null
+  int64_t ldg = 0;
+  void* t = nullptr;        // length-M scratch for the matrix-free normal operator
+  void* slab = nullptr;     // per-workgroup partial-v slab of the fused one-pass normal operator (or null)
 };
 
 static int32_t op_normal(rls_operator* op, const void* p, void* v, const int* skip) {
@@ -171,23 +174,12 @@ struct resident_slot : resident_loss_state {
   bool used = false;            // a resident launch went out since the last status read: that read fetches the flags
   bool clean = false;           // the plan's init kernel has just zeroed the arrival counters itself (chain)
 
-  // the sync block (zeroed once: the sticky word starts at 0) and the pinned mirror
-  hipError_t alloc(rls_ctx* ctx, const rls_operator* op) {
-    hipError_t e = dmalloc(&sync, rls_resident_sync_alloc_bytes(op->dtype, op->N));
-    if (e == hipSuccess) e = hipMemsetAsync(sync, 0, rls_cgnr_resident_sync_bytes(), ctx->stream);
-    if (e == hipSuccess && !flags_h) {
-      e = hmalloc(&flags_h, 4 * sizeof(unsigned));
-      if (e == hipSuccess) memset(flags_h, 0, 4 * sizeof(unsigned));
-    }
-    return e;
-  }
-  // (inside the plan's rls_alloc_scope.)  Also the way out of a failed alloc(): resident mode is an optimisation, the plan
-  // runs on its per-iteration pipeline without the block
-  void release() {
-    if (sync) dfree(sync);
-    if (flags_h) hfree(flags_h);
-    sync = nullptr;
-    flags_h = nullptr;
+  // the sync block (its head zeroed once: the sticky word starts at 0) and the pinned mirror, from the owning plan's arena.  A plan
+  // for which resident mode is only an optimisation asks between mark() and rollback(): without the block its pipeline runs
+  void alloc(plan_buffers& mem, rls_ctx* ctx, const rls_operator* op) {
+    mem.dev(&sync, rls_resident_sync_alloc_bytes(op->dtype, op->N), false);
+    if (sync) mem.fail((int)hipMemsetAsync(sync, 0, rls_cgnr_resident_sync_bytes(), ctx->stream));
+    mem.pinned(&flags_h, 4 * sizeof(unsigned), true);
   }
   bool usable(const rls_ctx* ctx) const { return sync && !off && ctx->tune.resident; }
 
@@ -259,43 +251,54 @@ struct srv_state {
   void* q_plan = nullptr;  // the rls_cgnr the ring belongs to
 };
 
+// The 32-word control block, if it can be had: server mode is an optimisation, a plan without the block answers every step call
+// with a launch of its own.
+static bool server_ctl_optional(plan_buffers& mem, srv_state* v) {
+  if (mem.error()) return false;
+  const plan_buffers::mark_t m = mem.mark();
+  mem.pinned(&v->ctl, 32 * sizeof(unsigned), true);
+  if (mem.error()) mem.rollback(m);
+  return v->ctl != nullptr;
+}
+
 struct rls_cgnr {
-  rls_operator* op;
-  rls_ctx* actx;  // the context whose pool the plan's scratch came from (checked alive before it is used in destroy)
+  plan_buffers mem;  // owns every block below, srv.ctl and resident.{sync, flags_h} included
+  rls_operator* op = nullptr;
+  rls_ctx* actx = nullptr;  // the context whose pool the plan's scratch came from (checked alive before it is used in destroy)
   uint64_t actx_id = 0;
-  int device;
-  void *x, *r, *p, *v;
-  cgnr_scalars* sc;    // device
-  cgnr_scalars* sc_h;  // pinned host
+  int device = 0;
+  void *x = nullptr, *r = nullptr, *p = nullptr, *v = nullptr;
+  cgnr_scalars* sc = nullptr;    // device
+  cgnr_scalars* sc_h = nullptr;  // pinned host
   step_graph graph;
-  bool initialised;
+  bool initialised = false;
   // fused pipeline (normal.hip): alternate (r, p) pair, partial dots, staged scalars
-  void *r1, *p1;
-  double* dots;
+  void *r1 = nullptr, *p1 = nullptr;
+  double* dots = nullptr;
   double* ttw = nullptr;
-  cgnr_scalars* scn;
+  cgnr_scalars* scn = nullptr;
   // batched plans: nrhs right-hand sides, columns ldv elements apart, own partial-row slab
-  int nrhs;
-  int64_t ldv;
-  void* slab_b;
+  int nrhs = 1;
+  int64_t ldv = 0;
+  void* slab_b = nullptr;
   // Gram-mode pipeline (normal.hip): one launch per iteration, second parity of v and the partial dots
-  bool gram_pipe;
-  void* v1;
-  double* gdots;
+  bool gram_pipe = false;
+  void* v1 = nullptr;
+  double* gdots = nullptr;
   // batched plans on the matrix cores (skinny.hip): packed operands + row-split partials
-  bool skinny;
-  float *Ppack, *Tpack;
-  void* Vpart;
-  int splits;
-  int half;  // operand-panel layout, fixed at creation (rls_skinny_half)
+  bool skinny = false;
+  float *Ppack = nullptr, *Tpack = nullptr;
+  void* Vpart = nullptr;
+  int splits = 1;
+  int half = 0;  // operand-panel layout, fixed at creation (rls_skinny_half)
   // resident mode (normal.hip, cgnr_resident_kernel): sync block + lost-launch bookkeeping, per-workgroup partial dots
   resident_slot resident;
-  double* rdots;
+  double* rdots = nullptr;
   rls_mailbox_slot mb_arm;  // step_status: the call's last kernel publishes the scalars (pipeline and small-system paths)
   srv_state srv;  // server mode of the resident kernel (rls_cgnr_step_status)
   bool mb_sent = false;     // ... and this call's path did take the slot
-  bool gram_resident;  // Gram mode: AHA fits the register files (rls_gram_resident_ok)
-  long long requested;  // iterations asked for since init (what a lost launch did not run: requested - the device's count)
+  bool gram_resident = false;  // Gram mode: AHA fits the register files (rls_gram_resident_ok)
+  long long requested = 0;  // iterations asked for since init (what a lost launch did not run: requested - the device's count)
   bool small = false;  // the system fits one CU's registers: a step call is ONE single-workgroup launch (small.hip)
   // batched plan on an explicit Gram matrix, <= 8 ComplexF32 columns, AHA in the register files (gramk.hip): exchange scratch
   bool gramk = false;
@@ -671,25 +674,26 @@ static int32_t cgnr_effective_iterations(rls_cgnr* s, int32_t iterations) {
 // FISTA
 // ---------------------------------------------------------------------------------------------
 struct rls_fista {
-  rls_operator* op;
-  rls_ctx* actx;
+  plan_buffers mem;  // owns every block below, srv.ctl and resident.{sync, flags_h} included
+  rls_operator* op = nullptr;
+  rls_ctx* actx = nullptr;
   uint64_t actx_id = 0;
-  int device;
-  void* buf[2];  // x / xold, swapped by iteration parity: state.x == buf[iteration & 1]
-  void *x0, *res;
-  void* y;       // extrapolated point (plan-owned), the GEMV input
-  void *y1, *res_raw;  // fused pipeline: second extrapolated-point buffer, AHA y before "- x0"
-  fista_scalars* scn;  // staged scalars (slab pipeline) / second parity (Gram pipeline)
-  bool use_pipe;
-  void* res_raw1;      // Gram pipeline: second parity of AHA y
-  bool use_gram;
-  fista_scalars* sc;
-  fista_scalars* sc_h;
+  int device = 0;
+  void* buf[2] = {nullptr, nullptr};  // x / xold, swapped by iteration parity: state.x == buf[iteration & 1]
+  void *x0 = nullptr, *res = nullptr;
+  void* y = nullptr;       // extrapolated point (plan-owned), the GEMV input
+  void *y1 = nullptr, *res_raw = nullptr;  // fused pipeline: second extrapolated-point buffer, AHA y before "- x0"
+  fista_scalars* scn = nullptr;  // staged scalars (slab pipeline) / second parity (Gram pipeline)
+  bool use_pipe = false;
+  void* res_raw1 = nullptr;      // Gram pipeline: second parity of AHA y
+  bool use_gram = false;
+  fista_scalars* sc = nullptr;
+  fista_scalars* sc_h = nullptr;
   step_graph graph;
-  int32_t reg_kind, proj_kind;
-  float lambda;
-  int64_t l21_slices;
-  bool initialised;
+  int32_t reg_kind = RLS_REG_L1, proj_kind = RLS_PROJ_NONE;
+  float lambda = 0.f;
+  int64_t l21_slices = 1;
+  bool initialised = false;
   // batched plan (rls_fista_create_batched): nrhs columns ldv elements apart, the K extrapolated points as an
   // MFMA operand panel, T = A Y and the partial rows of A^H T (skinny.hip)
   int nrhs = 1;
@@ -1083,23 +1087,24 @@ struct cg_scalars {
 };
 
 struct rls_cg {
-  rls_operator* op;
-  rls_ctx* actx;
+  plan_buffers mem;  // owns every block below, resident.{sync, flags_h} included
+  rls_operator* op = nullptr;
+  rls_ctx* actx = nullptr;
   uint64_t actx_id = 0;
-  int device;
-  void *u, *r, *c;
-  cg_scalars* sc;
-  cg_scalars* sc_h;
+  int device = 0;
+  void *u = nullptr, *r = nullptr, *c = nullptr;
+  cg_scalars* sc = nullptr;
+  cg_scalars* sc_h = nullptr;
   // fused pipeline (normal.hip): cg! on (AHA + rho I) is the CGNR recurrence with lambda = rho and the
   // start residual b - (AHA + rho I) x0, so it reuses the two-launch CGNR pipeline (p = u, v = c)
-  void *r1, *p1;
-  double* dots;
-  cgnr_scalars *psc, *pscn, *psc_h;
+  void *r1 = nullptr, *p1 = nullptr;
+  double* dots = nullptr;
+  cgnr_scalars *psc = nullptr, *pscn = nullptr, *psc_h = nullptr;
   step_graph graph;
-  bool used_pipeline;
+  bool used_pipeline = false;
   // Gram-mode pipeline: second parity of c (= v) and of the partial dots
-  void* v1;
-  double* gdots;
+  void* v1 = nullptr;
+  double* gdots = nullptr;
   // batched plan (rls_cg_create_batched): nrhs columns ldv elements apart, operand panel + partial rows of the
   // skinny matrix-core products (skinny.hip); sc / sc_h hold nrhs structs
   int nrhs = 1;
@@ -1451,13 +1456,11 @@ __global__ __launch_bounds__(256) void gram_kernel(const E* __restrict__ A, int6
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
+// a plan's scalars on the device and their pinned mirror, both zeroed
 template <typename S>
-static int32_t alloc_scalars(rls_ctx* ctx, S** d, S** h, int n = 1) {
-  RLS_HIP(ctx, dmalloc((void**)d, sizeof(S) * n));
-  RLS_HIP(ctx, hipMemsetAsync(*d, 0, sizeof(S) * n, ctx->stream));
-  RLS_HIP(ctx, hmalloc(h, sizeof(S) * n));
-  memset(*h, 0, sizeof(S) * n);
-  return 0;
+static void alloc_scalars(plan_buffers& mem, S** d, S** h, int n = 1) {
+  mem.dev(d, sizeof(S) * n, true);
+  mem.pinned(h, sizeof(S) * n, true);
 }
 template <typename S>
 static int32_t fetch_scalars(rls_ctx* ctx, S* d, S* h) {
@@ -1545,16 +1548,18 @@ struct admm_scalars {
 constexpr int ADMM_REC = 8;  // floats per log record: Delta, sk, eps_pri, rk, eps_dua, cg iterations, 0, 0
 
 struct rls_admm {
-  rls_cg* cg;
-  rls_ctx* actx;
+  plan_buffers mem;
+  rls_cg* cg = nullptr;
+  rls_ctx* actx = nullptr;
   uint64_t actx_id = 0;
-  int device;
-  rls_admm_params P;
-  bool ready;
-  admm_scalars *sc, *sc_h;
-  float *log, *log_h;
-  int log_cap;
-  int enq;  // outer iterations enqueued since init (== device iteration unless the plan stopped early)
+  int device = 0;
+  rls_admm_params P = {};
+  bool ready = false;
+  admm_scalars *sc = nullptr, *sc_h = nullptr;
+  float *log = nullptr, *log_h = nullptr;  // the group behind log_mark: replaced as a whole when an init asks for more records
+  plan_buffers::mark_t log_mark = {};
+  int log_cap = 0;
+  int enq = 0;  // outer iterations enqueued since init (== device iteration unless the plan stopped early)
   int nrhs = 1;  // batched plans: sc / sc_h / log hold one entry per column
   int requested = 0;  // outer iterations asked for since init (capped at P.iterations)
   int fallbacks = 0;  // resident cg! launches lost and recovered (rls_admm_get_status)
@@ -1975,7 +1980,8 @@ int32_t rls_operator_create(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, c
   if (A && (M <= 0 || lda < M)) return rls_fail(ctx, RLS_E_INVALID, "operator_create: bad shape/lda");
   RLS_HIP(ctx, rls_enter(ctx));
   rls_alloc_scope alloc_scope(ctx);
-  rls_operator* op = new rls_operator();
+  *out = nullptr;
+  rls_operator* op = new rls_operator{plan_memory(ctx)};
   op->ctx = ctx;
   op->ctx_id = ctx->id;
   op->dtype = dtype;
@@ -1983,18 +1989,13 @@ int32_t rls_operator_create(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, c
   op->N = N;
   op->A = A;
   op->lda = lda;
-  op->G = nullptr;
-  op->ldg = 0;
-  op->t = nullptr;
-  op->slab = nullptr;
   if (A) {
-    hipError_t e = dmalloc(&op->t, (size_t)M * rls_elem_size(dtype));
+    op->mem.dev(&op->t, (size_t)M * rls_elem_size(dtype), false);
     const size_t ws = rls_normal_fused_workspace(ctx, dtype, M, N, A, lda);
-    if (e == hipSuccess && ws > 0) e = dmalloc(&op->slab, ws);
-    if (e != hipSuccess) {
-      if (op->t) dfree(op->t);
-      delete op;
-      return rls_fail(ctx, (int32_t)e, "operator_create: hipMalloc failed");
+    if (ws > 0) op->mem.dev(&op->slab, ws, false);
+    if (const int e = op->mem.error()) {
+      rls_operator_destroy(op);
+      return rls_fail(ctx, e, "operator_create: hipMalloc failed");
     }
   }
   *out = op;
@@ -2012,8 +2013,7 @@ int32_t rls_operator_set_gram(rls_operator* op, const void* AHA, int64_t ld) {
 int32_t rls_operator_destroy(rls_operator* op) {
   if (!op) return RLS_E_INVALID;
   rls_alloc_scope alloc_scope(alloc_ctx_of(op->ctx, op->ctx_id));
-  if (op->slab) dfree(op->slab);
-  if (op->t) dfree(op->t);  // hipFree resolves the owning device from the pointer
+  op->mem.release();  // hipFree resolves the owning device from the pointer
   delete op;
   return 0;
 }
@@ -2053,11 +2053,13 @@ int32_t rls_gram(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* 
     // matrix cores: A^H T with T = A in 16-column panels (skinny.hip); M x N scratch for the panels
     void* panels = nullptr;
     rls_alloc_scope alloc_scope(ctx);
-    RLS_HIP(ctx, dmalloc(&panels, (size_t)M * (size_t)N * rls_elem_size(dtype)));
+    plan_buffers scratch = plan_memory(ctx);
+    scratch.dev(&panels, (size_t)M * (size_t)N * rls_elem_size(dtype), false);
+    RLS_HIP(ctx, (hipError_t)scratch.error());
     int32_t st = rls_skinny_gram(ctx, dtype, M, N, A, lda, G, ld, panels);
     if (st == 0) st = gram_hermitianize(ctx, dtype, N, G, ld);
     hipError_t e = rls_stream_wait(ctx->stream);  // setup path: the scratch is freed before returning
-    dfree(panels);
+    scratch.release();
     if (st == 0 && e != hipSuccess) st = rls_fail(ctx, (int32_t)e, hipGetErrorString(e));
     return st;
   }
@@ -2085,126 +2087,86 @@ static int32_t cgnr_create_impl(rls_operator* op, int32_t nrhs, void* x, void* r
   if (nrhs > 1 && !skinny)
     return rls_fail(ctx, RLS_E_UNSUPPORTED, "batched CGNR runs on the matrix cores: A (and AHA, when explicit) with M, N multiples "
                                             "of 16 and 16-byte aligned columns (other shapes: one plan per column)");
+  *out = nullptr;
   rls_alloc_scope alloc_scope(ctx);
-  rls_cgnr* s = new rls_cgnr();
+  rls_cgnr* s = new rls_cgnr{plan_memory(ctx)};
+  plan_buffers& mem = s->mem;  // after the first failure every request below is a no-op
   s->actx = ctx;
   s->actx_id = ctx->id;
   s->skinny = skinny;
-  s->gram_pipe = false;
-  s->v1 = nullptr;
-  s->gdots = nullptr;
-  s->Ppack = s->Tpack = nullptr;
-  s->Vpart = nullptr;
-  s->splits = 1;
   s->op = op;
   s->device = ctx->device;
   s->x = x;
   s->r = r;
   s->p = p;
   s->v = v;
-  s->initialised = false;
-  s->r1 = s->p1 = nullptr;
-  s->dots = nullptr;
-  s->scn = nullptr;
-  s->sc = nullptr;
-  s->sc_h = nullptr;
   s->nrhs = nrhs;
   s->ldv = ldv;
-  s->slab_b = nullptr;
-  s->rdots = nullptr;
-  s->gram_resident = false;
-  s->requested = 0;
   const size_t sb = sizeof(cgnr_scalars) * (size_t)nrhs;
-  hipError_t e = dmalloc(&s->sc, sb);
-  if (e == hipSuccess) e = hipMemsetAsync(s->sc, 0, sb, ctx->stream);
-  if (e == hipSuccess) e = hmalloc(&s->sc_h, sb);
-  if (e == hipSuccess) memset(s->sc_h, 0, sb);
-  if (e == hipSuccess && op->slab) {  // scratch of the fused pipeline
+  mem.dev(&s->sc, sb, true);
+  mem.pinned(&s->sc_h, sb, true);
+  if (op->slab) {  // scratch of the fused pipeline
     const size_t vb = (size_t)ldv * nrhs * rls_elem_size(op->dtype);
     const size_t nd = (size_t)((op->N + 15) / 16) * 4 * sizeof(double) * nrhs;
-    e = dmalloc(&s->r1, vb);
-    if (e == hipSuccess) e = dmalloc(&s->p1, vb);
-    if (e == hipSuccess) e = hipMemsetAsync(s->r1, 0, vb, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->p1, 0, vb, ctx->stream);
-    if (e == hipSuccess) e = dmalloc(&s->dots, nd);
-    if (e == hipSuccess && op->A && !op->G) {  // matrix-free: K_A's ||t_w||^2 per row block (alpha = zeta / ||A p||^2)
-      const size_t tb = (size_t)rls_cgnr_resident_nwg(op->ctx, op->dtype, op->M, op->N) * sizeof(double) * nrhs;
-      e = dmalloc(&s->ttw, tb);
-      if (e == hipSuccess) e = hipMemsetAsync(s->ttw, 0, tb, ctx->stream);
-    }
-    if (e == hipSuccess) e = dmalloc(&s->scn, sb);
-    if (e == hipSuccess) e = hipMemsetAsync(s->dots, 0, nd, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->scn, 0, sb, ctx->stream);
-    if (e == hipSuccess && nrhs > 1 && !skinny)
-      e = dmalloc(&s->slab_b, rls_normal_fused_workspace(op->ctx, op->dtype, op->M, op->N, op->A, op->lda) * (size_t)nrhs);
+    mem.dev(&s->r1, vb, true);
+    mem.dev(&s->p1, vb, true);
+    mem.dev(&s->dots, nd, true);
+    if (op->A && !op->G)  // matrix-free: K_A's ||t_w||^2 per row block (alpha = zeta / ||A p||^2)
+      mem.dev(&s->ttw, (size_t)rls_cgnr_resident_nwg(op->ctx, op->dtype, op->M, op->N) * sizeof(double) * nrhs, true);
+    mem.dev(&s->scn, sb, true);
+    if (nrhs > 1 && !skinny)
+      mem.dev(&s->slab_b, rls_normal_fused_workspace(op->ctx, op->dtype, op->M, op->N, op->A, op->lda) * (size_t)nrhs, false);
   }
   s->small = nrhs == 1 && op->A && !op->G && rls_small_ok(op->dtype, op->M, op->N, op->A, op->lda);
-  if (e == hipSuccess && s->small && !s->srv.ctl && hmalloc(&s->srv.ctl, 32 * sizeof(unsigned)) == hipSuccess) {
-    memset(s->srv.ctl, 0, 32 * sizeof(unsigned));  // (the single-workgroup kernel can stay and listen as well: rls_cgnr_step_status)
-    s->srv.resident_used = nullptr;                // (no co-residency requirement, nothing to give up: no flags to read)
-  }
-  if (e == hipSuccess && nrhs == 1 && op->slab && op->A && !op->G &&
-      rls_cgnr_resident_ok(ctx, op->dtype, op->M, op->N, op->A, op->lda)) {
-    const size_t db = (size_t)rls_cgnr_resident_nwg(op->ctx, op->dtype, op->M, op->N) * 4 * sizeof(double);
-    e = s->resident.alloc(ctx, op);
-    if (e == hipSuccess) e = dmalloc(&s->rdots, db);
-    if (e == hipSuccess) e = hipMemsetAsync(s->rdots, 0, db, ctx->stream);
-    if (e == hipSuccess && !s->srv.ctl) {
-      e = hmalloc(&s->srv.ctl, RLS_Q_CTL_WORDS * sizeof(unsigned));  // (the control block and the command ring of queue mode)
-      if (e == hipSuccess) memset(s->srv.ctl, 0, RLS_Q_CTL_WORDS * sizeof(unsigned));
-      s->q_ok = e == hipSuccess && rls_cgnr_resident_queue_ok(ctx, op->dtype, op->M, op->N);
+  // (the single-workgroup kernel can stay and listen as well: rls_cgnr_step_status; no co-residency requirement, nothing to give
+  // up: no flags to read)
+  if (s->small) server_ctl_optional(mem, &s->srv);
+  if (!mem.error() && nrhs == 1 && op->slab && op->A && !op->G && rls_cgnr_resident_ok(ctx, op->dtype, op->M, op->N, op->A, op->lda)) {
+    s->resident.alloc(mem, ctx, op);
+    mem.dev(&s->rdots, (size_t)rls_cgnr_resident_nwg(op->ctx, op->dtype, op->M, op->N) * 4 * sizeof(double), true);
+    if (!s->srv.ctl) {
+      mem.pinned(&s->srv.ctl, RLS_Q_CTL_WORDS * sizeof(unsigned), true);  // (the control block and the command ring of queue mode)
+      s->q_ok = !mem.error() && rls_cgnr_resident_queue_ok(ctx, op->dtype, op->M, op->N);
     }
-    if (e == hipSuccess) memset(s->srv.ctl, 0, 32 * sizeof(unsigned));
     s->srv.resident_used = &s->resident.used;
     s->srv.q_plan = s;
   }
-  if (e == hipSuccess && nrhs == 1 && op->G && rls_gram_pipe_ok(op->dtype, op->N, op->G, op->ldg)) {
+  if (!mem.error() && nrhs == 1 && op->G && rls_gram_pipe_ok(op->dtype, op->N, op->G, op->ldg)) {
     const size_t vb = (size_t)op->N * rls_elem_size(op->dtype);
     const size_t nd = (size_t)2 * rls_gram_pipe_nwg(op->dtype, op->N) * 4 * sizeof(double);
-    if (!s->r1) e = dmalloc(&s->r1, vb);
-    if (e == hipSuccess && !s->p1) e = dmalloc(&s->p1, vb);
-    if (e == hipSuccess) e = dmalloc(&s->v1, vb);
-    if (e == hipSuccess) e = dmalloc(&s->gdots, nd);
-    if (e == hipSuccess && !s->scn) e = dmalloc(&s->scn, sb);
-    if (e == hipSuccess) e = hipMemsetAsync(s->r1, 0, vb, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->p1, 0, vb, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->v1, 0, vb, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->gdots, 0, nd, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->scn, 0, sb, ctx->stream);
-    s->gram_pipe = e == hipSuccess;
-    if (e == hipSuccess && !s->resident.sync && rls_gram_resident_ok(ctx, op->dtype, op->N, op->G, op->ldg)) {
-      e = s->resident.alloc(ctx, op);
-      s->gram_resident = e == hipSuccess;
-      if (e == hipSuccess && !s->srv.ctl && rls_gram_resident_server_ok(op->dtype, op->N) &&
-          hmalloc(&s->srv.ctl, 32 * sizeof(unsigned)) == hipSuccess) {
-        memset(s->srv.ctl, 0, 32 * sizeof(unsigned));
+    if (!s->r1) mem.dev(&s->r1, vb, true);  // (an operator with A and AHA: the fused pipeline's blocks above, same sizes, zeroed)
+    if (!s->p1) mem.dev(&s->p1, vb, true);
+    mem.dev(&s->v1, vb, true);
+    mem.dev(&s->gdots, nd, true);
+    if (!s->scn) mem.dev(&s->scn, sb, true);
+    s->gram_pipe = !mem.error();
+    if (s->gram_pipe && !s->resident.sync && rls_gram_resident_ok(ctx, op->dtype, op->N, op->G, op->ldg)) {
+      s->resident.alloc(mem, ctx, op);
+      s->gram_resident = !mem.error();
+      if (s->gram_resident && !s->srv.ctl && rls_gram_resident_server_ok(op->dtype, op->N) && server_ctl_optional(mem, &s->srv))
         s->srv.resident_used = &s->resident.used;
-      }
     }
   }
-  if (e == hipSuccess && skinny) {
+  if (!mem.error() && skinny) {
     size_t pb, tb, vb;
     rls_skinny_sizes(op->ctx, op->dtype, op->M, op->N, nrhs, &pb, &tb, &vb, &s->splits);
     s->half = rls_skinny_half(op->ctx, op->dtype, nrhs);
-    e = dmalloc(&s->Ppack, pb);
-    if (e == hipSuccess) e = hipMemsetAsync(s->Ppack, 0, pb, ctx->stream);  // the padding columns of the last group stay zero
-    if (e == hipSuccess) e = dmalloc(&s->Tpack, tb);
-    if (e == hipSuccess) e = dmalloc(&s->Vpart, vb);
-    if (e == hipSuccess && op->G && s->half && rls_gramk_resident_ok(ctx, op->dtype, op->N, nrhs, op->G, op->ldg)) {
+    mem.dev(&s->Ppack, pb, true);  // the padding columns of the last group stay zero
+    mem.dev(&s->Tpack, tb, false);
+    mem.dev(&s->Vpart, vb, false);
+    if (!mem.error() && op->G && s->half && rls_gramk_resident_ok(ctx, op->dtype, op->N, nrhs, op->G, op->ldg)) {
       size_t xb, xxb, db;
       rls_gramk_sizes(op->N, &xb, &xxb, &db);
-      e = s->resident.alloc(ctx, op);
-      if (e == hipSuccess) e = dmalloc(&s->gk_vx, xb);
-      if (e == hipSuccess) e = hipMemsetAsync(s->gk_vx, 0, xb, ctx->stream);  // rows >= N are read, never written
-      if (e == hipSuccess) e = dmalloc(&s->gk_xx, xxb);
-      if (e == hipSuccess) e = dmalloc(&s->gk_dots, db);
-      if (e == hipSuccess) e = hipMemsetAsync(s->gk_dots, 0, db, ctx->stream);  // slots of absent workgroups add 0.0
-      s->gramk = e == hipSuccess;
+      s->resident.alloc(mem, ctx, op);
+      mem.dev(&s->gk_vx, xb, true);  // rows >= N are read, never written
+      mem.dev(&s->gk_xx, xxb, false);
+      mem.dev(&s->gk_dots, db, true);  // slots of absent workgroups add 0.0
+      s->gramk = !mem.error();
     }
   }
-  if (e != hipSuccess) {
+  if (const int e = mem.error()) {
     rls_cgnr_destroy(s);
-    return rls_fail(ctx, (int32_t)e, "cgnr_create: allocation failed");
+    return rls_fail(ctx, e, "cgnr_create: allocation failed");
   }
   *out = s;
   return 0;
@@ -2226,28 +2188,7 @@ int32_t rls_cgnr_destroy(rls_cgnr* s) {
   hipSetDevice(s->device);
   rls_alloc_scope alloc_scope(alloc_ctx_of(s->actx, s->actx_id));
   s->graph.drop();
-  if (s->r1) dfree(s->r1);
-  if (s->p1) dfree(s->p1);
-  if (s->dots) dfree(s->dots);
-  if (s->ttw) dfree(s->ttw);
-  if (s->scn) dfree(s->scn);
-  if (s->slab_b) dfree(s->slab_b);
-  if (s->v1) dfree(s->v1);
-  if (s->gdots) dfree(s->gdots);
-  if (s->Ppack) dfree(s->Ppack);
-  if (s->Tpack) dfree(s->Tpack);
-  if (s->Vpart) dfree(s->Vpart);
-  if (s->gk_vx) dfree(s->gk_vx);
-  if (s->gk_xx) dfree(s->gk_xx);
-  if (s->gk_dots) dfree(s->gk_dots);
-  if (s->q_b) dfree(s->q_b);
-  if (s->q_bh) hfree(s->q_bh);
-  if (s->q_xh) hfree(s->q_xh);
-  s->resident.release();
-  if (s->rdots) dfree(s->rdots);
-  if (s->srv.ctl) hfree(s->srv.ctl);
-  if (s->sc) dfree(s->sc);
-  if (s->sc_h) hfree(s->sc_h);
+  s->mem.release();
   delete s;
   return 0;
 }
@@ -2590,11 +2531,16 @@ int32_t rls_cgnr_solve_queue_host(rls_cgnr* const* plans, const void* const* b_h
     const size_t es = rls_elem_size(op->dtype);
     const size_t bb = (size_t)(op->A ? op->M : op->N) * es, xb = (size_t)op->N * es;
     if (!b_h[k] || !x_h[k]) return rls_fail(ctx, RLS_E_INVALID, "cgnr solve queue: null buffer");
-    if (!s->q_b) {
+    if (!s->q_b) {  // all three or none: a later call finds either the whole staging or nothing
       rls_alloc_scope alloc_scope(ctx);
-      RLS_HIP(ctx, dmalloc(&s->q_b, bb));
-      RLS_HIP(ctx, hmalloc(&s->q_bh, bb));
-      RLS_HIP(ctx, hmalloc(&s->q_xh, xb));
+      const plan_buffers::mark_t m = s->mem.mark();
+      s->mem.dev(&s->q_b, bb, false);
+      s->mem.pinned(&s->q_bh, bb, false);
+      s->mem.pinned(&s->q_xh, xb, false);
+      if (const int e = s->mem.error()) {
+        s->mem.rollback(m);
+        return rls_fail(ctx, e, "cgnr solve queue: allocation failed");
+      }
     }
     memcpy(s->q_bh, b_h[k], bb);
     RLS_HIP(ctx, hipMemcpyAsync(s->q_b, s->q_bh, bb, hipMemcpyHostToDevice, ctx->stream));
@@ -3192,8 +3138,10 @@ int32_t rls_fista_create(rls_operator* op, void* x, void* x0, void* xold, void* 
   rls_ctx* ctx = op->ctx;
   if (!x || !x0 || !xold || !res || !out) return rls_fail(ctx, RLS_E_INVALID, "fista_create: null pointer");
   RLS_HIP(ctx, rls_enter(ctx));
+  *out = nullptr;
   rls_alloc_scope alloc_scope(ctx);
-  rls_fista* s = new rls_fista();
+  rls_fista* s = new rls_fista{plan_memory(ctx)};
+  plan_buffers& mem = s->mem;
   s->op = op;
   s->actx = ctx;
   s->actx_id = ctx->id;
@@ -3202,63 +3150,32 @@ int32_t rls_fista_create(rls_operator* op, void* x, void* x0, void* xold, void* 
   s->buf[1] = xold;
   s->x0 = x0;
   s->res = res;
-  s->y = nullptr;
-  s->reg_kind = RLS_REG_L1;
-  s->proj_kind = RLS_PROJ_NONE;
-  s->lambda = 0.f;
-  s->l21_slices = 1;
-  s->initialised = false;
-  s->y1 = s->res_raw = nullptr;
-  s->scn = nullptr;
-  s->use_pipe = false;
-  s->res_raw1 = nullptr;
-  s->use_gram = false;
   s->small = op->A && !op->G && rls_small_ok(op->dtype, op->M, op->N, op->A, op->lda);
-  if (s->small && hmalloc(&s->srv.ctl, 32 * sizeof(unsigned)) == hipSuccess) memset(s->srv.ctl, 0, 32 * sizeof(unsigned));  // (server mode of the single-workgroup kernel)
+  if (s->small) server_ctl_optional(mem, &s->srv);  // (server mode of the single-workgroup kernel)
   const size_t vb = (size_t)op->N * rls_elem_size(op->dtype);
-  hipError_t e = dmalloc(&s->y, vb);
+  mem.dev(&s->y, vb, false);
   const bool gram = op->G && rls_gram_pipe_ok(op->dtype, op->N, op->G, op->ldg);
-  if (e == hipSuccess && gram) {
-    e = dmalloc(&s->res_raw1, vb);
-    if (e == hipSuccess) e = hipMemsetAsync(s->res_raw1, 0, vb, ctx->stream);
+  if (gram) mem.dev(&s->res_raw1, vb, true);
+  if (op->slab || gram) {
+    mem.dev(&s->y1, vb, true);
+    mem.dev(&s->res_raw, 2 * vb, true);  // (second half: state.res of the iteration a listening kernel runs ahead, fista_resident_kernel's SPEC)
+    mem.dev(&s->scn, sizeof(fista_scalars), true);
   }
-  if (e == hipSuccess && (op->slab || gram)) {
-    e = dmalloc(&s->y1, vb);
-    if (e == hipSuccess) e = dmalloc(&s->res_raw, 2 * vb);  // (second half: state.res of the iteration a listening kernel runs ahead, fista_resident_kernel's SPEC)
-    if (e == hipSuccess) e = dmalloc(&s->scn, sizeof(fista_scalars));
-    if (e == hipSuccess) e = hipMemsetAsync(s->y1, 0, vb, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->res_raw, 0, 2 * vb, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->scn, 0, sizeof(fista_scalars), ctx->stream);
-  }
-  if (e != hipSuccess) {
-    if (s->y) dfree(s->y);
-    if (s->y1) dfree(s->y1);
-    if (s->res_raw) dfree(s->res_raw);
-    if (s->res_raw1) dfree(s->res_raw1);
-    if (s->scn) dfree(s->scn);
-    delete s;
-    return rls_fail(ctx, (int32_t)e, "fista_create: hipMalloc failed");
-  }
-  if ((op->slab && op->A && !op->G && rls_cgnr_resident_ok(ctx, op->dtype, op->M, op->N, op->A, op->lda)) ||
-      (gram && rls_gram_resident_ok(ctx, op->dtype, op->N, op->G, op->ldg))) {
-    if (s->resident.alloc(ctx, op) != hipSuccess) {
-      s->resident.release();  // resident mode is an optimisation: without its scratch the pipeline runs
+  if (!mem.error() && ((op->slab && op->A && !op->G && rls_cgnr_resident_ok(ctx, op->dtype, op->M, op->N, op->A, op->lda)) ||
+                       (gram && rls_gram_resident_ok(ctx, op->dtype, op->N, op->G, op->ldg)))) {
+    const plan_buffers::mark_t m = mem.mark();
+    s->resident.alloc(mem, ctx, op);
+    if (mem.error()) {
+      mem.rollback(m);  // resident mode is an optimisation: without its scratch the pipeline runs
       (void)hipGetLastError();
-    } else if ((!gram || rls_gram_resident_server_ok(op->dtype, op->N)) &&
-               (s->srv.ctl || hmalloc(&s->srv.ctl, 32 * sizeof(unsigned)) == hipSuccess)) {  // (both resident kernels can stay and listen)
-      memset(s->srv.ctl, 0, 32 * sizeof(unsigned));
-      s->srv.resident_used = &s->resident.used;
+    } else if ((!gram || rls_gram_resident_server_ok(op->dtype, op->N)) && (s->srv.ctl || server_ctl_optional(mem, &s->srv))) {
+      s->srv.resident_used = &s->resident.used;  // (both resident kernels can stay and listen)
     }
   }
-  int32_t st = alloc_scalars(ctx, &s->sc, &s->sc_h);
-  if (st != 0) {
-    dfree(s->y);
-    if (s->y1) dfree(s->y1);
-    if (s->res_raw) dfree(s->res_raw);
-    if (s->res_raw1) dfree(s->res_raw1);
-    if (s->scn) dfree(s->scn);
-    delete s;
-    return st;
+  alloc_scalars(mem, &s->sc, &s->sc_h);
+  if (const int e = mem.error()) {
+    rls_fista_destroy(s);
+    return rls_fail(ctx, e, "fista_create: hipMalloc failed");
   }
   *out = s;
   return 0;
@@ -3268,26 +3185,9 @@ int32_t rls_fista_destroy(rls_fista* s) {
   if (!s) return RLS_E_INVALID;
   if (rls_ctx_alive(s->actx, s->actx_id) && s->actx->server == &s->srv) rls_server_stop(s->actx);  // (a kernel of this plan left listening)
   hipSetDevice(s->device);
-  if (s->srv.ctl) hfree(s->srv.ctl);
   rls_alloc_scope alloc_scope(alloc_ctx_of(s->actx, s->actx_id));
   s->graph.drop();
-  dfree(s->y);
-  if (s->y1) dfree(s->y1);
-  if (s->res_raw) dfree(s->res_raw);
-  if (s->res_raw1) dfree(s->res_raw1);
-  if (s->scn) dfree(s->scn);
-  if (s->Ypack) dfree(s->Ypack);
-  if (s->Tpack) dfree(s->Tpack);
-  if (s->Vpart) dfree(s->Vpart);
-  if (s->scb_h) hfree(s->scb_h);
-  s->resident.release();
-  if (s->fk_yx) dfree(s->fk_yx);
-  if (s->fk_xx) dfree(s->fk_xx);
-  if (s->fk_dots) dfree(s->fk_dots);
-  if (s->tv_in) dfree(s->tv_in);
-  if (s->tv_out) dfree(s->tv_out);
-  dfree(s->sc);
-  hfree(s->sc_h);
+  s->mem.release();
   delete s;
   return 0;
 }
@@ -3332,11 +3232,16 @@ int32_t rls_fista_set_reg_tv(rls_fista* s, float lambda, int32_t ndims, const in
   if (!rls_tv_single_ok(s->op->ctx, s->op->dtype, ndims, shape, ntv, dims))
     return rls_fail(ctx, RLS_E_UNSUPPORTED, "fista_set_reg_tv: the image does not fit the single-workgroup FGP kernel; drive FISTA from the primitives");
   RLS_HIP(ctx, rls_enter(ctx));
-  if (!s->tv_in) {
+  if (!s->tv_in) {  // both or neither
     rls_alloc_scope alloc_scope(ctx);
     const size_t bytes = (size_t)s->op->N * rls_elem_size(s->op->dtype);
-    RLS_HIP(ctx, dmalloc(&s->tv_in, bytes));
-    RLS_HIP(ctx, dmalloc(&s->tv_out, bytes));
+    const plan_buffers::mark_t m = s->mem.mark();
+    s->mem.dev(&s->tv_in, bytes, false);
+    s->mem.dev(&s->tv_out, bytes, false);
+    if (const int e = s->mem.error()) {
+      s->mem.rollback(m);
+      return rls_fail(ctx, e, "fista_set_reg_tv: allocation failed");
+    }
   }
   // lambda, the geometry and iterationsTV are arguments of the captured FGP launch: a cached graph survives only an identical call
   bool same = s->reg_kind == RLS_REG_TV && s->lambda == lambda && s->tv_iters == iterations_tv && s->tv_ndims == ndims &&
@@ -3457,8 +3362,10 @@ int32_t rls_fista_create_batched(rls_operator* op, int32_t nrhs, void* x, void* 
       (op->G && !rls_skinny_ok(op->dtype, op->N, op->N, op->G, op->ldg)))
     return rls_fail(ctx, RLS_E_UNSUPPORTED, "batched FISTA needs A (and AHA, when explicit) with 16-aligned M, N (matrix-core path)");
   RLS_HIP(ctx, rls_enter(ctx));
+  *out = nullptr;
   rls_alloc_scope alloc_scope(ctx);
-  rls_fista* s = new rls_fista();
+  rls_fista* s = new rls_fista{plan_memory(ctx)};
+  plan_buffers& mem = s->mem;
   s->op = op;
   s->actx = ctx;
   s->actx_id = ctx->id;
@@ -3467,56 +3374,31 @@ int32_t rls_fista_create_batched(rls_operator* op, int32_t nrhs, void* x, void* 
   s->buf[1] = xold;
   s->x0 = x0;
   s->res = res;
-  s->y = s->y1 = s->res_raw = s->res_raw1 = nullptr;
-  s->scn = nullptr;
-  s->use_pipe = s->use_gram = false;
-  s->reg_kind = RLS_REG_L1;
-  s->proj_kind = RLS_PROJ_NONE;
-  s->lambda = 0.f;
-  s->l21_slices = 1;
-  s->initialised = false;
   s->nrhs = nrhs;
   s->ldv = ldv;
-  s->sc = s->sc_h = nullptr;
   size_t pb, tb, vb;
   rls_skinny_sizes(op->ctx, op->dtype, op->M, op->N, nrhs, &pb, &tb, &vb, &s->splits);
   s->half = rls_skinny_half(op->ctx, op->dtype, nrhs);
-  const size_t yb = (size_t)ldv * nrhs * rls_elem_size(op->dtype);
-  hipError_t e = dmalloc(&s->y, yb);
-  if (e == hipSuccess) e = dmalloc(&s->Ypack, pb);
-  if (e == hipSuccess) e = hipMemsetAsync(s->Ypack, 0, pb, ctx->stream);  // the padding columns of the last group stay zero
-  if (e == hipSuccess) e = dmalloc(&s->Tpack, tb);
-  if (e == hipSuccess) e = dmalloc(&s->Vpart, vb);
-  if (e == hipSuccess) e = dmalloc(&s->sc, sizeof(fista_scalars) * nrhs);
-  if (e == hipSuccess) e = hipMemsetAsync(s->sc, 0, sizeof(fista_scalars) * nrhs, ctx->stream);
-  if (e == hipSuccess) e = hmalloc(&s->scb_h, sizeof(fista_scalars) * nrhs);
-  if (e == hipSuccess) e = hmalloc(&s->sc_h, sizeof(fista_scalars));
+  mem.dev(&s->y, (size_t)ldv * nrhs * rls_elem_size(op->dtype), false);
+  mem.dev(&s->Ypack, pb, true);  // the padding columns of the last group stay zero
+  mem.dev(&s->Tpack, tb, false);
+  mem.dev(&s->Vpart, vb, false);
+  mem.dev(&s->sc, sizeof(fista_scalars) * nrhs, true);
+  mem.pinned(&s->scb_h, sizeof(fista_scalars) * nrhs, false);
+  mem.pinned(&s->sc_h, sizeof(fista_scalars), false);
   const bool vec16 = ldv % 2 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(xold) | reinterpret_cast<uintptr_t>(res)) & 15) == 0;
-  if (e == hipSuccess && op->G && s->half && vec16 && rls_fgramk_resident_ok(ctx, op->dtype, op->N, nrhs, op->G, op->ldg)) {
+  if (!mem.error() && op->G && s->half && vec16 && rls_fgramk_resident_ok(ctx, op->dtype, op->N, nrhs, op->G, op->ldg)) {
     size_t yxb, xxb, db;
     rls_fgramk_sizes(op->N, &yxb, &xxb, &db);
-    e = s->resident.alloc(ctx, op);
-    if (e == hipSuccess) e = dmalloc(&s->fk_yx, yxb);
-    if (e == hipSuccess) e = hipMemsetAsync(s->fk_yx, 0, yxb, ctx->stream);  // rows >= N are read, never written
-    if (e == hipSuccess) e = dmalloc(&s->fk_xx, xxb);
-    if (e == hipSuccess) e = dmalloc(&s->fk_dots, db);
-    if (e == hipSuccess) e = hipMemsetAsync(s->fk_dots, 0, db, ctx->stream);  // slots of absent workgroups add 0.0
-    s->fgramk = e == hipSuccess;
+    s->resident.alloc(mem, ctx, op);
+    mem.dev(&s->fk_yx, yxb, true);  // rows >= N are read, never written
+    mem.dev(&s->fk_xx, xxb, false);
+    mem.dev(&s->fk_dots, db, true);  // slots of absent workgroups add 0.0
+    s->fgramk = !mem.error();
   }
-  if (e != hipSuccess) {
-    s->resident.release();
-    if (s->fk_yx) dfree(s->fk_yx);
-    if (s->fk_xx) dfree(s->fk_xx);
-    if (s->fk_dots) dfree(s->fk_dots);
-    if (s->y) dfree(s->y);
-    if (s->Ypack) dfree(s->Ypack);
-    if (s->Tpack) dfree(s->Tpack);
-    if (s->Vpart) dfree(s->Vpart);
-    if (s->sc) dfree(s->sc);
-    if (s->scb_h) hfree(s->scb_h);
-    if (s->sc_h) hfree(s->sc_h);
-    delete s;
-    return rls_fail(ctx, (int32_t)e, "fista_create_batched: allocation failed");
+  if (const int e = mem.error()) {
+    rls_fista_destroy(s);
+    return rls_fail(ctx, e, "fista_create_batched: allocation failed");
   }
   *out = s;
   return 0;
@@ -3803,8 +3685,10 @@ int32_t rls_cg_create(rls_operator* op, void* u, void* r, void* c, rls_cg** out)
   rls_ctx* ctx = op->ctx;
   if (!u || !r || !c || !out) return rls_fail(ctx, RLS_E_INVALID, "cg_create: null pointer");
   RLS_HIP(ctx, rls_enter(ctx));
+  *out = nullptr;
   rls_alloc_scope alloc_scope(ctx);
-  rls_cg* s = new rls_cg();
+  rls_cg* s = new rls_cg{plan_memory(ctx)};
+  plan_buffers& mem = s->mem;
   s->op = op;
   s->actx = ctx;
   s->actx_id = ctx->id;
@@ -3812,60 +3696,44 @@ int32_t rls_cg_create(rls_operator* op, void* u, void* r, void* c, rls_cg** out)
   s->u = u;
   s->r = r;
   s->c = c;
-  s->r1 = s->p1 = nullptr;
-  s->dots = nullptr;
-  s->psc = s->pscn = s->psc_h = nullptr;
-  s->used_pipeline = false;
-  s->v1 = nullptr;
-  s->gdots = nullptr;
-  int32_t st = alloc_scalars(ctx, &s->sc, &s->sc_h);
-  if (st != 0) {
-    delete s;
-    return st;
-  }
+  alloc_scalars(mem, &s->sc, &s->sc_h);
   if (op->G && rls_gram_pipe_ok(op->dtype, op->N, op->G, op->ldg)) {
     const size_t vb = (size_t)op->N * rls_elem_size(op->dtype);
     const size_t nd = (size_t)2 * rls_gram_pipe_nwg(op->dtype, op->N) * 4 * sizeof(double);
-    hipError_t e = dmalloc(&s->r1, vb);
-    if (e == hipSuccess) e = dmalloc(&s->p1, vb);
-    if (e == hipSuccess) e = dmalloc(&s->v1, vb);
-    if (e == hipSuccess) e = hipMemsetAsync(s->v1, 0, vb, ctx->stream);
-    if (e == hipSuccess) e = dmalloc(&s->gdots, nd);
-    if (e == hipSuccess) e = hipMemsetAsync(s->gdots, 0, nd, ctx->stream);
-    if (e == hipSuccess) e = dmalloc(&s->pscn, sizeof(cgnr_scalars));
-    if (e == hipSuccess) e = hipMemsetAsync(s->pscn, 0, sizeof(cgnr_scalars), ctx->stream);
-    if (e != hipSuccess || alloc_scalars(ctx, &s->psc, &s->psc_h) != 0) {
-      rls_cg_destroy(s);
-      return rls_fail(ctx, (int32_t)e, "cg_create: hipMalloc failed");
-    }
-    if (rls_gram_resident_ok(ctx, op->dtype, op->N, op->G, op->ldg)) {
-      if (s->resident.alloc(ctx, op) == hipSuccess) {
-        s->gram_resident = true;
-      } else {
-        s->resident.release();  // an optimisation only: the one-launch-per-iteration pipeline runs without it
+    mem.dev(&s->r1, vb, false);
+    mem.dev(&s->p1, vb, false);
+    mem.dev(&s->v1, vb, true);
+    mem.dev(&s->gdots, nd, true);
+    mem.dev(&s->pscn, sizeof(cgnr_scalars), true);
+    alloc_scalars(mem, &s->psc, &s->psc_h);
+    if (!mem.error() && rls_gram_resident_ok(ctx, op->dtype, op->N, op->G, op->ldg)) {
+      const plan_buffers::mark_t m = mem.mark();
+      s->resident.alloc(mem, ctx, op);
+      s->gram_resident = !mem.error();
+      if (!s->gram_resident) {
+        mem.rollback(m);  // an optimisation only: the one-launch-per-iteration pipeline runs without it
         (void)hipGetLastError();
       }
     }
   } else if (op->slab) {
-    if (op->A && rls_cgnr_resident_ok(ctx, op->dtype, op->M, op->N, op->A, op->lda)) {
-      const size_t db = (size_t)rls_cgnr_resident_nwg(op->ctx, op->dtype, op->M, op->N) * 4 * sizeof(double);
-      if (s->resident.alloc(ctx, op) != hipSuccess || dmalloc(&s->rdots, db) != hipSuccess) {
-        s->resident.release();  // an optimisation only: the two-launch pipeline runs without it
+    if (!mem.error() && op->A && rls_cgnr_resident_ok(ctx, op->dtype, op->M, op->N, op->A, op->lda)) {
+      const plan_buffers::mark_t m = mem.mark();
+      s->resident.alloc(mem, ctx, op);
+      mem.dev(&s->rdots, (size_t)rls_cgnr_resident_nwg(op->ctx, op->dtype, op->M, op->N) * 4 * sizeof(double), false);
+      if (mem.error()) {
+        mem.rollback(m);  // an optimisation only: the two-launch pipeline runs without it
         (void)hipGetLastError();
       }
     }
-    const size_t vb = (size_t)op->N * rls_elem_size(op->dtype);
-    const size_t nd = (size_t)((op->N + 15) / 16) * 4 * sizeof(double);
-    hipError_t e = dmalloc(&s->r1, vb);
-    if (e == hipSuccess) e = dmalloc(&s->p1, vb);
-    if (e == hipSuccess) e = dmalloc(&s->dots, nd);
-    if (e == hipSuccess) e = hipMemsetAsync(s->dots, 0, nd, ctx->stream);
-    if (e == hipSuccess) e = dmalloc(&s->pscn, sizeof(cgnr_scalars));
-    if (e == hipSuccess) e = hipMemsetAsync(s->pscn, 0, sizeof(cgnr_scalars), ctx->stream);
-    if (e != hipSuccess || alloc_scalars(ctx, &s->psc, &s->psc_h) != 0) {
-      rls_cg_destroy(s);
-      return rls_fail(ctx, (int32_t)e, "cg_create: hipMalloc failed");
-    }
+    mem.dev(&s->r1, (size_t)op->N * rls_elem_size(op->dtype), false);
+    mem.dev(&s->p1, (size_t)op->N * rls_elem_size(op->dtype), false);
+    mem.dev(&s->dots, (size_t)((op->N + 15) / 16) * 4 * sizeof(double), true);
+    mem.dev(&s->pscn, sizeof(cgnr_scalars), true);
+    alloc_scalars(mem, &s->psc, &s->psc_h);
+  }
+  if (const int e = mem.error()) {
+    rls_cg_destroy(s);
+    return rls_fail(ctx, e, "cg_create: hipMalloc failed");
   }
   *out = s;
   return 0;
@@ -3881,8 +3749,10 @@ int32_t rls_cg_create_batched(rls_operator* op, int32_t nrhs, void* U, void* R, 
       (op->G && !rls_skinny_ok(op->dtype, op->N, op->N, op->G, op->ldg)))
     return rls_fail(ctx, RLS_E_UNSUPPORTED, "cg_create_batched: needs A (and AHA, when explicit) with M, N multiples of 16");
   RLS_HIP(ctx, rls_enter(ctx));
+  *out = nullptr;
   rls_alloc_scope alloc_scope(ctx);
-  rls_cg* s = new rls_cg();
+  rls_cg* s = new rls_cg{plan_memory(ctx)};
+  plan_buffers& mem = s->mem;
   s->op = op;
   s->actx = ctx;
   s->actx_id = ctx->id;
@@ -3890,25 +3760,18 @@ int32_t rls_cg_create_batched(rls_operator* op, int32_t nrhs, void* U, void* R, 
   s->u = U;
   s->r = R;
   s->c = Cm;
-  s->r1 = s->p1 = nullptr;
-  s->dots = nullptr;
-  s->psc = s->pscn = s->psc_h = nullptr;
-  s->used_pipeline = false;
-  s->v1 = nullptr;
-  s->gdots = nullptr;
-  s->sc = s->sc_h = nullptr;
   s->nrhs = nrhs;
   s->ldv = ldv;
   size_t pb, tb, vb;
   rls_skinny_sizes(op->ctx, op->dtype, op->M, op->N, nrhs, &pb, &tb, &vb, &s->splits);
   s->half = rls_skinny_half(op->ctx, op->dtype, nrhs);
-  hipError_t e = dmalloc(&s->Ppack, pb);
-  if (e == hipSuccess) e = hipMemsetAsync(s->Ppack, 0, pb, ctx->stream);  // the padding columns of the last group stay zero
-  if (e == hipSuccess) e = dmalloc(&s->Tpack, tb);
-  if (e == hipSuccess) e = dmalloc(&s->Vpart, vb);
-  if (e != hipSuccess || alloc_scalars(ctx, &s->sc, &s->sc_h, nrhs) != 0) {
+  mem.dev(&s->Ppack, pb, true);  // the padding columns of the last group stay zero
+  mem.dev(&s->Tpack, tb, false);
+  mem.dev(&s->Vpart, vb, false);
+  alloc_scalars(mem, &s->sc, &s->sc_h, nrhs);
+  if (const int e = mem.error()) {
     rls_cg_destroy(s);
-    return rls_fail(ctx, (int32_t)e, "cg_create_batched: allocation failed");
+    return rls_fail(ctx, e, "cg_create_batched: allocation failed");
   }
   *out = s;
   return 0;
@@ -3919,21 +3782,7 @@ int32_t rls_cg_destroy(rls_cg* s) {
   hipSetDevice(s->device);
   rls_alloc_scope alloc_scope(alloc_ctx_of(s->actx, s->actx_id));
   s->graph.drop();
-  if (s->Ppack) dfree(s->Ppack);
-  if (s->Tpack) dfree(s->Tpack);
-  if (s->Vpart) dfree(s->Vpart);
-  s->resident.release();
-  if (s->rdots) dfree(s->rdots);
-  if (s->r1) dfree(s->r1);
-  if (s->p1) dfree(s->p1);
-  if (s->dots) dfree(s->dots);
-  if (s->v1) dfree(s->v1);
-  if (s->gdots) dfree(s->gdots);
-  if (s->psc) dfree(s->psc);
-  if (s->pscn) dfree(s->pscn);
-  if (s->psc_h) hfree(s->psc_h);
-  if (s->sc) dfree(s->sc);
-  if (s->sc_h) hfree(s->sc_h);
+  s->mem.release();
   delete s;
   return 0;
 }
@@ -4005,10 +3854,11 @@ int32_t rls_cg_local_update(rls_cg* s, void* x) {
 // entry points rls_optista_update_async / rls_pogm_update_async; the plan owns what a resident launch needs on top: the
 // arrival counters and the N-vector of the flat exchange.
 struct rls_pgm {
-  rls_operator* op;
-  rls_ctx* actx;
+  plan_buffers mem;
+  rls_operator* op = nullptr;
+  rls_ctx* actx = nullptr;
   uint64_t actx_id = 0;
-  int device;
+  int device = 0;
   resident_slot resident;  // (`used` stays false: the caller asks rls_pgm_lost behind its launches)
   void* raw = nullptr;
 };
@@ -4021,19 +3871,17 @@ int32_t rls_pgm_create(rls_operator* op, rls_pgm** out) {
   if (!(op->slab && op->A && !op->G && rls_pgm_resident_ok(ctx, op->dtype, op->M, op->N, op->A, op->lda)))
     return RLS_E_UNSUPPORTED;  // (not an error state: the caller keeps its launch-per-iteration sequence)
   rls_alloc_scope alloc_scope(ctx);
-  rls_pgm* s = new rls_pgm();
+  rls_pgm* s = new rls_pgm{plan_memory(ctx)};
   s->op = op;
   s->actx = ctx;
   s->actx_id = ctx->id;
   s->device = ctx->device;
-  hipError_t e = s->resident.alloc(ctx, op);
-  if (e == hipSuccess) e = dmalloc(&s->raw, (size_t)op->N * rls_elem_size(op->dtype));
-  if (e != hipSuccess) {
-    s->resident.release();
-    if (s->raw) dfree(s->raw);
-    delete s;
+  s->resident.alloc(s->mem, ctx, op);
+  s->mem.dev(&s->raw, (size_t)op->N * rls_elem_size(op->dtype), false);
+  if (const int e = s->mem.error()) {
+    rls_pgm_destroy(s);
     (void)hipGetLastError();
-    return rls_fail(ctx, (int32_t)e, "pgm_create: hipMalloc failed");
+    return rls_fail(ctx, e, "pgm_create: hipMalloc failed");
   }
   *out = s;
   return 0;
@@ -4043,8 +3891,7 @@ int32_t rls_pgm_destroy(rls_pgm* s) {
   if (!s) return RLS_E_INVALID;
   hipSetDevice(s->device);
   rls_alloc_scope alloc_scope(alloc_ctx_of(s->actx, s->actx_id));
-  s->resident.release();
-  dfree(s->raw);
+  s->mem.release();
   delete s;
   return 0;
 }
@@ -4148,11 +3995,12 @@ int32_t rls_pgm_lost(rls_pgm* s, int32_t* lost, int32_t* fallbacks_total) {
 // product over an explicit AHA) on the matrix cores, then one workgroup per column (pgm.hip, pgmb_update_kernel).
 // ---------------------------------------------------------------------------------------------
 struct rls_pgm_batched {
-  rls_operator* op;
-  rls_ctx* actx;
+  plan_buffers mem;
+  rls_operator* op = nullptr;
+  rls_ctx* actx = nullptr;
   uint64_t actx_id = 0;
-  int device;
-  int kind;  // 0 = OptISTA, 1 = POGM
+  int device = 0;
+  int kind = 0;  // 0 = OptISTA, 1 = POGM
   rls_pgmb D;
   float *panel = nullptr, *Tpack = nullptr;
   void* Vpart = nullptr;
@@ -4196,7 +4044,7 @@ int32_t rls_pgm_create_batched(rls_operator* op, int32_t kind, int32_t nrhs, voi
     return rls_fail(ctx, RLS_E_UNSUPPORTED, "batched OptISTA / POGM needs A (and AHA, when explicit) with 16-aligned M, N (matrix-core path)");
   RLS_HIP(ctx, rls_enter(ctx));
   rls_alloc_scope alloc_scope(ctx);
-  rls_pgm_batched* s = new rls_pgm_batched();
+  rls_pgm_batched* s = new rls_pgm_batched{plan_memory(ctx)};
   s->op = op;
   s->actx = ctx;
   s->actx_id = ctx->id;
@@ -4205,22 +4053,15 @@ int32_t rls_pgm_create_batched(rls_operator* op, int32_t kind, int32_t nrhs, voi
   size_t pb, tb, vb;
   rls_skinny_sizes(ctx, op->dtype, op->M, op->N, nrhs, &pb, &tb, &vb, &s->splits);
   s->half = rls_skinny_half(ctx, op->dtype, nrhs);
-  hipError_t e = dmalloc(&s->panel, pb);
-  if (e == hipSuccess) e = hipMemsetAsync(s->panel, 0, pb, ctx->stream);  // the padding columns of the last group stay zero
-  if (e == hipSuccess) e = dmalloc(&s->Tpack, tb);
-  if (e == hipSuccess) e = dmalloc(&s->Vpart, vb);
-  if (e == hipSuccess) e = dmalloc(&s->sc, sizeof(pgmb_scalars) * nrhs);
-  if (e == hipSuccess) e = hipMemsetAsync(s->sc, 0, sizeof(pgmb_scalars) * nrhs, ctx->stream);
-  if (e == hipSuccess) e = hmalloc(&s->sc_h, sizeof(pgmb_scalars) * nrhs);
-  if (e != hipSuccess) {
-    if (s->panel) dfree(s->panel);
-    if (s->Tpack) dfree(s->Tpack);
-    if (s->Vpart) dfree(s->Vpart);
-    if (s->sc) dfree(s->sc);
-    if (s->sc_h) hfree(s->sc_h);
-    delete s;
+  s->mem.dev(&s->panel, pb, true);  // the padding columns of the last group stay zero
+  s->mem.dev(&s->Tpack, tb, false);
+  s->mem.dev(&s->Vpart, vb, false);
+  s->mem.dev(&s->sc, sizeof(pgmb_scalars) * nrhs, true);
+  s->mem.pinned(&s->sc_h, sizeof(pgmb_scalars) * nrhs, false);
+  if (const int e = s->mem.error()) {
+    rls_pgm_destroy_batched(s);
     (void)hipGetLastError();
-    return rls_fail(ctx, (int32_t)e, "pgm_create_batched: allocation failed");
+    return rls_fail(ctx, e, "pgm_create_batched: allocation failed");
   }
   rls_pgmb& D = s->D;
   D = rls_pgmb();
@@ -4254,11 +4095,7 @@ int32_t rls_pgm_destroy_batched(rls_pgm_batched* s) {
   hipSetDevice(s->device);
   rls_alloc_scope alloc_scope(alloc_ctx_of(s->actx, s->actx_id));
   s->graph.drop();
-  dfree(s->panel);
-  dfree(s->Tpack);
-  dfree(s->Vpart);
-  dfree(s->sc);
-  hfree(s->sc_h);
+  s->mem.release();
   delete s;
   return 0;
 }
@@ -4426,21 +4263,19 @@ int32_t rls_admm_create(rls_cg* cg, rls_admm** out) {
   if (!out) return rls_fail(ctx, RLS_E_INVALID, "admm_create: null out");
   RLS_HIP(ctx, rls_enter(ctx));
   rls_alloc_scope alloc_scope(ctx);
-  rls_admm* a = new rls_admm();
+  *out = nullptr;
+  rls_admm* a = new rls_admm{plan_memory(ctx)};
   a->cg = cg;
   a->actx = ctx;
   a->actx_id = ctx->id;
   a->device = ctx->device;
-  a->ready = false;
-  a->log = a->log_h = nullptr;
-  a->log_cap = 0;
-  a->enq = 0;
   a->nrhs = cg->nrhs;
-  const int32_t st = alloc_scalars(ctx, &a->sc, &a->sc_h, cg->nrhs);
-  if (st != 0) {
-    delete a;
-    return st;
+  alloc_scalars(a->mem, &a->sc, &a->sc_h, cg->nrhs);
+  if (const int e = a->mem.error()) {
+    rls_admm_destroy(a);
+    return rls_fail(ctx, e, "admm_create: allocation failed");
   }
+  a->log_mark = a->mem.mark();
   *out = a;
   return 0;
 }
@@ -4449,10 +4284,7 @@ int32_t rls_admm_destroy(rls_admm* a) {
   if (!a) return RLS_E_INVALID;
   hipSetDevice(a->device);
   rls_alloc_scope alloc_scope(alloc_ctx_of(a->actx, a->actx_id));
-  if (a->log) dfree(a->log);
-  if (a->log_h) hfree(a->log_h);
-  dfree(a->sc);
-  hfree(a->sc_h);
+  a->mem.release();
   delete a;
   return 0;
 }
@@ -4489,12 +4321,14 @@ int32_t rls_admm_init(rls_admm* a, const rls_admm_params* p) {
   rls_alloc_scope alloc_scope(ctx);
   const int cap = p->iterations > 0 ? p->iterations : 1;
   if (cap > a->log_cap) {
-    if (a->log) dfree(a->log);
-    if (a->log_h) hfree(a->log_h);
-    a->log = a->log_h = nullptr;
+    a->mem.rollback(a->log_mark);  // (the smaller log)
     a->log_cap = 0;
-    RLS_HIP(ctx, dmalloc(&a->log, sizeof(float) * ADMM_REC * cap * a->nrhs));
-    RLS_HIP(ctx, hmalloc(&a->log_h, sizeof(float) * ADMM_REC * cap * a->nrhs));
+    a->mem.dev(&a->log, sizeof(float) * ADMM_REC * cap * a->nrhs, false);
+    a->mem.pinned(&a->log_h, sizeof(float) * ADMM_REC * cap * a->nrhs, false);
+    if (const int e = a->mem.error()) {
+      a->mem.rollback(a->log_mark);
+      return rls_fail(ctx, e, "admm_init: allocation failed");
+    }
     a->log_cap = cap;
   }
   a->P = *p;
