@@ -114,8 +114,10 @@ int32_t reduce_dispatch(rls_ctx* ctx, int32_t dtype, int64_t n, const void* x, c
   if (!rls_dtype_ok(dtype) || n < 0 || (n > 0 && (!x || (OP == RED_DOTC && !y))) || !out_d)
     return rls_fail(ctx, RLS_E_INVALID, "reduction: bad argument");
   RLS_HIP(ctx, rls_enter(ctx));
-  if (dtype == RLS_F32) return reduce_launch<float, OP>(ctx, n, (const float*)x, (const float*)y, out_d);
-  return reduce_launch<float2, OP>(ctx, n, (const float2*)x, (const float2*)y, out_d);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return reduce_launch<E, OP>(ctx, n, (const E*)x, (const E*)y, out_d);
+  });
 }
 
 int32_t fetch_result(rls_ctx* ctx, float* result_h, int nfloats) {
@@ -131,12 +133,6 @@ int32_t fetch_result(rls_ctx* ctx, float* result_h, int nfloats) {
   if (n == 0) return 0;                                                                      \
   RLS_HIP(ctx, rls_enter(ctx));
 
-static int32_t ew_status(rls_ctx* ctx) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rls_fail(ctx, (int32_t)e, hipGetErrorString(e));
-  return 0;
-}
-
 }  // namespace
 
 // y = beta * y, with beta == 0 writing exact zeros (used by gemv for empty contractions)
@@ -150,35 +146,28 @@ extern "C" {
 int32_t rls_fill(rls_ctx* ctx, int32_t dtype, int64_t n, void* x, float re, float im) {
   EW_PRELUDE("fill");
   if (!x) return rls_fail(ctx, RLS_E_INVALID, "fill: null pointer");
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(fill_kernel<float>, dim3(ew_grid(n)), dim3(EW_THREADS), 0, ctx->stream, (float*)x, n, re);
-  else
-    hipLaunchKernelGGL(fill_kernel<float2>, dim3(ew_grid(n)), dim3(EW_THREADS), 0, ctx->stream, (float2*)x, n,
-                       make_float2(re, im));
-  return ew_status(ctx);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<fill_kernel<E>>(ctx, dim3(ew_grid(n)), dim3(EW_THREADS), 0, (E*)x, n, elem<E>::make(re, im));
+  });
 }
 
 int32_t rls_scal(rls_ctx* ctx, int32_t dtype, int64_t n, float a_re, float a_im, void* x) {
   EW_PRELUDE("scal");
   if (!x) return rls_fail(ctx, RLS_E_INVALID, "scal: null pointer");
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(scal_kernel<float>, dim3(ew_grid(n)), dim3(EW_THREADS), 0, ctx->stream, (float*)x, n, a_re);
-  else
-    hipLaunchKernelGGL(scal_kernel<float2>, dim3(ew_grid(n)), dim3(EW_THREADS), 0, ctx->stream, (float2*)x, n,
-                       make_float2(a_re, a_im));
-  return ew_status(ctx);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<scal_kernel<E>>(ctx, dim3(ew_grid(n)), dim3(EW_THREADS), 0, (E*)x, n, elem<E>::make(a_re, a_im));
+  });
 }
 
 int32_t rls_axpy(rls_ctx* ctx, int32_t dtype, int64_t n, float a_re, float a_im, const void* x, void* y) {
   EW_PRELUDE("axpy");
   if (!x || !y) return rls_fail(ctx, RLS_E_INVALID, "axpy: null pointer");
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(axpy_kernel<float>, dim3(ew_grid(n)), dim3(EW_THREADS), 0, ctx->stream, (float*)y,
-                       (const float*)x, n, a_re);
-  else
-    hipLaunchKernelGGL(axpy_kernel<float2>, dim3(ew_grid(n)), dim3(EW_THREADS), 0, ctx->stream, (float2*)y,
-                       (const float2*)x, n, make_float2(a_re, a_im));
-  return ew_status(ctx);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<axpy_kernel<E>>(ctx, dim3(ew_grid(n)), dim3(EW_THREADS), 0, (E*)y, (const E*)x, n, elem<E>::make(a_re, a_im));
+  });
 }
 
 int32_t rls_lincomb(rls_ctx* ctx, int32_t dtype, int64_t n, float a_re, float a_im, const void* x, float b_re,
@@ -188,23 +177,13 @@ int32_t rls_lincomb(rls_ctx* ctx, int32_t dtype, int64_t n, float a_re, float a_
   const bool has_y = (b_re != 0.f || b_im != 0.f);
   if (has_y && !y) return rls_fail(ctx, RLS_E_INVALID, "lincomb: null y");
   const dim3 g(ew_grid(n)), b(EW_THREADS);
-  if (dtype == RLS_F32) {
-    if (has_y)
-      hipLaunchKernelGGL((lincomb_kernel<float, true>), g, b, 0, ctx->stream, (float*)z, (const float*)x,
-                         (const float*)y, n, a_re, b_re);
-    else
-      hipLaunchKernelGGL((lincomb_kernel<float, false>), g, b, 0, ctx->stream, (float*)z, (const float*)x,
-                         (const float*)y, n, a_re, b_re);
-  } else {
-    const float2 a = make_float2(a_re, a_im), bb = make_float2(b_re, b_im);
-    if (has_y)
-      hipLaunchKernelGGL((lincomb_kernel<float2, true>), g, b, 0, ctx->stream, (float2*)z, (const float2*)x,
-                         (const float2*)y, n, a, bb);
-    else
-      hipLaunchKernelGGL((lincomb_kernel<float2, false>), g, b, 0, ctx->stream, (float2*)z, (const float2*)x,
-                         (const float2*)y, n, a, bb);
-  }
-  return ew_status(ctx);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return with_bool(has_y, [&](auto HAS_Y) {
+      return rls_launch<lincomb_kernel<E, HAS_Y>>(ctx, g, b, 0, (E*)z, (const E*)x, (const E*)y, n, elem<E>::make(a_re, a_im),
+                                                  elem<E>::make(b_re, b_im));
+    });
+  });
 }
 
 int32_t rls_axpby(rls_ctx* ctx, int32_t dtype, int64_t n, float a_re, float a_im, const void* x, float b_re,

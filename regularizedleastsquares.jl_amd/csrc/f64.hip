@@ -399,8 +399,10 @@ static int32_t d_reduce(rls_ctx* ctx, int32_t dtype, int64_t n, const void* x, c
   result_h[0] = result_h[1] = 0.0;
   if (n == 0) return 0;
   RLS_HIP(ctx, rls_enter(ctx));
-  if (dtype == RLS_F64) return d_reduce_launch<double, OP>(ctx, n, (const double*)x, (const double*)y, result_h);
-  return d_reduce_launch<double2, OP>(ctx, n, (const double2*)x, (const double2*)y, result_h);
+  return rls_with_elem64(dtype, [&](auto t) {
+    using D = typename decltype(t)::type;
+    return d_reduce_launch<D, OP>(ctx, n, (const D*)x, (const D*)y, result_h);
+  });
 }
 
 static bool dtv_make(int32_t ndims, const int64_t* shape, int32_t ntv, const int32_t* dims, dtv_geom* G) {
@@ -462,26 +464,26 @@ extern "C" {
 int32_t rls_fill_d(rls_ctx* ctx, int32_t dtype, int64_t n, void* x, double re, double im) {
   D_PRELUDE("fill_d");
   if (!x) return rls_fail(ctx, RLS_E_INVALID, "fill_d: null pointer");
-  if (dtype == RLS_F64) hipLaunchKernelGGL(d_fill_kernel<double>, dim3(dgrid(n)), dim3(DT), 0, ctx->stream, (double*)x, n, re);
-  else hipLaunchKernelGGL(d_fill_kernel<double2>, dim3(dgrid(n)), dim3(DT), 0, ctx->stream, (double2*)x, n, make_double2(re, im));
-  return d_status(ctx);
+  return rls_with_elem64(dtype, [&](auto t) {
+    using D = typename decltype(t)::type;
+    return rls_launch<d_fill_kernel<D>>(ctx, dim3(dgrid(n)), dim3(DT), 0, (D*)x, n, dp_make<D>(re, im));
+  });
 }
 int32_t rls_scal_d(rls_ctx* ctx, int32_t dtype, int64_t n, double a_re, double a_im, void* x) {
   D_PRELUDE("scal_d");
   if (!x) return rls_fail(ctx, RLS_E_INVALID, "scal_d: null pointer");
-  if (dtype == RLS_F64) hipLaunchKernelGGL(d_scal_kernel<double>, dim3(dgrid(n)), dim3(DT), 0, ctx->stream, (double*)x, n, a_re);
-  else hipLaunchKernelGGL(d_scal_kernel<double2>, dim3(dgrid(n)), dim3(DT), 0, ctx->stream, (double2*)x, n, make_double2(a_re, a_im));
-  return d_status(ctx);
+  return rls_with_elem64(dtype, [&](auto t) {
+    using D = typename decltype(t)::type;
+    return rls_launch<d_scal_kernel<D>>(ctx, dim3(dgrid(n)), dim3(DT), 0, (D*)x, n, dp_make<D>(a_re, a_im));
+  });
 }
 int32_t rls_axpy_d(rls_ctx* ctx, int32_t dtype, int64_t n, double a_re, double a_im, const void* x, void* y) {
   D_PRELUDE("axpy_d");
   if (!x || !y) return rls_fail(ctx, RLS_E_INVALID, "axpy_d: null pointer");
-  if (dtype == RLS_F64)
-    hipLaunchKernelGGL(d_axpy_kernel<double>, dim3(dgrid(n)), dim3(DT), 0, ctx->stream, (double*)y, (const double*)x, n, a_re);
-  else
-    hipLaunchKernelGGL(d_axpy_kernel<double2>, dim3(dgrid(n)), dim3(DT), 0, ctx->stream, (double2*)y, (const double2*)x, n,
-                       make_double2(a_re, a_im));
-  return d_status(ctx);
+  return rls_with_elem64(dtype, [&](auto t) {
+    using D = typename decltype(t)::type;
+    return rls_launch<d_axpy_kernel<D>>(ctx, dim3(dgrid(n)), dim3(DT), 0, (D*)y, (const D*)x, n, dp_make<D>(a_re, a_im));
+  });
 }
 int32_t rls_lincomb_d(rls_ctx* ctx, int32_t dtype, int64_t n, double a_re, double a_im, const void* x, double b_re, double b_im,
                       const void* y, void* z) {
@@ -490,15 +492,13 @@ int32_t rls_lincomb_d(rls_ctx* ctx, int32_t dtype, int64_t n, double a_re, doubl
   const bool has_y = b_re != 0.0 || b_im != 0.0;
   if (has_y && !y) return rls_fail(ctx, RLS_E_INVALID, "lincomb_d: null y");
   const dim3 g(dgrid(n)), b(DT);
-  if (dtype == RLS_F64) {
-    if (has_y) hipLaunchKernelGGL((d_lincomb_kernel<double, true>), g, b, 0, ctx->stream, (double*)z, (const double*)x, (const double*)y, n, a_re, b_re);
-    else hipLaunchKernelGGL((d_lincomb_kernel<double, false>), g, b, 0, ctx->stream, (double*)z, (const double*)x, (const double*)y, n, a_re, b_re);
-  } else {
-    const double2 a = make_double2(a_re, a_im), bb = make_double2(b_re, b_im);
-    if (has_y) hipLaunchKernelGGL((d_lincomb_kernel<double2, true>), g, b, 0, ctx->stream, (double2*)z, (const double2*)x, (const double2*)y, n, a, bb);
-    else hipLaunchKernelGGL((d_lincomb_kernel<double2, false>), g, b, 0, ctx->stream, (double2*)z, (const double2*)x, (const double2*)y, n, a, bb);
-  }
-  return d_status(ctx);
+  return rls_with_elem64(dtype, [&](auto t) {
+    using D = typename decltype(t)::type;
+    return with_bool(has_y, [&](auto HAS_Y) {
+      return rls_launch<d_lincomb_kernel<D, HAS_Y>>(ctx, g, b, 0, (D*)z, (const D*)x, (const D*)y, n, dp_make<D>(a_re, a_im),
+                                                    dp_make<D>(b_re, b_im));
+    });
+  });
 }
 int32_t rls_nrm2_d(rls_ctx* ctx, int32_t dtype, int64_t n, const void* x, double* result_h) {
   return d_reduce<DRED_NRM2>(ctx, dtype, n, x, nullptr, result_h, "nrm2_d: bad argument");
@@ -521,57 +521,56 @@ int32_t rls_gemv_d(rls_ctx* ctx, int32_t dtype, int32_t op, int64_t M, int64_t N
   RLS_HIP(ctx, rls_enter(ctx));
   const int bz = beta_re == 0.0 && beta_im == 0.0;
   if (nin == 0) return bz ? rls_fill_d(ctx, dtype, nout, y, 0.0, 0.0) : rls_scal_d(ctx, dtype, nout, beta_re, beta_im, y);
-  if (dtype == RLS_F64) {
+  return rls_with_elem64(dtype, [&](auto t) {
+    using D = typename decltype(t)::type;
+    const D al = dp_make<D>(alpha_re, alpha_im), be = dp_make<D>(beta_re, beta_im);
     if (op == RLS_OP_N)
-      hipLaunchKernelGGL(d_gemv_n_kernel<double>, dim3((unsigned)((M + 63) / 64)), dim3(256), 0, ctx->stream, (const double*)A, lda,
-                         (const double*)x, (double*)y, M, N, alpha_re, beta_re, bz);
-    else
-      hipLaunchKernelGGL((d_gemv_t_kernel<double, false>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, ctx->stream, (const double*)A, lda,
-                         (const double*)x, (double*)y, M, N, alpha_re, beta_re, bz);
-  } else {
-    const double2 al = make_double2(alpha_re, alpha_im), be = make_double2(beta_re, beta_im);
-    if (op == RLS_OP_N)
-      hipLaunchKernelGGL(d_gemv_n_kernel<double2>, dim3((unsigned)((M + 63) / 64)), dim3(256), 0, ctx->stream, (const double2*)A, lda,
-                         (const double2*)x, (double2*)y, M, N, al, be, bz);
-    else if (op == RLS_OP_T)
-      hipLaunchKernelGGL((d_gemv_t_kernel<double2, false>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, ctx->stream, (const double2*)A,
-                         lda, (const double2*)x, (double2*)y, M, N, al, be, bz);
-    else
-      hipLaunchKernelGGL((d_gemv_t_kernel<double2, true>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, ctx->stream, (const double2*)A,
-                         lda, (const double2*)x, (double2*)y, M, N, al, be, bz);
-  }
-  return d_status(ctx);
+      return rls_launch<d_gemv_n_kernel<D>>(ctx, dim3((unsigned)((M + 63) / 64)), dim3(256), 0, (const D*)A, lda, (const D*)x, (D*)y,
+                                            M, N, al, be, bz);
+    auto gemv_t = [&](auto HERM) {
+      return rls_launch<d_gemv_t_kernel<D, HERM>>(ctx, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (const D*)A, lda, (const D*)x,
+                                                  (D*)y, M, N, al, be, bz);
+    };
+    if constexpr (std::is_same_v<D, double2>) {  // the conjugating instantiation exists for the complex type only
+      if (op == RLS_OP_C) return gemv_t(std::true_type{});
+    }
+    return gemv_t(std::false_type{});
+  });
 }
 
 int32_t rls_prox_l1_d(rls_ctx* ctx, int32_t dtype, int64_t n, void* x, double lambda) {
   D_PRELUDE("prox_l1_d");
   if (!x) return rls_fail(ctx, RLS_E_INVALID, "prox_l1_d: null pointer");
-  if (dtype == RLS_F64) hipLaunchKernelGGL(d_prox_l1_kernel<double>, dim3(dgrid(n)), dim3(DT), 0, ctx->stream, (double*)x, n, lambda);
-  else hipLaunchKernelGGL(d_prox_l1_kernel<double2>, dim3(dgrid(n)), dim3(DT), 0, ctx->stream, (double2*)x, n, lambda);
-  return d_status(ctx);
+  return rls_with_elem64(dtype, [&](auto t) {
+    using D = typename decltype(t)::type;
+    return rls_launch<d_prox_l1_kernel<D>>(ctx, dim3(dgrid(n)), dim3(DT), 0, (D*)x, n, lambda);
+  });
 }
 int32_t rls_prox_l2_d(rls_ctx* ctx, int32_t dtype, int64_t n, void* x, double lambda) {
   D_PRELUDE("prox_l2_d");
   if (!x) return rls_fail(ctx, RLS_E_INVALID, "prox_l2_d: null pointer");
   const double factor = 1.0 / (1.0 + 2.0 * lambda);
-  if (dtype == RLS_F64) hipLaunchKernelGGL(d_prox_l2_kernel<double>, dim3(dgrid(n)), dim3(DT), 0, ctx->stream, (double*)x, n, factor);
-  else hipLaunchKernelGGL(d_prox_l2_kernel<double2>, dim3(dgrid(n)), dim3(DT), 0, ctx->stream, (double2*)x, n, factor);
-  return d_status(ctx);
+  return rls_with_elem64(dtype, [&](auto t) {
+    using D = typename decltype(t)::type;
+    return rls_launch<d_prox_l2_kernel<D>>(ctx, dim3(dgrid(n)), dim3(DT), 0, (D*)x, n, factor);
+  });
 }
 int32_t rls_prox_l21_d(rls_ctx* ctx, int32_t dtype, int64_t n, int64_t slices, void* x, double lambda) {
   D_PRELUDE("prox_l21_d");
   if (!x || slices <= 0 || n / slices == 0) return rls_fail(ctx, RLS_E_INVALID, "prox_l21_d: bad argument");
   const int64_t slen = n / slices;
-  if (dtype == RLS_F64) hipLaunchKernelGGL(d_l21_kernel<double>, dim3(dgrid(slen)), dim3(DT), 0, ctx->stream, (double*)x, n, slen, lambda);
-  else hipLaunchKernelGGL(d_l21_kernel<double2>, dim3(dgrid(slen)), dim3(DT), 0, ctx->stream, (double2*)x, n, slen, lambda);
-  return d_status(ctx);
+  return rls_with_elem64(dtype, [&](auto t) {
+    using D = typename decltype(t)::type;
+    return rls_launch<d_l21_kernel<D>>(ctx, dim3(dgrid(slen)), dim3(DT), 0, (D*)x, n, slen, lambda);
+  });
 }
 int32_t rls_prox_positive_d(rls_ctx* ctx, int32_t dtype, int64_t n, void* x) {
   D_PRELUDE("prox_positive_d");
   if (!x) return rls_fail(ctx, RLS_E_INVALID, "prox_positive_d: null pointer");
-  if (dtype == RLS_F64) hipLaunchKernelGGL((d_project_kernel<double, true>), dim3(dgrid(n)), dim3(DT), 0, ctx->stream, (double*)x, n);
-  else hipLaunchKernelGGL((d_project_kernel<double2, true>), dim3(dgrid(n)), dim3(DT), 0, ctx->stream, (double2*)x, n);
-  return d_status(ctx);
+  return rls_with_elem64(dtype, [&](auto t) {
+    using D = typename decltype(t)::type;
+    return rls_launch<d_project_kernel<D, true>>(ctx, dim3(dgrid(n)), dim3(DT), 0, (D*)x, n);
+  });
 }
 int32_t rls_prox_real_d(rls_ctx* ctx, int32_t dtype, int64_t n, void* x) {
   D_PRELUDE("prox_real_d");
@@ -587,8 +586,10 @@ int32_t rls_prox_tv_fgp_d(rls_ctx* ctx, int32_t dtype, int32_t ndims, const int6
   if (!d_dtype_ok(dtype) || !x || iterations < 0 || !dtv_make(ndims, shape, ntv, dims, &G))
     return rls_fail(ctx, RLS_E_INVALID, "prox_tv_fgp_d: bad argument");
   RLS_HIP(ctx, rls_enter(ctx));
-  if (dtype == RLS_F64) return d_fgp<double>(ctx, G, (double*)x, lambda, iterations);
-  return d_fgp<double2>(ctx, G, (double2*)x, lambda, iterations);
+  return rls_with_elem64(dtype, [&](auto t) {
+    using D = typename decltype(t)::type;
+    return d_fgp<D>(ctx, G, (D*)x, lambda, iterations);
+  });
 }
 
 int32_t rls_transpose_d(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* A, int64_t lda, void* At, int64_t ldat) {
@@ -596,27 +597,28 @@ int32_t rls_transpose_d(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const
   if (!d_dtype_ok(dtype) || M <= 0 || N <= 0 || !A || !At || lda < M || ldat < N) return rls_fail(ctx, RLS_E_INVALID, "transpose_d: bad argument");
   RLS_HIP(ctx, rls_enter(ctx));
   const dim3 grid((unsigned)((M + 31) / 32), (unsigned)((N + 31) / 32));
-  if (dtype == RLS_F64) hipLaunchKernelGGL(d_transpose_kernel<double>, grid, dim3(256), 0, ctx->stream, (const double*)A, lda, (double*)At, ldat, M, N);
-  else hipLaunchKernelGGL(d_transpose_kernel<double2>, grid, dim3(256), 0, ctx->stream, (const double2*)A, lda, (double2*)At, ldat, M, N);
-  return d_status(ctx);
+  return rls_with_elem64(dtype, [&](auto t) {
+    using D = typename decltype(t)::type;
+    return rls_launch<d_transpose_kernel<D>>(ctx, grid, dim3(256), 0, (const D*)A, lda, (D*)At, ldat, M, N);
+  });
 }
 int32_t rls_rownorm2_d(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* A, int64_t lda, double* out_d) {
   RLS_CHECK_CTX(ctx);
   if (!d_dtype_ok(dtype) || M <= 0 || N <= 0 || !A || !out_d || lda < M) return rls_fail(ctx, RLS_E_INVALID, "rownorm2_d: bad argument");
   RLS_HIP(ctx, rls_enter(ctx));
-  if (dtype == RLS_F64) hipLaunchKernelGGL(d_rownorm2_kernel<double>, dim3(dgrid(M)), dim3(DT), 0, ctx->stream, (const double*)A, lda, M, N, out_d);
-  else hipLaunchKernelGGL(d_rownorm2_kernel<double2>, dim3(dgrid(M)), dim3(DT), 0, ctx->stream, (const double2*)A, lda, M, N, out_d);
-  return d_status(ctx);
+  return rls_with_elem64(dtype, [&](auto t) {
+    using D = typename decltype(t)::type;
+    return rls_launch<d_rownorm2_kernel<D>>(ctx, dim3(dgrid(M)), dim3(DT), 0, (const D*)A, lda, M, N, out_d);
+  });
 }
 int32_t rls_scale_rows_d(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* w, const void* A, int64_t lda, void* B, int64_t ldb) {
   RLS_CHECK_CTX(ctx);
   if (!d_dtype_ok(dtype) || M <= 0 || N <= 0 || !w || !A || !B || lda < M || ldb < M) return rls_fail(ctx, RLS_E_INVALID, "scale_rows_d: bad argument");
   RLS_HIP(ctx, rls_enter(ctx));
-  if (dtype == RLS_F64)
-    hipLaunchKernelGGL(d_scale_rows_kernel<double>, dim3(dgrid(M * N)), dim3(DT), 0, ctx->stream, (const double*)w, (const double*)A, lda, (double*)B, ldb, M, N);
-  else
-    hipLaunchKernelGGL(d_scale_rows_kernel<double2>, dim3(dgrid(M * N)), dim3(DT), 0, ctx->stream, (const double2*)w, (const double2*)A, lda, (double2*)B, ldb, M, N);
-  return d_status(ctx);
+  return rls_with_elem64(dtype, [&](auto t) {
+    using D = typename decltype(t)::type;
+    return rls_launch<d_scale_rows_kernel<D>>(ctx, dim3(dgrid(M * N)), dim3(DT), 0, (const D*)w, (const D*)A, lda, (D*)B, ldb, M, N);
+  });
 }
 int32_t rls_kaczmarz_solve_d(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* At, int64_t ldat, int32_t nrhs, void* X,
                              int64_t ldx, const void* U, int64_t ldu, void* VL, int64_t ldvl, const int32_t* rows_d, const double* denom_d,
@@ -633,15 +635,12 @@ int32_t rls_kaczmarz_solve_d(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, 
     return rls_fail(ctx, RLS_E_UNSUPPORTED, "kaczmarz_solve_d: switched off (rls_tune_set kaczmarz_fused = 0)");
   if (nused == 0 || n_sweeps == 0) return 0;
   RLS_HIP(ctx, rls_enter(ctx));
-  if (dtype == RLS_F64)
-    hipLaunchKernelGGL(d_kaczmarz_kernel<double>, dim3((unsigned)nrhs), dim3(1024), 0, ctx->stream, (const double*)At, ldat, (double*)X, ldx,
-                       (const double*)U, ldu, (double*)VL, ldvl, rows_d, denom_d, nused, n_sweeps, order_stride, eps_w, proj_kind, reg_kind,
-                       reg_lambda, N);
-  else
-    hipLaunchKernelGGL(d_kaczmarz_kernel<double2>, dim3((unsigned)nrhs), dim3(1024), 0, ctx->stream, (const double2*)At, ldat, (double2*)X, ldx,
-                       (const double2*)U, ldu, (double2*)VL, ldvl, rows_d, denom_d, nused, n_sweeps, order_stride, eps_w, proj_kind, reg_kind,
-                       reg_lambda, N);
-  return d_status(ctx);
+  return rls_with_elem64(dtype, [&](auto t) {
+    using D = typename decltype(t)::type;
+    return rls_launch<d_kaczmarz_kernel<D>>(ctx, dim3((unsigned)nrhs), dim3(1024), 0, (const D*)At, ldat, (D*)X, ldx, (const D*)U, ldu,
+                                            (D*)VL, ldvl, rows_d, denom_d, nused, n_sweeps, order_stride, eps_w, proj_kind, reg_kind,
+                                            reg_lambda, N);
+  });
 }
 int32_t rls_kaczmarz_sweep_d(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* At, int64_t ldat, int32_t nrhs, void* X,
                              int64_t ldx, const void* U, int64_t ldu, void* VL, int64_t ldvl, const int32_t* rows_d, const double* denom_d,

@@ -378,8 +378,8 @@ int32_t rls_launch_gemv(rls_ctx* ctx, int32_t dtype, int32_t op, int64_t M, int6
     return rls_launch_scale_or_zero(ctx, dtype, ny, br, bi, y);
   }
   RLS_HIP(ctx, rls_enter(ctx));
-  if (dtype == RLS_F32)
-    return gemv_typed<float>(ctx, op, M, N, ar, br, (const float*)A, lda, (const float*)x, (float*)y, skip);
-  return gemv_typed<float2>(ctx, op, M, N, make_float2(ar, ai), make_float2(br, bi), (const float2*)A, lda,
-                            (const float2*)x, (float2*)y, skip);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return gemv_typed<E>(ctx, op, M, N, elem<E>::make(ar, ai), elem<E>::make(br, bi), (const E*)A, lda, (const E*)x, (E*)y, skip);
+  });
 }

@@ -399,13 +399,10 @@ int32_t rls_transpose(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const v
     return rls_fail(ctx, RLS_E_INVALID, "transpose: bad argument");
   RLS_HIP(ctx, rls_enter(ctx));
   const dim3 grid((unsigned)((M + 31) / 32), (unsigned)((N + 31) / 32));
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(transpose_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float*)A, lda, (float*)At, ldat,
-                       M, N);
-  else
-    hipLaunchKernelGGL(transpose_kernel<float2>, grid, dim3(256), 0, ctx->stream, (const float2*)A, lda, (float2*)At,
-                       ldat, M, N);
-  return kz_status(ctx);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<transpose_kernel<E>>(ctx, grid, dim3(256), 0, (const E*)A, lda, (E*)At, ldat, M, N);
+  });
 }
 
 int32_t rls_kaczmarz_solve(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* At, int64_t ldat,
@@ -424,7 +421,7 @@ int32_t rls_kaczmarz_solve(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, co
     return rls_fail(ctx, RLS_E_UNSUPPORTED, "kaczmarz_solve: switched off (rls_tune_set kaczmarz_fused = 0)");
   if (nused == 0 || n_sweeps == 0) return 0;
   RLS_HIP(ctx, rls_enter(ctx));
-  const int V = dtype == RLS_C32 ? 2 : 4;
+  const int V = rls_with_elem(dtype, [](auto t) { return elem<typename decltype(t)::type>::vec; });
   const bool vec = (N % V == 0) && (ldat % V == 0) && (ldx % V == 0) && ((uintptr_t)At % 16 == 0) &&
                    ((uintptr_t)X % 16 == 0);
   // several sweeps in one launch: the pipeline may prefetch vl[row] of the next sweep before this sweep's update of
@@ -435,18 +432,12 @@ int32_t rls_kaczmarz_solve(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, co
   for (int done = 0; done < n_sweeps; done += per_launch) {
     const kz_args a{rows_d + (int64_t)done * order_stride, denom_d + (int64_t)done * order_stride, nused, per_launch,
                     order_stride, eps_w, proj_kind, reg_kind, reg_lambda};
-    int32_t st;
-    if (dtype == RLS_F32)
-      st = vec ? kz_launch<float, true>(ctx, N, (const float*)At, ldat, nrhs, (float*)X, ldx, (const float*)U, ldu,
-                                        (float*)VL, ldvl, a)
-               : kz_launch<float, false>(ctx, N, (const float*)At, ldat, nrhs, (float*)X, ldx, (const float*)U, ldu,
-                                         (float*)VL, ldvl, a);
-    else
-      st = vec ? kz_launch<float2, true>(ctx, N, (const float2*)At, ldat, nrhs, (float2*)X, ldx, (const float2*)U, ldu,
-                                         (float2*)VL, ldvl, a)
-               : kz_launch<float2, false>(ctx, N, (const float2*)At, ldat, nrhs, (float2*)X, ldx, (const float2*)U,
-                                          ldu, (float2*)VL, ldvl, a);
-    if (st != 0) return st;
+    RLS_TRY(rls_with_elem(dtype, [&](auto t) {
+      using E = typename decltype(t)::type;
+      return with_bool(vec, [&](auto VEC) {
+        return kz_launch<E, VEC>(ctx, N, (const E*)At, ldat, nrhs, (E*)X, ldx, (const E*)U, ldu, (E*)VL, ldvl, a);
+      });
+    }));
   }
   return 0;
 }

@@ -157,11 +157,10 @@ int32_t rls_gather(rls_ctx* ctx, int32_t dtype, int64_t m, const int32_t* idx, c
   if (!rls_dtype_ok(dtype) || m < 0 || (m > 0 && (!idx || !x || !out))) return rls_fail(ctx, RLS_E_INVALID, "gather: bad argument");
   if (m == 0) return 0;
   RLS_HIP(ctx, rls_enter(ctx));
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(gather_kernel<float>, dim3(ns_grid(m)), dim3(NS_THREADS), 0, ctx->stream, idx, m, (const float*)x, (float*)out);
-  else
-    hipLaunchKernelGGL(gather_kernel<float2>, dim3(ns_grid(m)), dim3(NS_THREADS), 0, ctx->stream, idx, m, (const float2*)x, (float2*)out);
-  return ns_status(ctx);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<gather_kernel<E>>(ctx, dim3(ns_grid(m)), dim3(NS_THREADS), 0, idx, m, (const E*)x, (E*)out);
+  });
 }
 
 int32_t rls_scatter(rls_ctx* ctx, int32_t dtype, int64_t m, const int32_t* idx, const void* in, void* x) {
@@ -169,11 +168,10 @@ int32_t rls_scatter(rls_ctx* ctx, int32_t dtype, int64_t m, const int32_t* idx, 
   if (!rls_dtype_ok(dtype) || m < 0 || (m > 0 && (!idx || !x || !in))) return rls_fail(ctx, RLS_E_INVALID, "scatter: bad argument");
   if (m == 0) return 0;
   RLS_HIP(ctx, rls_enter(ctx));
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(scatter_kernel<float>, dim3(ns_grid(m)), dim3(NS_THREADS), 0, ctx->stream, idx, m, (const float*)in, (float*)x);
-  else
-    hipLaunchKernelGGL(scatter_kernel<float2>, dim3(ns_grid(m)), dim3(NS_THREADS), 0, ctx->stream, idx, m, (const float2*)in, (float2*)x);
-  return ns_status(ctx);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<scatter_kernel<E>>(ctx, dim3(ns_grid(m)), dim3(NS_THREADS), 0, idx, m, (const E*)in, (E*)x);
+  });
 }
 
 int32_t rls_stats(rls_ctx* ctx, int32_t dtype, int64_t n, const void* x, double* out_h) {
@@ -184,10 +182,10 @@ int32_t rls_stats(rls_ctx* ctx, int32_t dtype, int64_t n, const void* x, double*
   const int cap = RLS_RED_SLOTS / NSTAT - 1;
   if (nwg > cap) nwg = cap;
   double* fin = ctx->red_d + (size_t)NSTAT * cap;  // last record of the scratch block
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(stats_kernel<float>, dim3(nwg), dim3(1024), 0, ctx->stream, (const float*)x, n, ctx->red_d);
-  else
-    hipLaunchKernelGGL(stats_kernel<float2>, dim3(nwg), dim3(1024), 0, ctx->stream, (const float2*)x, n, ctx->red_d);
+  rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    hipLaunchKernelGGL(stats_kernel<E>, dim3(nwg), dim3(1024), 0, ctx->stream, (const E*)x, n, ctx->red_d);
+  });
   hipLaunchKernelGGL(stats_final_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->red_d, nwg, fin);
   RLS_TRY(ns_status(ctx));
   RLS_HIP(ctx, hipMemcpyAsync(out_h, fin, sizeof(double) * NSTAT, hipMemcpyDeviceToHost, ctx->stream));

@@ -4424,64 +4424,60 @@ static bool pgm_resident_ok_typed(const rls_tuning& T, int device, int64_t M, in
 }  // namespace
 
 int32_t rls_fista_gram_iteration(rls_ctx* ctx, int32_t dtype, const rls_fista_gram& P, int parity) {
-  if (dtype == RLS_F32) return fista_gram_iteration_typed<float>(ctx, P, parity & 1);
-  return fista_gram_iteration_typed<float2>(ctx, P, parity & 1);
+  return rls_with_elem(dtype, [&](auto t) { return fista_gram_iteration_typed<typename decltype(t)::type>(ctx, P, parity & 1); });
 }
 int32_t rls_fista_gram_finish(rls_ctx* ctx, int32_t dtype, const rls_fista_gram& P, int parity) {
-  if (dtype == RLS_F32) return fista_gram_finish_typed<float>(ctx, P, parity & 1);
-  return fista_gram_finish_typed<float2>(ctx, P, parity & 1);
+  return rls_with_elem(dtype, [&](auto t) { return fista_gram_finish_typed<typename decltype(t)::type>(ctx, P, parity & 1); });
 }
 
 int rls_gram_pipe_nwg(int32_t dtype, int64_t N) {
-  const int V = dtype == RLS_C32 ? 2 : 4;
+  const int V = rls_with_elem(dtype, [](auto t) { return elem<typename decltype(t)::type>::vec; });
   const int64_t Mc = N / V;
   return (int)((Mc + 3) / 4);
 }
 bool rls_gram_pipe_ok(int32_t dtype, int64_t N, const void* G, int64_t ldg) {
-  const int V = dtype == RLS_C32 ? 2 : 4;
+  const int V = rls_with_elem(dtype, [](auto t) { return elem<typename decltype(t)::type>::vec; });
   if (!G || N <= 0 || N % V || ldg % V || (reinterpret_cast<uintptr_t>(G) % 16)) return false;
   if (N > 32 * 128 || N > 4 * FIN_THREADS) return false;
   if (rls_gram_pipe_nwg(dtype, N) > 512) return false;  // the partial dots are summed one per thread (NT = 512)
-  return 128 * ldg * (int64_t)(dtype == RLS_C32 ? 8 : 4) + (N / V) * 16 < (int64_t)0xffffffffll;
+  return 128 * ldg * (int64_t)rls_elem_size(dtype) + (N / V) * 16 < (int64_t)0xffffffffll;
 }
 int32_t rls_gram_pipe_iteration(rls_ctx* ctx, int32_t dtype, const rls_gram_pipe& P, int parity) {
-  if (dtype == RLS_F32) return gram_iteration_typed<float>(ctx, P, parity & 1);
-  return gram_iteration_typed<float2>(ctx, P, parity & 1);
+  return rls_with_elem(dtype, [&](auto t) { return gram_iteration_typed<typename decltype(t)::type>(ctx, P, parity & 1); });
 }
 int32_t rls_gram_pipe_finish(rls_ctx* ctx, int32_t dtype, const rls_gram_pipe& P, int parity) {
-  if (dtype == RLS_F32) return gram_finish_typed<float>(ctx, P, parity & 1);
-  return gram_finish_typed<float2>(ctx, P, parity & 1);
+  return rls_with_elem(dtype, [&](auto t) { return gram_finish_typed<typename decltype(t)::type>(ctx, P, parity & 1); });
 }
 
 int32_t rls_fista_gram_resident_launch(rls_ctx* ctx, int32_t dtype, const rls_fista_gram& P, void* sync, int n_steps,
                                        unsigned spin_limit, const rls_srv_args& Sv) {
-  if (dtype == RLS_F32) return fista_gram_resident_typed<float>(ctx, P, sync, n_steps, spin_limit, Sv);
-  return fista_gram_resident_typed<float2>(ctx, P, sync, n_steps, spin_limit, Sv);
+  return rls_with_elem(dtype, [&](auto t) {
+    return fista_gram_resident_typed<typename decltype(t)::type>(ctx, P, sync, n_steps, spin_limit, Sv);
+  });
 }
 bool rls_gram_resident_ok(rls_ctx* ctx, int32_t dtype, int64_t N, const void* G, int64_t ldg) {
   if (!rls_gram_pipe_ok(dtype, N, G, ldg)) return false;
-  return dtype == RLS_F32 ? gram_resident_ok_typed<float>(ctx->device, N) : gram_resident_ok_typed<float2>(ctx->device, N);
+  return rls_with_elem(dtype, [&](auto t) { return gram_resident_ok_typed<typename decltype(t)::type>(ctx->device, N); });
 }
 // shapes whose resident Gram kernel has a listening (server mode) instantiation: every one but the 32-columns-per-row-piece slabs
 bool rls_gram_resident_server_ok(int32_t dtype, int64_t N) {
   int K = 0;
-  const bool ok = dtype == RLS_F32 ? gram_pick<float>(N, &K) : gram_pick<float2>(N, &K);
+  const bool ok = rls_with_elem(dtype, [&](auto t) { return gram_pick<typename decltype(t)::type>(N, &K); });
   return ok && K != 32;
 }
 int32_t rls_gram_resident_launch(rls_ctx* ctx, int32_t dtype, const rls_gram_pipe& P, void* sync, int n_steps,
                                  unsigned spin_limit, const rls_cg_start& St) {
-  if (dtype == RLS_F32) return gram_resident_typed<float>(ctx, P, sync, n_steps, spin_limit, St);
-  return gram_resident_typed<float2>(ctx, P, sync, n_steps, spin_limit, St);
+  return rls_with_elem(dtype, [&](auto t) {
+    return gram_resident_typed<typename decltype(t)::type>(ctx, P, sync, n_steps, spin_limit, St);
+  });
 }
 
 
 int32_t rls_fista_pipe_iteration(rls_ctx* ctx, int32_t dtype, const rls_fista_pipe& P) {
-  if (dtype == RLS_F32) return fista_iteration_typed<float>(ctx, P);
-  return fista_iteration_typed<float2>(ctx, P);
+  return rls_with_elem(dtype, [&](auto t) { return fista_iteration_typed<typename decltype(t)::type>(ctx, P); });
 }
 int32_t rls_fista_pipe_finish(rls_ctx* ctx, int32_t dtype, const rls_fista_pipe& P) {
-  if (dtype == RLS_F32) return fista_finish_typed<float>(ctx, P);
-  return fista_finish_typed<float2>(ctx, P);
+  return rls_with_elem(dtype, [&](auto t) { return fista_finish_typed<typename decltype(t)::type>(ctx, P); });
 }
 
 #ifdef RLS_STAMPS
@@ -4491,25 +4487,23 @@ extern "C" int32_t rls_debug_stamps(unsigned long long* out_h) {
 #endif
 
 int32_t rls_cgnr_pipe_iteration(rls_ctx* ctx, int32_t dtype, const rls_cgnr_pipe& P) {
-  if (dtype == RLS_F32) return pipe_iteration_typed<float>(ctx, P);
-  return pipe_iteration_typed<float2>(ctx, P);
+  return rls_with_elem(dtype, [&](auto t) { return pipe_iteration_typed<typename decltype(t)::type>(ctx, P); });
 }
 // which: 1 = only the normal-operator kernel K_A, 2 = only the reduce kernel K_R (both are
 // idempotent when repeated: K_A reads the committed scalars and K_R the staged ones)
 int32_t rls_cgnr_pipe_launch(rls_ctx* ctx, int32_t dtype, const rls_cgnr_pipe& P, int which) {
-  if (dtype == RLS_F32) return pipe_iteration_typed<float>(ctx, P, which);
-  return pipe_iteration_typed<float2>(ctx, P, which);
+  return rls_with_elem(dtype, [&](auto t) { return pipe_iteration_typed<typename decltype(t)::type>(ctx, P, which); });
 }
 int32_t rls_cgnr_pipe_finish(rls_ctx* ctx, int32_t dtype, const rls_cgnr_pipe& P) {
-  if (dtype == RLS_F32) return pipe_finish_typed<float>(ctx, P);
-  return pipe_finish_typed<float2>(ctx, P);
+  return rls_with_elem(dtype, [&](auto t) { return pipe_finish_typed<typename decltype(t)::type>(ctx, P); });
 }
 
 size_t rls_normal_fused_workspace(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* A, int64_t lda) {
-  if (!ctx) return 0;
-  if (dtype == RLS_F32) return fused_ok<float>(ctx->tune, M, N, A, lda) ? (size_t)fused_nwg<float>(ctx->tune, M, N) * N * 4 : 0;
-  if (dtype == RLS_C32) return fused_ok<float2>(ctx->tune, M, N, A, lda) ? (size_t)fused_nwg<float2>(ctx->tune, M, N) * N * 8 : 0;
-  return 0;
+  if (!ctx || !rls_dtype_ok(dtype)) return 0;
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return fused_ok<E>(ctx->tune, M, N, A, lda) ? (size_t)fused_nwg<E>(ctx->tune, M, N) * N * sizeof(E) : 0;
+  });
 }
 
 int32_t rls_launch_normal_fused(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* A, int64_t lda,
@@ -4517,9 +4511,10 @@ int32_t rls_launch_normal_fused(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t 
   RLS_CHECK_CTX(ctx);
   if (!A || !p || !v || !slab) return rls_fail(ctx, RLS_E_INVALID, "normal_fused: null pointer");
   RLS_HIP(ctx, rls_enter(ctx));
-  if (dtype == RLS_F32)
-    return normal_typed<float>(ctx, M, N, (const float*)A, lda, (const float*)p, (float*)v, (float*)slab, skip);
-  return normal_typed<float2>(ctx, M, N, (const float2*)A, lda, (const float2*)p, (float2*)v, (float2*)slab, skip);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return normal_typed<E>(ctx, M, N, (const E*)A, lda, (const E*)p, (E*)v, (E*)slab, skip);
+  });
 }
 
 // resident CGNR (one launch per step call, A in registers across iterations)
@@ -4532,23 +4527,23 @@ size_t rls_resident_sync_clear_bytes() { return offsetof(resident_sync, failed);
 size_t rls_resident_sync_flags_offset() { return offsetof(resident_sync, fail); }
 size_t rls_resident_sync_placement_offset() { return offsetof(resident_sync, gcnt) + sizeof(unsigned); }  // the word resident_report_placement sets
 bool rls_cgnr_resident_ok(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* A, int64_t lda) {
-  if (!ctx) return false;
-  if (dtype == RLS_F32) return resident_ok_typed<float>(ctx->tune, ctx->device, M, N, A, lda);
-  if (dtype == RLS_C32) return resident_ok_typed<float2>(ctx->tune, ctx->device, M, N, A, lda);
-  return false;
+  if (!ctx || !rls_dtype_ok(dtype)) return false;
+  return rls_with_elem(dtype, [&](auto t) { return resident_ok_typed<typename decltype(t)::type>(ctx->tune, ctx->device, M, N, A, lda); });
 }
 int rls_cgnr_resident_nwg(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N) {
-  return dtype == RLS_F32 ? (int)fused_nwg<float>(ctx->tune, M, N) : (int)fused_nwg<float2>(ctx->tune, M, N);
+  return rls_with_elem(dtype, [&](auto t) { return (int)fused_nwg<typename decltype(t)::type>(ctx->tune, M, N); });
 }
 int32_t rls_cgnr_resident_launch(rls_ctx* ctx, int32_t dtype, const rls_cgnr_pipe& P, double* dout, void* sync,
                                  int n_steps, unsigned spin_limit, const rls_cg_start& St) {
-  if (dtype == RLS_F32) return resident_typed<float>(ctx, P, dout, sync, n_steps, spin_limit, St);
-  return resident_typed<float2>(ctx, P, dout, sync, n_steps, spin_limit, St);
+  return rls_with_elem(dtype, [&](auto t) {
+    return resident_typed<typename decltype(t)::type>(ctx, P, dout, sync, n_steps, spin_limit, St);
+  });
 }
 
 bool rls_cgnr_resident_queue_ok(const rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N) {
-  auto ok = [&](auto tag) {
-    using E = decltype(tag);
+  if (!rls_dtype_ok(dtype)) return false;
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
     if (M % elem<E>::vec) return false;  // (init! reads b in whole 16-byte row pieces)
     fused_cfg c;
     if (!pick_cfg<E>(ctx->tune, N, &c)) return false;
@@ -4556,27 +4551,22 @@ bool rls_cgnr_resident_queue_ok(const rls_ctx* ctx, int32_t dtype, int64_t M, in
       return resident_shape<E, S.G, S.K, S.WV>() && owner_cfg<E, S.G, S.K, S.WV>::ok &&
              slab_full<E, S.G, S.K, S.WV>(M, N, fused_nwg<E>(ctx->tune, M, N));
     });
-  };
-  if (dtype == RLS_F32) return ok(float());
-  if (dtype == RLS_C32) return ok(float2());
-  return false;
+  });
 }
 
 int32_t rls_fista_resident_launch(rls_ctx* ctx, int32_t dtype, const rls_fista_pipe& P, void* sync, int n_steps,
                                   unsigned spin_limit, const rls_srv_args& Sv) {
-  if (dtype == RLS_F32) return fista_resident_typed<float>(ctx, P, sync, n_steps, spin_limit, Sv);
-  return fista_resident_typed<float2>(ctx, P, sync, n_steps, spin_limit, Sv);
+  return rls_with_elem(dtype, [&](auto t) {
+    return fista_resident_typed<typename decltype(t)::type>(ctx, P, sync, n_steps, spin_limit, Sv);
+  });
 }
 
 bool rls_pgm_resident_ok(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* A, int64_t lda) {
-  if (!ctx) return false;
-  if (dtype == RLS_F32) return pgm_resident_ok_typed<float>(ctx->tune, ctx->device, M, N, A, lda);
-  if (dtype == RLS_C32) return pgm_resident_ok_typed<float2>(ctx->tune, ctx->device, M, N, A, lda);
-  return false;
+  if (!ctx || !rls_dtype_ok(dtype)) return false;
+  return rls_with_elem(dtype, [&](auto t) { return pgm_resident_ok_typed<typename decltype(t)::type>(ctx->tune, ctx->device, M, N, A, lda); });
 }
 int32_t rls_pgm_resident_launch(rls_ctx* ctx, int32_t dtype, const rls_pgm_desc& D, const rls_pgm_coefs& C, void* sync,
                                 int n_steps, unsigned spin_limit) {
   if (n_steps > RLS_PGM_MAX_IT) return rls_fail(ctx, RLS_E_INVALID, "pgm_resident: more iterations than coefficient slots");
-  if (dtype == RLS_F32) return pgm_resident_typed<float>(ctx, D, C, sync, n_steps, spin_limit);
-  return pgm_resident_typed<float2>(ctx, D, C, sync, n_steps, spin_limit);
+  return rls_with_elem(dtype, [&](auto t) { return pgm_resident_typed<typename decltype(t)::type>(ctx, D, C, sync, n_steps, spin_limit); });
 }

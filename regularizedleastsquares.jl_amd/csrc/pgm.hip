@@ -384,29 +384,18 @@ static bool pgmb_desc_ok(const rls_pgmb& D) {
 
 int32_t rls_pgmb_launch_init(rls_ctx* ctx, int32_t dtype, const rls_pgmb& D) {
   if (!rls_dtype_ok(dtype) || !pgmb_desc_ok(D)) return rls_fail(ctx, RLS_E_INVALID, "batched OptISTA / POGM init: bad argument");
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(pgmb_init_kernel<float>, dim3((unsigned)D.nrhs), dim3(PGMB_THREADS), 0, ctx->stream, D);
-  else
-    hipLaunchKernelGGL(pgmb_init_kernel<float2>, dim3((unsigned)D.nrhs), dim3(PGMB_THREADS), 0, ctx->stream, D);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rls_fail(ctx, (int32_t)e, hipGetErrorString(e));
-  return 0;
+  return rls_with_elem(dtype, [&](auto t) {
+    return rls_launch<pgmb_init_kernel<typename decltype(t)::type>>(ctx, dim3((unsigned)D.nrhs), dim3(PGMB_THREADS), 0, D);
+  });
 }
 
 int32_t rls_pgmb_launch_update(rls_ctx* ctx, int32_t dtype, const rls_pgmb& D) {
   if (!rls_dtype_ok(dtype) || !pgmb_desc_ok(D)) return rls_fail(ctx, RLS_E_INVALID, "batched OptISTA / POGM update: bad argument");
-#define RLS_PGMB(EE)                                                                             \
-  do {                                                                                           \
-    if (D.kind == RLS_PGMB_OPTISTA) pgmb_launch_update_typed<EE, RLS_PGMB_OPTISTA>(ctx, D);      \
-    else if (D.kind == RLS_PGMB_POGM) pgmb_launch_update_typed<EE, RLS_PGMB_POGM>(ctx, D);       \
-    else pgmb_launch_update_typed<EE, RLS_PGMB_POGM_RESTART>(ctx, D);                            \
-  } while (0)
-  if (dtype == RLS_F32) RLS_PGMB(float);
-  else RLS_PGMB(float2);
-#undef RLS_PGMB
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rls_fail(ctx, (int32_t)e, hipGetErrorString(e));
-  return 0;
+  rls_with_elem(dtype, [&](auto t) {
+    rls_with<RLS_PGMB_OPTISTA, RLS_PGMB_POGM, RLS_PGMB_POGM_RESTART>(
+        D.kind, [&](auto KIND) { pgmb_launch_update_typed<typename decltype(t)::type, KIND>(ctx, D); });
+  });
+  return launch_status(ctx);
 }
 
 static int32_t pgm_fetch(rls_ctx* ctx, float* out_h, int nfloats) {
@@ -426,17 +415,12 @@ static int32_t optista_launch(rls_ctx* ctx, int32_t dtype, int64_t n, void* res,
       reg_kind > RLS_REG_L2)
     return rls_fail(ctx, RLS_E_INVALID, "optista_update: bad argument");
   RLS_HIP(ctx, rls_enter(ctx));
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(optista_update_kernel<float>, dim3(1), dim3(PGM_THREADS), 0, ctx->stream, (float*)res,
-                       (const float*)x0, (float*)x, (float*)y, (float*)z, (float*)zold, n, step, reg_kind, thr, c_z, c_y,
-                       c_x, c_zn, c_zo, ctx->res_d, state, norm_x0, rel_tol);
-  else
-    hipLaunchKernelGGL(optista_update_kernel<float2>, dim3(1), dim3(PGM_THREADS), 0, ctx->stream, (float2*)res,
-                       (const float2*)x0, (float2*)x, (float2*)y, (float2*)z, (float2*)zold, n, step, reg_kind, thr, c_z,
-                       c_y, c_x, c_zn, c_zo, ctx->res_d, state, norm_x0, rel_tol);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rls_fail(ctx, (int32_t)e, hipGetErrorString(e));
-  return 0;
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<optista_update_kernel<E>>(ctx, dim3(1), dim3(PGM_THREADS), 0, (E*)res, (const E*)x0, (E*)x, (E*)y, (E*)z,
+                                                (E*)zold, n, step, reg_kind, thr, c_z, c_y, c_x, c_zn, c_zo, ctx->res_d, state,
+                                                norm_x0, rel_tol);
+  });
 }
 
 int32_t rls_optista_update(rls_ctx* ctx, int32_t dtype, int64_t n, void* res, const void* x0, void* x, void* y, void* z,
@@ -467,21 +451,14 @@ static int32_t pogm_launch(rls_ctx* ctx, int32_t dtype, int64_t n, void* res, co
       reg_kind < RLS_REG_NONE || reg_kind > RLS_REG_L2 || proj_kind < RLS_PROJ_NONE || proj_kind > RLS_PROJ_POSITIVE)
     return rls_fail(ctx, RLS_E_INVALID, "pogm_update: bad argument");
   RLS_HIP(ctx, rls_enter(ctx));
-#define RLS_POGM(EE, RR)                                                                                             \
-  hipLaunchKernelGGL((pogm_update_kernel<EE, RR>), dim3(1), dim3(PGM_THREADS), 0, ctx->stream, (EE*)res, (const EE*)x0, \
-                     (EE*)xbuf, (EE*)ybuf, (EE*)xold, (EE*)z, (EE*)w, n, rho, c_y, c_x1, c_xo, c_z, reg_kind, thr,     \
-                     proj_kind, rho_over_gamma, ctx->res_d, state, norm_x0, rel_tol)
-  if (dtype == RLS_F32) {
-    if (restart) RLS_POGM(float, true);
-    else RLS_POGM(float, false);
-  } else {
-    if (restart) RLS_POGM(float2, true);
-    else RLS_POGM(float2, false);
-  }
-#undef RLS_POGM
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rls_fail(ctx, (int32_t)e, hipGetErrorString(e));
-  return 0;
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return with_bool(restart != 0, [&](auto RESTART) {
+      return rls_launch<pogm_update_kernel<E, RESTART>>(ctx, dim3(1), dim3(PGM_THREADS), 0, (E*)res, (const E*)x0, (E*)xbuf,
+                                                        (E*)ybuf, (E*)xold, (E*)z, (E*)w, n, rho, c_y, c_x1, c_xo, c_z, reg_kind,
+                                                        thr, proj_kind, rho_over_gamma, ctx->res_d, state, norm_x0, rel_tol);
+    });
+  });
 }
 
 int32_t rls_pogm_update(rls_ctx* ctx, int32_t dtype, int64_t n, void* res, const void* x0, void* xbuf, void* ybuf,
@@ -517,17 +494,12 @@ int32_t rls_pogm_update_auto(rls_ctx* ctx, int32_t dtype, int64_t n, void* res, 
       reg_kind < RLS_REG_NONE || reg_kind > RLS_REG_L2 || proj_kind < RLS_PROJ_NONE || proj_kind > RLS_PROJ_POSITIVE)
     return rls_fail(ctx, RLS_E_INVALID, "pogm_update_auto: bad argument");
   RLS_HIP(ctx, rls_enter(ctx));
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(pogm_auto_kernel<float>, dim3(1), dim3(PGM_THREADS), 0, ctx->stream, (float*)res, (const float*)x0,
-                       (float*)xbuf, (float*)ybuf, (float*)xold, (float*)z, (float*)w, n, rho, lambda, sigma_fac,
-                       iterations, reg_kind, proj_kind, (pogm_auto_state*)state_d, norm_x0, rel_tol);
-  else
-    hipLaunchKernelGGL(pogm_auto_kernel<float2>, dim3(1), dim3(PGM_THREADS), 0, ctx->stream, (float2*)res,
-                       (const float2*)x0, (float2*)xbuf, (float2*)ybuf, (float2*)xold, (float2*)z, (float2*)w, n, rho,
-                       lambda, sigma_fac, iterations, reg_kind, proj_kind, (pogm_auto_state*)state_d, norm_x0, rel_tol);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rls_fail(ctx, (int32_t)e, hipGetErrorString(e));
-  return 0;
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<pogm_auto_kernel<E>>(ctx, dim3(1), dim3(PGM_THREADS), 0, (E*)res, (const E*)x0, (E*)xbuf, (E*)ybuf, (E*)xold,
+                                           (E*)z, (E*)w, n, rho, lambda, sigma_fac, iterations, reg_kind, proj_kind,
+                                           (pogm_auto_state*)state_d, norm_x0, rel_tol);
+  });
 }
 
 }  // extern "C"

@@ -654,12 +654,11 @@ int32_t rls_cgnr_init_d(rls_cgnr_d* s, const void* b, double lambda, double rel_
   RLS_HIP(B.ctx, rls_enter(B.ctx));
   RLS_TRY(dp_adjoint_b(B, b, s->r));
   const int max_iter = (int)(iterations < B.N ? iterations : B.N);  // done(): iteration >= min(iterations, N)
-  if (B.dtype == RLS_F64)
-    RLS_TRY((rls_launch<dp_cgnr_init_kernel<double>>(B.ctx, dim3(1), dim3(UPD_T), 0, (double*)s->x, (const double*)s->r, (double*)s->p, (double*)s->v,
-                                                     B.N, lambda, rel_tol, max_iter, s->rec)));
-  else
-    RLS_TRY((rls_launch<dp_cgnr_init_kernel<double2>>(B.ctx, dim3(1), dim3(UPD_T), 0, (double2*)s->x, (const double2*)s->r, (double2*)s->p,
-                                                      (double2*)s->v, B.N, lambda, rel_tol, max_iter, s->rec)));
+  RLS_TRY(rls_with_elem64(B.dtype, [&](auto t) {
+    using D = typename decltype(t)::type;
+    return rls_launch<dp_cgnr_init_kernel<D>>(B.ctx, dim3(1), dim3(UPD_T), 0, (D*)s->x, (const D*)s->r, (D*)s->p, (D*)s->v, B.N, lambda,
+                                              rel_tol, max_iter, s->rec);
+  }));
   B.initialised = true;
   return 0;
 }
@@ -669,7 +668,7 @@ int32_t rls_cgnr_step_d(rls_cgnr_d* s, int32_t n_steps) {
   if (!B.initialised) return rls_fail(B.ctx, RLS_E_STATE, "cgnr_step_d before cgnr_init_d");
   if (n_steps < 0) return rls_fail(B.ctx, RLS_E_INVALID, "cgnr_step_d: negative step count");
   RLS_HIP(B.ctx, rls_enter(B.ctx));
-  return B.dtype == RLS_F64 ? dp_cgnr_step<double>(s, n_steps) : dp_cgnr_step<double2>(s, n_steps);
+  return rls_with_elem64(B.dtype, [&](auto t) { return dp_cgnr_step<typename decltype(t)::type>(s, n_steps); });
 }
 int32_t rls_cgnr_get_status_d(rls_cgnr_d* s, rls_cgnr_status_d* out_h) {
   if (!s) return RLS_E_INVALID;
@@ -749,12 +748,11 @@ int32_t rls_fista_init_d(rls_fista_d* s, const void* b, double rho, double theta
   init.restart = restart_gradient ? 1 : 0;
   init.reg_kind = s->reg_kind;
   init.proj_kind = s->proj_kind;
-  if (B.dtype == RLS_F64)
-    RLS_TRY((rls_launch<dp_fista_init_kernel<double>>(B.ctx, dim3(1), dim3(UPD_T), 0, (double*)s->buf[0], (double*)s->buf[1], (const double*)s->x0,
-                                                      (double*)s->res, B.N, init, s->rec)));
-  else
-    RLS_TRY((rls_launch<dp_fista_init_kernel<double2>>(B.ctx, dim3(1), dim3(UPD_T), 0, (double2*)s->buf[0], (double2*)s->buf[1],
-                                                       (const double2*)s->x0, (double2*)s->res, B.N, init, s->rec)));
+  RLS_TRY(rls_with_elem64(B.dtype, [&](auto t) {
+    using D = typename decltype(t)::type;
+    return rls_launch<dp_fista_init_kernel<D>>(B.ctx, dim3(1), dim3(UPD_T), 0, (D*)s->buf[0], (D*)s->buf[1], (const D*)s->x0,
+                                               (D*)s->res, B.N, init, s->rec);
+  }));
   s->enqueued = 0;
   s->status_current = false;
   B.initialised = true;
@@ -778,7 +776,7 @@ int32_t rls_fista_step_d(rls_fista_d* s, int32_t n_steps) {
   if (n_steps < 0) return rls_fail(B.ctx, RLS_E_INVALID, "fista_step_d: negative step count");
   RLS_HIP(B.ctx, rls_enter(B.ctx));
   if (n_steps > 0) s->status_current = false;
-  return B.dtype == RLS_F64 ? dp_fista_step<double>(s, n_steps) : dp_fista_step<double2>(s, n_steps);
+  return rls_with_elem64(B.dtype, [&](auto t) { return dp_fista_step<typename decltype(t)::type>(s, n_steps); });
 }
 int32_t rls_fista_get_status_d(rls_fista_d* s, rls_fista_status_d* out_h) {
   if (!s) return RLS_E_INVALID;

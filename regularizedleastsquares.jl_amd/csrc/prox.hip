@@ -105,30 +105,27 @@ extern "C" {
 
 int32_t rls_prox_l1(rls_ctx* ctx, int32_t dtype, int64_t n, void* x, float lambda) {
   PX_PRELUDE("prox_l1");
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(prox_l1_kernel<float>, dim3(px_grid(n)), dim3(PX_THREADS), 0, ctx->stream, (float*)x, n, lambda);
-  else
-    hipLaunchKernelGGL(prox_l1_kernel<float2>, dim3(px_grid(n)), dim3(PX_THREADS), 0, ctx->stream, (float2*)x, n, lambda);
-  return px_status(ctx);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<prox_l1_kernel<E>>(ctx, dim3(px_grid(n)), dim3(PX_THREADS), 0, (E*)x, n, lambda);
+  });
 }
 
 int32_t rls_prox_l2(rls_ctx* ctx, int32_t dtype, int64_t n, void* x, float lambda) {
   PX_PRELUDE("prox_l2");
   const double factor = 1.0 / (1.0 + 2.0 * (double)lambda);
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(prox_l2_kernel<float>, dim3(px_grid(n)), dim3(PX_THREADS), 0, ctx->stream, (float*)x, n, factor);
-  else
-    hipLaunchKernelGGL(prox_l2_kernel<float2>, dim3(px_grid(n)), dim3(PX_THREADS), 0, ctx->stream, (float2*)x, n, factor);
-  return px_status(ctx);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<prox_l2_kernel<E>>(ctx, dim3(px_grid(n)), dim3(PX_THREADS), 0, (E*)x, n, factor);
+  });
 }
 
 int32_t rls_prox_positive(rls_ctx* ctx, int32_t dtype, int64_t n, void* x) {
   PX_PRELUDE("prox_positive");
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL((project_kernel<float, true>), dim3(px_grid(n)), dim3(PX_THREADS), 0, ctx->stream, (float*)x, n);
-  else
-    hipLaunchKernelGGL((project_kernel<float2, true>), dim3(px_grid(n)), dim3(PX_THREADS), 0, ctx->stream, (float2*)x, n);
-  return px_status(ctx);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<project_kernel<E, true>>(ctx, dim3(px_grid(n)), dim3(PX_THREADS), 0, (E*)x, n);
+  });
 }
 
 int32_t rls_prox_real(rls_ctx* ctx, int32_t dtype, int64_t n, void* x) {
@@ -142,13 +139,10 @@ int32_t rls_prox_l21(rls_ctx* ctx, int32_t dtype, int64_t n, int64_t slices, voi
   PX_PRELUDE("prox_l21");
   if (slices <= 0 || n / slices == 0) return rls_fail(ctx, RLS_E_INVALID, "prox_l21: slices must be in 1..n");
   const int64_t slen = n / slices;
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL((l21_kernel<float, true>), dim3(px_grid(slen)), dim3(PX_THREADS), 0, ctx->stream, (float*)x, n,
-                       slen, lambda, (double*)nullptr);
-  else
-    hipLaunchKernelGGL((l21_kernel<float2, true>), dim3(px_grid(slen)), dim3(PX_THREADS), 0, ctx->stream, (float2*)x,
-                       n, slen, lambda, (double*)nullptr);
-  return px_status(ctx);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<l21_kernel<E, true>>(ctx, dim3(px_grid(slen)), dim3(PX_THREADS), 0, (E*)x, n, slen, lambda, (double*)nullptr);
+  });
 }
 
 int32_t rls_norm_l21(rls_ctx* ctx, int32_t dtype, int64_t n, int64_t slices, const void* x, float lambda,
@@ -160,12 +154,10 @@ int32_t rls_norm_l21(rls_ctx* ctx, int32_t dtype, int64_t n, int64_t slices, con
   const int64_t slen = n / slices;
   unsigned g = px_grid(slen);
   if (g > RLS_RED_SLOTS / 2) g = RLS_RED_SLOTS / 2;
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL((l21_kernel<float, false>), dim3(g), dim3(PX_THREADS), 0, ctx->stream, (float*)x, n, slen,
-                       lambda, ctx->red_d);
-  else
-    hipLaunchKernelGGL((l21_kernel<float2, false>), dim3(g), dim3(PX_THREADS), 0, ctx->stream, (float2*)x, n, slen,
-                       lambda, ctx->red_d);
+  rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    hipLaunchKernelGGL((l21_kernel<E, false>), dim3(g), dim3(PX_THREADS), 0, ctx->stream, (E*)x, n, slen, lambda, ctx->red_d);
+  });
   hipLaunchKernelGGL(l21_norm_final, dim3(1), dim3(256), 0, ctx->stream, ctx->red_d, (int)g, lambda, ctx->res_d);
   RLS_TRY(px_status(ctx));
   RLS_HIP(ctx, hipMemcpyAsync(ctx->res_h, ctx->res_d, sizeof(float) * 2, hipMemcpyDeviceToHost, ctx->stream));

@@ -361,6 +361,24 @@ static inline auto with_bool(bool b, F&& f) {
   return rls_with<false, true>(b, static_cast<F&&>(f));
 }
 
+// Element-type dispatch: calls f(rls_type<E>{}) with E = float for RLS_F32 and float2 for anything else (rls_with_elem), double
+// for RLS_F64 and double2 for anything else (rls_with_elem64) -- the fall-through of rls_with; entry points reject other dtypes
+// first.  In f, `using E = typename decltype(t)::type;` names the kernel instantiation and every cast, so a launch is written once.
+template <typename E>
+struct rls_type {
+  using type = E;
+};
+template <typename F>
+static inline auto rls_with_elem(int32_t dtype, F&& f) {
+  if (dtype == RLS_F32) return f(rls_type<float>{});
+  return f(rls_type<float2>{});
+}
+template <typename F>
+static inline auto rls_with_elem64(int32_t dtype, F&& f) {
+  if (dtype == RLS_F64) return f(rls_type<double>{});
+  return f(rls_type<double2>{});
+}
+
 static inline size_t rls_elem_size(int32_t dtype) { return dtype == RLS_C32 ? 8 : 4; }
 static inline bool rls_dtype_ok(int32_t dtype) { return dtype == RLS_F32 || dtype == RLS_C32; }
 
@@ -375,7 +393,7 @@ struct elem<float> {
   static constexpr bool cplx = false;
   static constexpr int vec = 4;  // elements per 16-byte load
   __device__ static inline float zero() { return 0.f; }
-  __device__ static inline float make(float re, float) { return re; }
+  __host__ __device__ static inline float make(float re, float) { return re; }
   __device__ static inline float mul(float a, float b) { return a * b; }
   __device__ static inline float mulc(float a, float b) { return a * b; }  // conj(a)*b
   __device__ static inline float fma(float a, float b, float c) { return fmaf(a, b, c); }
@@ -395,7 +413,7 @@ struct elem<float2> {
   static constexpr bool cplx = true;
   static constexpr int vec = 2;
   __device__ static inline float2 zero() { return make_float2(0.f, 0.f); }
-  __device__ static inline float2 make(float re, float im) { return make_float2(re, im); }
+  __host__ __device__ static inline float2 make(float re, float im) { return make_float2(re, im); }
   __device__ static inline float2 mul(float2 a, float2 b) {
     return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
   }
@@ -712,7 +730,7 @@ __device__ static inline E fista_proj_elem(E v, int proj_kind) {
 
 // the same maps for D = double / double2 (the double-precision FISTA plan of plans_f64.hip and the sweep of f64.hip)
 template <typename D>
-__device__ static inline D dp_make(double re, double im) {
+__host__ __device__ static inline D dp_make(double re, double im) {
   if constexpr (sizeof(D) == sizeof(double2)) return make_double2(re, im);
   else return re;
 }

@@ -49,11 +49,10 @@ int32_t rls_rownorm2(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const vo
   float* partial = nullptr;
   RLS_HIP(ctx, hipMalloc((void**)&partial, sizeof(float) * (size_t)CS * (size_t)M));
   const dim3 grid((unsigned)((M + 255) / 256), (unsigned)CS);
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(rownorm2_partial_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float*)A, lda, M, N, partial);
-  else
-    hipLaunchKernelGGL(rownorm2_partial_kernel<float2>, grid, dim3(256), 0, ctx->stream, (const float2*)A, lda, M, N,
-                       partial);
+  rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    hipLaunchKernelGGL(rownorm2_partial_kernel<E>, grid, dim3(256), 0, ctx->stream, (const E*)A, lda, M, N, partial);
+  });
   hipLaunchKernelGGL(rownorm2_sum_kernel, dim3(grid.x), dim3(256), 0, ctx->stream, partial, CS, M, out_d);
   int32_t st = setup_status(ctx);
   hipError_t e = rls_stream_wait(ctx->stream);  // setup path: the scratch is freed before returning
@@ -69,13 +68,10 @@ int32_t rls_scale_rows(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const 
     return rls_fail(ctx, RLS_E_INVALID, "scale_rows: bad argument");
   RLS_HIP(ctx, rls_enter(ctx));
   const dim3 grid((unsigned)((M + 255) / 256), (unsigned)(N < 256 ? N : 256));
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(scale_rows_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float*)w, (const float*)A, lda,
-                       (float*)B, ldb, M, N);
-  else
-    hipLaunchKernelGGL(scale_rows_kernel<float2>, grid, dim3(256), 0, ctx->stream, (const float2*)w, (const float2*)A,
-                       lda, (float2*)B, ldb, M, N);
-  return setup_status(ctx);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<scale_rows_kernel<E>>(ctx, grid, dim3(256), 0, (const E*)w, (const E*)A, lda, (E*)B, ldb, M, N);
+  });
 }
 
 }  // extern "C"

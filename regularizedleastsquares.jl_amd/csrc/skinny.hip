@@ -662,7 +662,7 @@ __global__ __launch_bounds__(NT) void skinny_u_kernel(E* __restrict__ X, E* __re
 
 bool rls_skinny_ok(int32_t dtype, int64_t M, int64_t N, const void* A, int64_t lda) {
   if (!A || M < 16 || N < 16 || M % 16 || N % 16) return false;
-  const int V = dtype == RLS_C32 ? 2 : 4;
+  const int V = rls_with_elem(dtype, [](auto t) { return elem<typename decltype(t)::type>::vec; });
   return ((uintptr_t)A % 16 == 0) && (lda % V == 0);
 }
 
@@ -848,38 +848,33 @@ static int32_t skinny_init_typed(rls_ctx* ctx, const rls_skinny& K, const void* 
 
 int32_t rls_skinny_init(rls_ctx* ctx, int32_t dtype, const rls_skinny& K, const void* B, int64_t ldb, float lambda,
                         float rel_tol, int max_iter) {
-  return dtype == RLS_F32 ? skinny_init_typed<float>(ctx, K, B, ldb, lambda, rel_tol, max_iter)
-                          : skinny_init_typed<float2>(ctx, K, B, ldb, lambda, rel_tol, max_iter);
+  return rls_with_elem(dtype, [&](auto t) {
+    return skinny_init_typed<typename decltype(t)::type>(ctx, K, B, ldb, lambda, rel_tol, max_iter);
+  });
 }
 
 // partial rows of A^H B into K.Vpart (B: M x nrhs column-major): the init product of the batched plans
 int32_t rls_skinny_atb(rls_ctx* ctx, int32_t dtype, const rls_skinny& K, const void* B, int64_t ldb) {
-  if (dtype == RLS_F32) {
-    launch_pack_rows<float>(ctx, K, (const float*)B, ldb);
-    launch_v<float>(ctx, K);
-  } else {
-    launch_pack_rows<float2>(ctx, K, (const float2*)B, ldb);
-    launch_v<float2>(ctx, K);
-  }
+  rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    launch_pack_rows<E>(ctx, K, (const E*)B, ldb);
+    launch_v<E>(ctx, K);
+  });
   return sk_status(ctx);
 }
 
 // which: bit 0 = T kernel, bit 1 = V kernel, bit 2 = update kernel
 int32_t rls_skinny_launch(rls_ctx* ctx, int32_t dtype, const rls_skinny& K, int which) {
-  if (K.G && (which & 3)) {  // explicit AHA: the two products over A are one product over the Gram matrix
-    if (dtype == RLS_F32) launch_g<float>(ctx, K);
-    else launch_g<float2>(ctx, K);
-    which &= ~3;
-  }
-  if (dtype == RLS_F32) {
-    if (which & 1) launch_t<float>(ctx, K);
-    if (which & 2) launch_v<float>(ctx, K);
-    if (which & 4) launch_u<float, false>(ctx, K, 0.f, 0.f, 0);
-  } else {
-    if (which & 1) launch_t<float2>(ctx, K);
-    if (which & 2) launch_v<float2>(ctx, K);
-    if (which & 4) launch_u<float2, false>(ctx, K, 0.f, 0.f, 0);
-  }
+  rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    if (K.G && (which & 3)) {  // explicit AHA: the two products over A are one product over the Gram matrix
+      launch_g<E>(ctx, K);
+      which &= ~3;
+    }
+    if (which & 1) launch_t<E>(ctx, K);
+    if (which & 2) launch_v<E>(ctx, K);
+    if (which & 4) launch_u<E, false>(ctx, K, 0.f, 0.f, 0);
+  });
   return sk_status(ctx);
 }
 
@@ -1040,16 +1035,17 @@ int32_t rls_gram_tiles(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const 
     hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_mfma_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_mfma_kernel<float2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   }
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(gram_mfma_kernel<float>, grid, dim3(256), lds, ctx->stream, (const float*)A, lda, (float*)G, ldg, M, N);
-  else
-    hipLaunchKernelGGL(gram_mfma_kernel<float2>, grid, dim3(256), lds, ctx->stream, (const float2*)A, lda, (float2*)G, ldg,
-                       M, N);
+  rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    hipLaunchKernelGGL(gram_mfma_kernel<E>, grid, dim3(256), lds, ctx->stream, (const E*)A, lda, (E*)G, ldg, M, N);
+  });
   return sk_status(ctx);
 }
 
 int32_t rls_skinny_gram(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* A, int64_t lda, void* G,
                         int64_t ldg, void* panels) {
-  return dtype == RLS_F32 ? skinny_gram_typed<float>(ctx, M, N, (const float*)A, lda, (float*)G, ldg, (float*)panels)
-                          : skinny_gram_typed<float2>(ctx, M, N, (const float2*)A, lda, (float2*)G, ldg, (float2*)panels);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return skinny_gram_typed<E>(ctx, M, N, (const E*)A, lda, (E*)G, ldg, (E*)panels);
+  });
 }

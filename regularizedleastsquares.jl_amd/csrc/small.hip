@@ -578,17 +578,17 @@ static int32_t fista_small_typed(rls_ctx* ctx, const rls_fista_pipe& P, int n_st
 
 // a whole rls_fista_step call of a system rls_small_ok accepts (plan state in the pipeline's layout: P.b0 / b1, y0 / y1, sc)
 int32_t rls_fista_small_launch(rls_ctx* ctx, int32_t dtype, const rls_fista_pipe& P, int n_steps, const rls_srv_args& Sv) {
-  return dtype == RLS_F32 ? fista_small_typed<float>(ctx, P, n_steps, Sv) : fista_small_typed<float2>(ctx, P, n_steps, Sv);
+  return rls_with_elem(dtype, [&](auto t) { return fista_small_typed<typename decltype(t)::type>(ctx, P, n_steps, Sv); });
 }
 
 bool rls_small_ok(int32_t dtype, int64_t M, int64_t N, const void* A, int64_t lda) {
   if (!A || M < 1 || N < 1 || lda < M) return false;
   small_tile t;
-  return dtype == RLS_F32 ? small_pick<float>(M, N, &t) : small_pick<float2>(M, N, &t);
+  return rls_with_elem(dtype, [&](auto e) { return small_pick<typename decltype(e)::type>(M, N, &t); });
 }
 
 int32_t rls_small_group_launch(rls_ctx* ctx, int32_t dtype, const rls_small_group& G, int n_steps) {
-  return dtype == RLS_F32 ? small_typed<float>(ctx, G, n_steps) : small_typed<float2>(ctx, G, n_steps);
+  return rls_with_elem(dtype, [&](auto t) { return small_typed<typename decltype(t)::type>(ctx, G, n_steps); });
 }
 int32_t rls_small_launch(rls_ctx* ctx, int32_t dtype, const rls_small& D, int n_steps) {
   rls_small_group G;

@@ -652,10 +652,7 @@ static void cgnr_launch_update(rls_cgnr* s) {
 }
 
 static int32_t cgnr_enqueue_update(rls_cgnr* s) {
-  if (s->op->dtype == RLS_F32)
-    cgnr_launch_update<float>(s);
-  else
-    cgnr_launch_update<float2>(s);
+  rls_with_elem(s->op->dtype, [&](auto t) { cgnr_launch_update<typename decltype(t)::type>(s); });
   return launch_status(s->op->ctx);
 }
 
@@ -1070,10 +1067,10 @@ static rls_fista_pipe fista_pipe_desc(const rls_fista* s) {
 static int32_t fista_enqueue_iteration(rls_fista* s) {
   rls_operator* op = s->op;
   RLS_TRY(op_normal(op, s->y, s->res, &s->sc->done));
-  if (op->dtype == RLS_F32)
-    RLS_TRY(fista_launch_update<float>(s, 1, fista_batch<float>{0, nullptr, 1, 0, nullptr, 0}));
-  else
-    RLS_TRY(fista_launch_update<float2>(s, 1, fista_batch<float2>{0, nullptr, 1, 0, nullptr, 0}));
+  RLS_TRY(rls_with_elem(op->dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return fista_launch_update<E>(s, 1, fista_batch<E>{0, nullptr, 1, 0, nullptr, 0});
+  }));
   return launch_status(op->ctx);
 }
 
@@ -1529,13 +1526,10 @@ __global__ void hermitianize_kernel(E* __restrict__ G, int64_t ld, int64_t N) {
 
 static int32_t gram_hermitianize(rls_ctx* ctx, int32_t dtype, int64_t N, void* G, int64_t ld) {
   const dim3 block(32, 8), grid((unsigned)((N + 31) / 32), (unsigned)((N + 7) / 8));
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(hermitianize_kernel<float>, grid, block, 0, ctx->stream, (float*)G, ld, N);
-  else
-    hipLaunchKernelGGL(hermitianize_kernel<float2>, grid, block, 0, ctx->stream, (float2*)G, ld, N);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rls_fail(ctx, (int32_t)e, hipGetErrorString(e));
-  return 0;
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<hermitianize_kernel<E>>(ctx, grid, block, 0, (E*)G, ld, N);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1702,10 +1696,10 @@ static int32_t fista_enqueue_batched(rls_fista* s) {
   rls_operator* op = s->op;
   rls_ctx* ctx = op->ctx;
   RLS_TRY(rls_skinny_launch(ctx, op->dtype, fista_skinny_desc(s), 1 | 2));
-  if (op->dtype == RLS_F32)
-    RLS_TRY(fista_launch_update<float>(s, (unsigned)s->nrhs, fista_batch_desc<float>(s)));
-  else
-    RLS_TRY(fista_launch_update<float2>(s, (unsigned)s->nrhs, fista_batch_desc<float2>(s)));
+  RLS_TRY(rls_with_elem(op->dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return fista_launch_update<E>(s, (unsigned)s->nrhs, fista_batch_desc<E>(s));
+  }));
   return launch_status(ctx);
 }
 
@@ -1735,8 +1729,14 @@ static int32_t cg_solve_impl(rls_cg* s, void* x, const void* b, float rho, int32
   rls_operator* op = s->op;
   rls_ctx* ctx = op->ctx;
   const int64_t n = op->N;
-  const admm_fuse<float> Ff = typed_fuse<float>(FV);
-  const admm_fuse<float2> Fc = typed_fuse<float2>(FV);
+  // the start kernel of both per-iteration pipelines (Gram mode and matrix-free)
+  auto pipe_start = [&] {
+    return rls_with_elem(op->dtype, [&](auto t) {
+      using E = typename decltype(t)::type;
+      return rls_launch<cg_pipe_start_kernel<E>>(ctx, dim3(1), dim3(UPD_THREADS), 0, (const E*)x, (const E*)b, (E*)s->u, (E*)s->r,
+                                                 (const E*)s->c, n, s->psc, rho, reltol, maxiter, typed_fuse<E>(FV));
+    });
+  };
   // the cg! entry folded into a resident launch: warm-start apply, r = b - (AHA + rho I) x (ADMM's beta formed on the way)
   rls_cg_start St;
   St.enabled = 1;
@@ -1767,15 +1767,7 @@ static int32_t cg_solve_impl(rls_cg* s, void* x, const void* b, float rho, int32
   if (!resident_mf) RLS_TRY(op_normal(op, x, s->c, FV.skip));
   if (cg_use_gram_pipeline(s)) {
     s->used_pipeline = true;
-    if (op->dtype == RLS_F32)
-      hipLaunchKernelGGL(cg_pipe_start_kernel<float>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (const float*)x,
-                         (const float*)b, (float*)s->u, (float*)s->r, (const float*)s->c, n, s->psc, rho, reltol,
-                         maxiter, Ff);
-    else
-      hipLaunchKernelGGL(cg_pipe_start_kernel<float2>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (const float2*)x,
-                         (const float2*)b, (float2*)s->u, (float2*)s->r, (const float2*)s->c, n, s->psc, rho, reltol,
-                         maxiter, Fc);
-    RLS_TRY(launch_status(ctx));
+    RLS_TRY(pipe_start());
     const rls_gram_pipe P = cg_gram_desc(s, x);
     const int32_t dtype = op->dtype;
     s->graph.keep_for(3, x);
@@ -1801,15 +1793,7 @@ static int32_t cg_solve_impl(rls_cg* s, void* x, const void* b, float rho, int32
         return rls_cgnr_resident_launch(ctx, op->dtype, P, s->rdots, sync, maxiter, spin, St);
       });
     }
-    if (op->dtype == RLS_F32)
-      hipLaunchKernelGGL(cg_pipe_start_kernel<float>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (const float*)x,
-                         (const float*)b, (float*)s->u, (float*)s->r, (const float*)s->c, n, s->psc, rho, reltol,
-                         maxiter, Ff);
-    else
-      hipLaunchKernelGGL(cg_pipe_start_kernel<float2>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (const float2*)x,
-                         (const float2*)b, (float2*)s->u, (float2*)s->r, (const float2*)s->c, n, s->psc, rho, reltol,
-                         maxiter, Fc);
-    RLS_TRY(launch_status(ctx));
+    RLS_TRY(pipe_start());
     rls_cgnr_pipe P = cg_pipe_desc(s, x);
     const int32_t dtype = op->dtype;
     s->graph.keep_for(1, x);
@@ -1820,26 +1804,17 @@ static int32_t cg_solve_impl(rls_cg* s, void* x, const void* b, float rho, int32
     }, [&k](int c) { k -= c; }));
     return rls_cgnr_pipe_finish(ctx, dtype, P);
   }
-  if (op->dtype == RLS_F32)
-    hipLaunchKernelGGL(cg_start_kernel<float>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (const float*)x,
-                       (const float*)b, (float*)s->u, (float*)s->r, (const float*)s->c, n, s->sc, rho, reltol, maxiter,
-                       Ff, col_batch<float>());
-  else
-    hipLaunchKernelGGL(cg_start_kernel<float2>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (const float2*)x,
-                       (const float2*)b, (float2*)s->u, (float2*)s->r, (const float2*)s->c, n, s->sc, rho, reltol,
-                       maxiter, Fc, col_batch<float2>());
-  RLS_TRY(launch_status(ctx));
-  for (int it = 0; it < maxiter; ++it) {
-    RLS_TRY(op_normal(op, s->u, s->c, &s->sc->done));
-    if (op->dtype == RLS_F32)
-      hipLaunchKernelGGL(cg_update_kernel<float>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (float*)x, (float*)s->u,
-                         (float*)s->r, (float*)s->c, n, s->sc, col_batch<float>());
-    else
-      hipLaunchKernelGGL(cg_update_kernel<float2>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (float2*)x,
-                         (float2*)s->u, (float2*)s->r, (float2*)s->c, n, s->sc, col_batch<float2>());
-    RLS_TRY(launch_status(ctx));
-  }
-  return 0;
+  return rls_with_elem(op->dtype, [&](auto t) -> int32_t {
+    using E = typename decltype(t)::type;
+    RLS_TRY(rls_launch<cg_start_kernel<E>>(ctx, dim3(1), dim3(UPD_THREADS), 0, (const E*)x, (const E*)b, (E*)s->u, (E*)s->r,
+                                           (const E*)s->c, n, s->sc, rho, reltol, maxiter, typed_fuse<E>(FV), col_batch<E>()));
+    for (int it = 0; it < maxiter; ++it) {
+      RLS_TRY(op_normal(op, s->u, s->c, &s->sc->done));
+      RLS_TRY(rls_launch<cg_update_kernel<E>>(ctx, dim3(1), dim3(UPD_THREADS), 0, (E*)x, (E*)s->u, (E*)s->r, (E*)s->c, n, s->sc,
+                                              col_batch<E>()));
+    }
+    return 0;
+  });
 }
 
 // ---- batched ADMM (shared A): every column's outer iteration advances together --------------------------------
@@ -1925,7 +1900,7 @@ static int32_t admm_step_batched_typed(rls_admm* a, int32_t n_outer) {
 }
 
 static int32_t admm_step_batched(rls_admm* a, int32_t n_outer) {
-  return a->cg->op->dtype == RLS_F32 ? admm_step_batched_typed<float>(a, n_outer) : admm_step_batched_typed<float2>(a, n_outer);
+  return rls_with_elem(a->cg->op->dtype, [&](auto t) { return admm_step_batched_typed<typename decltype(t)::type>(a, n_outer); });
 }
 
 // ---- helpers of the row-sharded entry points (templates: C++ linkage) --------------------------------------------------
@@ -2064,11 +2039,10 @@ int32_t rls_gram(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* 
     return st;
   }
   dim3 grid((unsigned)((N + 63) / 64), (unsigned)((N + 63) / 64));
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(gram_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float*)A, lda, M, N, (float*)G, ld);
-  else
-    hipLaunchKernelGGL(gram_kernel<float2>, grid, dim3(256), 0, ctx->stream, (const float2*)A, lda, M, N, (float2*)G, ld);
-  RLS_TRY(launch_status(ctx));
+  RLS_TRY(rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<gram_kernel<E>>(ctx, grid, dim3(256), 0, (const E*)A, lda, M, N, (E*)G, ld);
+  }));
   return gram_hermitianize(ctx, dtype, N, G, ld);
 }
 
@@ -2215,10 +2189,9 @@ int32_t rls_cgnr_init_local_b(rls_cgnr* s) {
   if (!s) return RLS_E_INVALID;
   rls_ctx* ctx = s->op->ctx;
   RLS_HIP(ctx, rls_enter(ctx));
-  if (s->op->dtype == RLS_F32)
-    cgnr_launch_init<float>(s, s->sc_h->lambda, s->sc_h->rel_tol, s->sc_h->max_iter);
-  else
-    cgnr_launch_init<float2>(s, s->sc_h->lambda, s->sc_h->rel_tol, s->sc_h->max_iter);
+  rls_with_elem(s->op->dtype, [&](auto t) {
+    cgnr_launch_init<typename decltype(t)::type>(s, s->sc_h->lambda, s->sc_h->rel_tol, s->sc_h->max_iter);
+  });
   s->initialised = true;
   s->requested = 0;
   s->srv.off = false;  // (a new solve: the caller's pattern between iterates is judged afresh)
@@ -2272,12 +2245,11 @@ int32_t rls_cgnr_init_batched(rls_cgnr* s, const void* B, int64_t ldb, float lam
     char* xb = (char*)s->x + (size_t)b * s->ldv * es;
     char* pb = (char*)s->p + (size_t)b * s->ldv * es;
     char* vb = (char*)s->v + (size_t)b * s->ldv * es;
-    if (op->dtype == RLS_F32)
-      hipLaunchKernelGGL(cgnr_init_kernel<float>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (float*)xb,
-                         (const float*)rb, (float*)pb, (float*)vb, op->N, s->sc + b, lambda, rel_tol, max_iter);
-    else
-      hipLaunchKernelGGL(cgnr_init_kernel<float2>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (float2*)xb,
-                         (const float2*)rb, (float2*)pb, (float2*)vb, op->N, s->sc + b, lambda, rel_tol, max_iter);
+    rls_with_elem(op->dtype, [&](auto t) {
+      using E = typename decltype(t)::type;
+      hipLaunchKernelGGL(cgnr_init_kernel<E>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (E*)xb, (const E*)rb, (E*)pb, (E*)vb,
+                         op->N, s->sc + b, lambda, rel_tol, max_iter);
+    });
   }
   s->sc_h->lambda = lambda;
   s->sc_h->rel_tol = rel_tol;
@@ -3282,18 +3254,14 @@ static int32_t fista_init_finish(rls_fista* s, float rho, float theta, float rel
   rls_operator* op = s->op;
   rls_ctx* ctx = op->ctx;
   RLS_HIP(ctx, rls_enter(ctx));
-  if (op->dtype == RLS_F32)
-    hipLaunchKernelGGL(fista_init_kernel<float>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (float*)s->buf[0],
-                       (float*)s->buf[1], (float*)s->x0, (float*)s->res, (float*)s->y, op->N, s->sc, rho, theta,
-                       rel_tol, iterations, restart_gradient, s->reg_kind, s->proj_kind, s->lambda,
-                       (long long)s->l21_slices, fista_batch<float>{0, nullptr, 1, 0, nullptr, 0}, (unsigned*)s->resident.sync,
+  rls_with_elem(op->dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    hipLaunchKernelGGL(fista_init_kernel<E>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (E*)s->buf[0], (E*)s->buf[1], (E*)s->x0,
+                       (E*)s->res, (E*)s->y, op->N, s->sc, rho, theta, rel_tol, iterations, restart_gradient, s->reg_kind,
+                       s->proj_kind, s->lambda, (long long)s->l21_slices, fista_batch<E>{0, nullptr, 1, 0, nullptr, 0},
+                       (unsigned*)s->resident.sync,
                        s->resident.sync ? (int)(rls_resident_sync_clear_bytes() / sizeof(unsigned)) : 0);
-  else
-    hipLaunchKernelGGL(fista_init_kernel<float2>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (float2*)s->buf[0],
-                       (float2*)s->buf[1], (float2*)s->x0, (float2*)s->res, (float2*)s->y, op->N, s->sc, rho,
-                       theta, rel_tol, iterations, restart_gradient, s->reg_kind, s->proj_kind, s->lambda,
-                       (long long)s->l21_slices, fista_batch<float2>{0, nullptr, 1, 0, nullptr, 0}, (unsigned*)s->resident.sync,
-                       s->resident.sync ? (int)(rls_resident_sync_clear_bytes() / sizeof(unsigned)) : 0);
+  });
   s->resident.clean = s->resident.sync != nullptr;
   s->enq = 0;
   s->requested = 0;
@@ -3343,10 +3311,10 @@ int32_t rls_fista_step_local_b(rls_fista* s) {
   rls_ctx* ctx = op->ctx;
   if (!s->initialised || s->use_pipe || s->use_gram) return rls_fail(ctx, RLS_E_STATE, "fista_step_local before fista_init_local_b");
   RLS_HIP(ctx, rls_enter(ctx));
-  if (op->dtype == RLS_F32)
-    RLS_TRY(fista_launch_update<float>(s, 1, fista_batch<float>{0, nullptr, 1, 0, nullptr, 0}));
-  else
-    RLS_TRY(fista_launch_update<float2>(s, 1, fista_batch<float2>{0, nullptr, 1, 0, nullptr, 0}));
+  RLS_TRY(rls_with_elem(op->dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return fista_launch_update<E>(s, 1, fista_batch<E>{0, nullptr, 1, 0, nullptr, 0});
+  }));
   return launch_status(ctx);
 }
 
@@ -3415,16 +3383,13 @@ int32_t rls_fista_init_batched(rls_fista* s, const void* B, int64_t ldb, float r
   RLS_TRY(rls_skinny_atb(ctx, op->dtype, fista_skinny_desc(s), B, ldb));  // partial rows of A^H B   (src/FISTA.jl:114)
   // (the resident launch's arrival counters are zeroed by the init kernel: every workgroup writes the same zeros)
   const int n_clear = s->resident.sync ? (int)(rls_resident_sync_clear_bytes() / sizeof(unsigned)) : 0;
-  if (op->dtype == RLS_F32)
-    hipLaunchKernelGGL(fista_init_kernel<float>, dim3((unsigned)s->nrhs), dim3(UPD_THREADS), 0, ctx->stream,
-                       (float*)s->buf[0], (float*)s->buf[1], (float*)s->x0, (float*)s->res, (float*)s->y, op->N, s->sc,
-                       rho, theta, rel_tol, iterations, restart_gradient, s->reg_kind, s->proj_kind, s->lambda,
-                       (long long)s->l21_slices, fista_batch_desc<float>(s), (unsigned*)s->resident.sync, n_clear);
-  else
-    hipLaunchKernelGGL(fista_init_kernel<float2>, dim3((unsigned)s->nrhs), dim3(UPD_THREADS), 0, ctx->stream,
-                       (float2*)s->buf[0], (float2*)s->buf[1], (float2*)s->x0, (float2*)s->res, (float2*)s->y, op->N,
-                       s->sc, rho, theta, rel_tol, iterations, restart_gradient, s->reg_kind, s->proj_kind, s->lambda,
-                       (long long)s->l21_slices, fista_batch_desc<float2>(s), (unsigned*)s->resident.sync, n_clear);
+  rls_with_elem(op->dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    hipLaunchKernelGGL(fista_init_kernel<E>, dim3((unsigned)s->nrhs), dim3(UPD_THREADS), 0, ctx->stream, (E*)s->buf[0],
+                       (E*)s->buf[1], (E*)s->x0, (E*)s->res, (E*)s->y, op->N, s->sc, rho, theta, rel_tol, iterations,
+                       restart_gradient, s->reg_kind, s->proj_kind, s->lambda, (long long)s->l21_slices, fista_batch_desc<E>(s),
+                       (unsigned*)s->resident.sync, n_clear);
+  });
   s->initialised = true;
   s->use_pipe = s->use_gram = false;
   s->restart_b = restart_gradient;
@@ -3821,15 +3786,12 @@ int32_t rls_cg_local_start(rls_cg* s, const void* x, const void* b, float rho, i
   if (!x || !b || maxiter < 0) return rls_fail(ctx, RLS_E_INVALID, "cg_local_start: bad argument");
   RLS_HIP(ctx, rls_enter(ctx));
   s->used_pipeline = false;
-  if (op->dtype == RLS_F32)
-    hipLaunchKernelGGL(cg_start_kernel<float>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (const float*)x,
-                       (const float*)b, (float*)s->u, (float*)s->r, (const float*)s->c, op->N, s->sc, rho, reltol,
-                       maxiter, typed_fuse<float>(admm_fuse_v()), col_batch<float>());
-  else
-    hipLaunchKernelGGL(cg_start_kernel<float2>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (const float2*)x,
-                       (const float2*)b, (float2*)s->u, (float2*)s->r, (const float2*)s->c, op->N, s->sc, rho, reltol,
-                       maxiter, typed_fuse<float2>(admm_fuse_v()), col_batch<float2>());
-  return launch_status(ctx);
+  return rls_with_elem(op->dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<cg_start_kernel<E>>(ctx, dim3(1), dim3(UPD_THREADS), 0, (const E*)x, (const E*)b, (E*)s->u, (E*)s->r,
+                                          (const E*)s->c, op->N, s->sc, rho, reltol, maxiter, typed_fuse<E>(admm_fuse_v()),
+                                          col_batch<E>());
+  });
 }
 
 int32_t rls_cg_local_update(rls_cg* s, void* x) {
@@ -3838,13 +3800,11 @@ int32_t rls_cg_local_update(rls_cg* s, void* x) {
   rls_ctx* ctx = op->ctx;
   if (!x) return rls_fail(ctx, RLS_E_INVALID, "cg_local_update: null x");
   RLS_HIP(ctx, rls_enter(ctx));
-  if (op->dtype == RLS_F32)
-    hipLaunchKernelGGL(cg_update_kernel<float>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (float*)x, (float*)s->u,
-                       (float*)s->r, (float*)s->c, op->N, s->sc, col_batch<float>());
-  else
-    hipLaunchKernelGGL(cg_update_kernel<float2>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (float2*)x,
-                       (float2*)s->u, (float2*)s->r, (float2*)s->c, op->N, s->sc, col_batch<float2>());
-  return launch_status(ctx);
+  return rls_with_elem(op->dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<cg_update_kernel<E>>(ctx, dim3(1), dim3(UPD_THREADS), 0, (E*)x, (E*)s->u, (E*)s->r, (E*)s->c, op->N, s->sc,
+                                           col_batch<E>());
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4227,14 +4187,11 @@ int32_t rls_admm_pre(rls_ctx* ctx, int32_t dtype, int64_t n, void* beta, const v
   RLS_HIP(ctx, rls_enter(ctx));
   unsigned grid = (unsigned)((n + 255) / 256);
   if (grid > 2048) grid = 2048;
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(admm_pre_kernel<float>, dim3(grid), dim3(256), 0, ctx->stream, (float*)beta, (const float*)beta_y,
-                       (const float*)z, (const float*)u, (const float*)x, (float*)xold, n, rho, accumulate);
-  else
-    hipLaunchKernelGGL(admm_pre_kernel<float2>, dim3(grid), dim3(256), 0, ctx->stream, (float2*)beta,
-                       (const float2*)beta_y, (const float2*)z, (const float2*)u, (const float2*)x, (float2*)xold, n,
-                       rho, accumulate);
-  return launch_status(ctx);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<admm_pre_kernel<E>>(ctx, dim3(grid), dim3(256), 0, (E*)beta, (const E*)beta_y, (const E*)z, (const E*)u,
+                                          (const E*)x, (E*)xold, n, rho, accumulate);
+  });
 }
 
 int32_t rls_admm_post(rls_ctx* ctx, int32_t dtype, int64_t n, const void* x, const void* xold, const void* z,
@@ -4243,13 +4200,11 @@ int32_t rls_admm_post(rls_ctx* ctx, int32_t dtype, int64_t n, const void* x, con
   if (!rls_dtype_ok(dtype) || n <= 0 || !x || !xold || !z || !zold || !u || !out_h)
     return rls_fail(ctx, RLS_E_INVALID, "admm_post: bad argument");
   RLS_HIP(ctx, rls_enter(ctx));
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(admm_post_kernel<float>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (const float*)x,
-                       (const float*)xold, (const float*)z, (const float*)zold, (float*)u, n, ctx->res_d);
-  else
-    hipLaunchKernelGGL(admm_post_kernel<float2>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (const float2*)x,
-                       (const float2*)xold, (const float2*)z, (const float2*)zold, (float2*)u, n, ctx->res_d);
-  RLS_TRY(launch_status(ctx));
+  RLS_TRY(rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<admm_post_kernel<E>>(ctx, dim3(1), dim3(UPD_THREADS), 0, (const E*)x, (const E*)xold, (const E*)z,
+                                           (const E*)zold, (E*)u, n, ctx->res_d);
+  }));
   RLS_HIP(ctx, hipMemcpyAsync(ctx->res_h, ctx->res_d, sizeof(float) * 6, hipMemcpyDeviceToHost, ctx->stream));
   RLS_HIP(ctx, rls_stream_wait(ctx->stream));
   for (int i = 0; i < 6; ++i) out_h[i] = ctx->res_h[i];
@@ -4371,15 +4326,12 @@ int32_t rls_admm_step(rls_admm* a, int32_t n_outer) {
     if (z_ready)
       RLS_TRY(rls_tv_single_launch(ctx, dtype, P.tv_ndims, P.tv_shape, P.tv_ntv, P.tv_dims, P.x, P.u, znew,
                                    P.prox_lambda, P.tv_iterations, &a->sc->done));
-    if (dtype == RLS_F32)
-      hipLaunchKernelGGL(admm_zu_kernel<float>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (float*)P.x,
-                         (const float*)P.xold, (float*)znew, (const float*)zcur, (float*)P.u, n, P.reg_kind,
-                         P.prox_lambda, P.proj_kind, z_ready, a->sc, cg_it, a->log, col_batch<float>(), nullptr);
-    else
-      hipLaunchKernelGGL(admm_zu_kernel<float2>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (float2*)P.x,
-                         (const float2*)P.xold, (float2*)znew, (const float2*)zcur, (float2*)P.u, n, P.reg_kind,
-                         P.prox_lambda, P.proj_kind, z_ready, a->sc, cg_it, a->log, col_batch<float2>(), nullptr);
-    RLS_TRY(launch_status(ctx));
+    RLS_TRY(rls_with_elem(dtype, [&](auto t) {
+      using E = typename decltype(t)::type;
+      return rls_launch<admm_zu_kernel<E>>(ctx, dim3(1), dim3(UPD_THREADS), 0, (E*)P.x, (const E*)P.xold, (E*)znew, (const E*)zcur,
+                                           (E*)P.u, n, P.reg_kind, P.prox_lambda, P.proj_kind, z_ready, a->sc, cg_it, a->log,
+                                           col_batch<E>(), (const cg_scalars*)nullptr);
+    }));
   }
   return 0;
 }
@@ -4463,8 +4415,7 @@ int32_t rls_admm_step_rowsharded(rls_comm* comm, rls_admm* const* plans, int32_t
                           F.xold = a->P.xold;
                           F.rho = a->P.rho;
                           F.skip = &a->sc->done;
-                          if (dtype == RLS_F32) admm_local_start<float>(a, F);
-                          else admm_local_start<float2>(a, F);
+                          rls_with_elem(dtype, [&](auto t) { admm_local_start<typename decltype(t)::type>(a, F); });
                         } else {
                           RLS_TRY(rls_cg_local_update(cg, a->P.x));
                         }
@@ -4477,8 +4428,7 @@ int32_t rls_admm_step_rowsharded(rls_comm* comm, rls_admm* const* plans, int32_t
                         if (a->P.reg_kind == RLS_REG_TV)
                           RLS_TRY(rls_tv_single_launch(ctx, dtype, a->P.tv_ndims, a->P.tv_shape, a->P.tv_ntv, a->P.tv_dims, a->P.x,
                                                        a->P.u, znew, a->P.prox_lambda, a->P.tv_iterations, &a->sc->done));
-                        if (dtype == RLS_F32) admm_local_finish<float>(a, zcur, znew);
-                        else admm_local_finish<float2>(a, zcur, znew);
+                        rls_with_elem(dtype, [&](auto t) { admm_local_finish<typename decltype(t)::type>(a, zcur, znew); });
                         ++a->enq;
                         a->requested = a->enq;
                         return launch_status(ctx);

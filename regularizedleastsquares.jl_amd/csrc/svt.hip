@@ -218,26 +218,15 @@ static int32_t svt_launch(rls_ctx* ctx, int32_t dtype, const svt_geom& G, void* 
   const int want = (int)(16 / blocks_per_cu > 1 ? 16 / blocks_per_cu : 1);
   int nw = 1;
   while (nw * 2 <= want && nw * 2 <= cap) nw *= 2;
-#define RLS_SVT_LAUNCH(EE, NWV)                                                                                        \
-  do {                                                                                                                 \
-    RLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&svt_blocks_kernel<EE, NWV>),                       \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                          \
-    hipLaunchKernelGGL((svt_blocks_kernel<EE, NWV>), dim3((unsigned)nb), dim3(64 * NWV), lds, ctx->stream, (EE*)x, G, lam); \
-  } while (0)
-  if (dtype == RLS_F32) {
-    if (nw == 1) RLS_SVT_LAUNCH(float, 1);
-    else if (nw == 2) RLS_SVT_LAUNCH(float, 2);
-    else if (nw == 4) RLS_SVT_LAUNCH(float, 4);
-    else if (nw == 8) RLS_SVT_LAUNCH(float, 8);
-    else RLS_SVT_LAUNCH(float, 16);
-  } else {
-    if (nw == 1) RLS_SVT_LAUNCH(float2, 1);
-    else if (nw == 2) RLS_SVT_LAUNCH(float2, 2);
-    else if (nw == 4) RLS_SVT_LAUNCH(float2, 4);
-    else if (nw == 8) RLS_SVT_LAUNCH(float2, 8);
-    else RLS_SVT_LAUNCH(float2, 16);
-  }
-#undef RLS_SVT_LAUNCH
+  RLS_TRY(rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_with<1, 2, 4, 8, 16>(nw, [&](auto NWV) -> int32_t {
+      RLS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&svt_blocks_kernel<E, NWV>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL((svt_blocks_kernel<E, NWV>), dim3((unsigned)nb), dim3(64 * NWV), lds, ctx->stream, (E*)x, G, lam);
+      return 0;
+    });
+  }));
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return rls_fail(ctx, (int32_t)e, hipGetErrorString(e));
   return 0;

@@ -644,10 +644,10 @@ int32_t rls_tv_single_launch(rls_ctx* ctx, int32_t dtype, int32_t ndims, const i
   Bt.count = count;
   Bt.ldv = ldv;
   Bt.skip_stride = skip_stride;
-  const bool ok = dtype == RLS_F32
-                      ? fgp_single_launch<float>(ctx, G, (const float*)xin, (const float*)add, (float*)out, lam, iters, skip, Bt)
-                      : fgp_single_launch<float2>(ctx, G, (const float2*)xin, (const float2*)add, (float2*)out, lam,
-                                                  iters, skip, Bt);
+  const bool ok = rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return fgp_single_launch<E>(ctx, G, (const E*)xin, (const E*)add, (E*)out, lam, iters, skip, Bt);
+  });
   if (!ok) return rls_fail(ctx, RLS_E_UNSUPPORTED, "tv_single_launch: image does not fit one workgroup");
   return tv_status(ctx);
 }
@@ -684,13 +684,10 @@ int32_t rls_tv_grad(rls_ctx* ctx, int32_t dtype, int32_t ndims, const int64_t* s
     return rls_fail(ctx, RLS_E_INVALID, "tv_grad: bad argument");
   if (G.goff[G.ntv] == 0) return 0;
   RLS_HIP(ctx, rls_enter(ctx));
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(grad_kernel<float>, dim3(tv_grid(G.goff[G.ntv])), dim3(256), 0, ctx->stream, (const float*)x,
-                       (float*)g, G, alpha, beta);
-  else
-    hipLaunchKernelGGL(grad_kernel<float2>, dim3(tv_grid(G.goff[G.ntv])), dim3(256), 0, ctx->stream, (const float2*)x,
-                       (float2*)g, G, alpha, beta);
-  return tv_status(ctx);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<grad_kernel<E>>(ctx, dim3(tv_grid(G.goff[G.ntv])), dim3(256), 0, (const E*)x, (E*)g, G, alpha, beta);
+  });
 }
 
 int32_t rls_tv_grad_t(rls_ctx* ctx, int32_t dtype, int32_t ndims, const int64_t* shape, int32_t ntv,
@@ -700,13 +697,10 @@ int32_t rls_tv_grad_t(rls_ctx* ctx, int32_t dtype, int32_t ndims, const int64_t*
   if (!rls_dtype_ok(dtype) || !x || !g || !make_geom(ndims, shape, ntv, dims, &G))
     return rls_fail(ctx, RLS_E_INVALID, "tv_grad_t: bad argument");
   RLS_HIP(ctx, rls_enter(ctx));
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(gradt_kernel<float>, dim3(tv_grid(G.n)), dim3(256), 0, ctx->stream, (const float*)g,
-                       (const float*)x, (float*)x, G, alpha, beta);
-  else
-    hipLaunchKernelGGL(gradt_kernel<float2>, dim3(tv_grid(G.n)), dim3(256), 0, ctx->stream, (const float2*)g,
-                       (const float2*)x, (float2*)x, G, alpha, beta);
-  return tv_status(ctx);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<gradt_kernel<E>>(ctx, dim3(tv_grid(G.n)), dim3(256), 0, (const E*)g, (const E*)x, (E*)x, G, alpha, beta);
+  });
 }
 
 int32_t rls_tv_restrict(rls_ctx* ctx, int32_t dtype, int64_t n, void* pq) {
@@ -714,11 +708,10 @@ int32_t rls_tv_restrict(rls_ctx* ctx, int32_t dtype, int64_t n, void* pq) {
   if (!rls_dtype_ok(dtype) || n < 0 || (n > 0 && !pq)) return rls_fail(ctx, RLS_E_INVALID, "tv_restrict: bad argument");
   if (n == 0) return 0;
   RLS_HIP(ctx, rls_enter(ctx));
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(restrict_kernel<float>, dim3(tv_grid(n)), dim3(256), 0, ctx->stream, (float*)pq, n);
-  else
-    hipLaunchKernelGGL(restrict_kernel<float2>, dim3(tv_grid(n)), dim3(256), 0, ctx->stream, (float2*)pq, n);
-  return tv_status(ctx);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<restrict_kernel<E>>(ctx, dim3(tv_grid(n)), dim3(256), 0, (E*)pq, n);
+  });
 }
 
 int32_t rls_tv_lincomb(rls_ctx* ctx, int32_t dtype, int64_t n, void* rs, float t3, const void* pq, float t2,
@@ -728,13 +721,10 @@ int32_t rls_tv_lincomb(rls_ctx* ctx, int32_t dtype, int64_t n, void* rs, float t
     return rls_fail(ctx, RLS_E_INVALID, "tv_lincomb: bad argument");
   if (n == 0) return 0;
   RLS_HIP(ctx, rls_enter(ctx));
-  if (dtype == RLS_F32)
-    hipLaunchKernelGGL(tv_lincomb_kernel<float>, dim3(tv_grid(n)), dim3(256), 0, ctx->stream, (float*)rs, t3,
-                       (const float*)pq, t2, (const float*)pqOld, n);
-  else
-    hipLaunchKernelGGL(tv_lincomb_kernel<float2>, dim3(tv_grid(n)), dim3(256), 0, ctx->stream, (float2*)rs, t3,
-                       (const float2*)pq, t2, (const float2*)pqOld, n);
-  return tv_status(ctx);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return rls_launch<tv_lincomb_kernel<E>>(ctx, dim3(tv_grid(n)), dim3(256), 0, (E*)rs, t3, (const E*)pq, t2, (const E*)pqOld, n);
+  });
 }
 
 int32_t rls_prox_tv_fgp(rls_ctx* ctx, int32_t dtype, int32_t ndims, const int64_t* shape, int32_t ntv,
@@ -749,8 +739,10 @@ int32_t rls_prox_tv_fgp(rls_ctx* ctx, int32_t dtype, int32_t ndims, const int64_
   if (!fused && (!workspace || workspace_bytes < need))
     return rls_fail(ctx, RLS_E_WORKSPACE, "prox_tv_fgp: workspace too small");
   RLS_HIP(ctx, rls_enter(ctx));
-  if (dtype == RLS_F32) return fgp_typed<float>(ctx, G, (float*)x, lambda, iterations, (float*)workspace);
-  return fgp_typed<float2>(ctx, G, (float2*)x, lambda, iterations, (float2*)workspace);
+  return rls_with_elem(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return fgp_typed<E>(ctx, G, (E*)x, lambda, iterations, (E*)workspace);
+  });
 }
 
 }  // extern "C"
