@@ -14,6 +14,7 @@ import ctypes as C
 import inspect
 import math
 import warnings
+from collections import namedtuple
 from typing import Callable, List, Optional, Sequence
 
 import numpy as np
@@ -72,6 +73,20 @@ def _resolve_operator(A, AHA):
 
 
 
+def _scalar_state(solver):
+    """the state that carries the solver's scalars (rho, the tolerances, POGM's gamma): its plain state, or column 0's under a
+    per-column scheduler (the one src/MultiThreading.jl:39-48 copies and hands on).  Never a batched state: init_() has put
+    that state's _plain() in its place before anything asks."""
+    st = solver.state
+    return st.states[0] if isinstance(st, AbstractMatrixSolverState) and st.states else st
+
+
+def _cold_start_only(kw, *also):
+    """the shared-A plans cover a cold start only: the keywords of init! are x0 = 0 (a scalar) and those named in `also`, no
+    others.  Anything else (a warm start, ...) goes to the per-column path, which forwards `kw` to the solver's own init_."""
+    return all(k in also or (k == "x0" and np.ndim(v) == 0 and not isinstance(v, DeviceVector) and v == 0) for k, v in kw.items())
+
+
 def _cg_is_resident(lib, plan) -> bool:
     """a cg! that runs as ONE resident launch can time out as a no-op (another tenant on the device); its status call
     repeats the solve on the per-iteration pipeline then, so x must not be consumed before that call (include/rls_mi355x.h,
@@ -82,6 +97,12 @@ def _cg_is_resident(lib, plan) -> bool:
 
 class AbstractLinearSolver:
     state = None
+
+    def _init_batched(self, b, kw, previous):
+        """init! of every column of `b` on ONE shared-A plan (scheduler = BatchedState): the initialised state, or None where
+        the solver, its settings, the keywords `kw` of init! or the shape are not covered -- init_() runs independent
+        per-column plans then.  `previous`: the batched state this solver held until now, if it held one."""
+        return None
 
     # preserved accessors (src/RegularizedLeastSquares.jl:163-183)
     def solversolution(self):
@@ -137,8 +158,50 @@ def solverconvergence(obj):
 # --------------------------------------------------------------------------------------------
 
 
-class CGNRState(AbstractSolverState):
+# what a vector state calls on its device plan: the status struct and the entry points' names
+_PlanEntries = namedtuple("_PlanEntries", "status get_status step_status destroy init set_start")
+
+
+class _PlanState(AbstractSolverState):
+    """A vector state that may own a device plan (`_plan`), of the Float32 / ComplexF32 family or -- `_plan_d` -- of the
+    Float64 / ComplexF64 one.  `_entries[_plan_d]` names either family's status struct and entry points, so every call
+    below is written once.  (By name: the functions are looked up on the `lib` of the call, which tests wrap.)"""
+
+    _entries = {}
+
+    def _refresh(self, lib):
+        e = self._entries[self._plan_d]
+        st = e.status()
+        check(self.x.ctx.handle, getattr(lib, e.get_status)(self._plan, C.byref(st)), e.get_status)
+        return self._take(st)
+
+    def _step_status(self, lib, n):
+        """advance n iterations and read the status back in ONE call (one host synchronisation): rls_*_step_status"""
+        e = self._entries[self._plan_d]
+        st = e.status()
+        check(self.x.ctx.handle, getattr(lib, e.step_status)(self._plan, int(n), C.byref(st)), e.step_status)
+        return self._take(st)
+
+    def _drop_plan(self, lib):
+        if self._plan:
+            getattr(lib, self._entries[self._plan_d].destroy)(self._plan)
+        self._plan, self._plan_d = None, False
+
+    def __del__(self):
+        try:
+            if self._plan and self.x is not None and self.x.ctx.handle:
+                self._drop_plan(self.x.ctx.lib)
+        except Exception:
+            pass
+        self._plan = None
+
+
+class CGNRState(_PlanState):
     """src/CGNR.jl:13-24.  x0 is the normal-equation residual (x₀ in the reference)."""
+
+    _entries = {False: _PlanEntries(CgnrStatus, "rls_cgnr_get_status", "rls_cgnr_step_status", "rls_cgnr_destroy", "rls_cgnr_init", None),
+                True: _PlanEntries(CgnrStatusD, "rls_cgnr_get_status_d", "rls_cgnr_step_status_d", "rls_cgnr_destroy_d", "rls_cgnr_init_d",
+                                   None)}
 
     def __init__(self, relTol):
         self.x = self.x0 = self.pl = self.vl = None
@@ -149,30 +212,6 @@ class CGNRState(AbstractSolverState):
         self._plan = None
         self._plan_d = False   # the plan is a Float64 / ComplexF64 one (rls_cgnr_*_d)
         self._done = False
-
-    def _refresh(self, lib):
-        if self._plan_d:
-            st = CgnrStatusD()
-            check(self.x.ctx.handle, lib.rls_cgnr_get_status_d(self._plan, C.byref(st)), "rls_cgnr_get_status_d")
-            return self._take(st)
-        st = CgnrStatus()
-        check(self.x.ctx.handle, lib.rls_cgnr_get_status(self._plan, C.byref(st)), "rls_cgnr_get_status")
-        return self._take(st)
-
-    def _step_status(self, lib, n):
-        """advance n iterations and read the status back in ONE call (one host synchronisation): rls_cgnr_step_status"""
-        if self._plan_d:
-            st = CgnrStatusD()
-            check(self.x.ctx.handle, lib.rls_cgnr_step_status_d(self._plan, int(n), C.byref(st)), "rls_cgnr_step_status_d")
-            return self._take(st)
-        st = CgnrStatus()
-        check(self.x.ctx.handle, lib.rls_cgnr_step_status(self._plan, int(n), C.byref(st)), "rls_cgnr_step_status")
-        return self._take(st)
-
-    def _drop_plan(self, lib):
-        if self._plan:
-            (lib.rls_cgnr_destroy_d if self._plan_d else lib.rls_cgnr_destroy)(self._plan)
-        self._plan, self._plan_d = None, False
 
     def _take(self, st):
         cplx = self.x.dtype.kind == "c"
@@ -191,14 +230,6 @@ class CGNRState(AbstractSolverState):
         if self._plan:
             self._refresh(self.x.ctx.lib)
         return {"residual": self._residual}  # src/CGNR.jl:136
-
-    def __del__(self):
-        try:
-            if self._plan and self.x is not None and self.x.ctx.handle:
-                self._drop_plan(self.x.ctx.lib)
-        except Exception:
-            pass
-        self._plan = None
 
 
 class CGNR(AbstractKrylovSolver):
@@ -224,10 +255,18 @@ class CGNR(AbstractKrylovSolver):
         self.state = CGNRState(_eps_of(self._op, relTol))
 
     def _new_state(self):
-        st = self.state
-        if isinstance(st, AbstractMatrixSolverState) and not isinstance(st, BatchedState):
-            st = st.states[0]
-        return CGNRState(st.relTol)
+        return CGNRState(_scalar_state(self).relTol)
+
+    def _init_batched(self, b, kw, previous):
+        if not (isinstance(b, DeviceMatrix) and b.N > 1 and not self.constr and _cold_start_only(kw)
+                and not isinstance(self.normalizeReg, MeasurementBasedNormalization)):  # per-column lambda: not batched
+            return None
+        try:
+            st = CgnrBatchedState(self, b)
+            st.init(b, _scalar_state(self))
+            return st
+        except _lib.RLSError:
+            return None  # shape not covered by the one-pass kernel
 
     def init_(self, state: CGNRState, b: DeviceVector, x0=0):
         """init!(solver, state, b; x0 = 0)  src/CGNR.jl:91-130"""
@@ -238,12 +277,8 @@ class CGNR(AbstractKrylovSolver):
         if self._op.double and not self.use_device_plan_f64:
             return self._init_from_primitives(state, b)
         self._prepare(state, b)
-        if state._plan_d:
-            check(b.ctx.handle, lib.rls_cgnr_init_d(state._plan, b.ptr, float(self.L2.lam), state.relTol, self.iterations),
-                  "rls_cgnr_init_d")
-        else:
-            check(b.ctx.handle, lib.rls_cgnr_init(state._plan, b.ptr, float(self.L2.lam), state.relTol, self.iterations),
-                  "rls_cgnr_init")
+        init = state._entries[state._plan_d].init
+        check(b.ctx.handle, getattr(lib, init)(state._plan, b.ptr, float(self.L2.lam), state.relTol, self.iterations), init)
         self._after_init(state)
 
     # ---- Float64 / ComplexF64: the reference's loop on the L1 protocol (rls_*_d), statement by statement ----------------------------
@@ -525,8 +560,13 @@ def _set_start(x, start):
         x.fill_(start)
 
 
-class FISTAState(AbstractSolverState):
+class FISTAState(_PlanState):
     """src/FISTA.jl:15-27"""
+
+    _entries = {False: _PlanEntries(FistaStatus, "rls_fista_get_status", "rls_fista_step_status", "rls_fista_destroy", "rls_fista_init",
+                                    "rls_fista_set_start"),
+                True: _PlanEntries(FistaStatusD, "rls_fista_get_status_d", "rls_fista_step_status_d", "rls_fista_destroy_d",
+                                   "rls_fista_init_d", "rls_fista_set_start_d")}
 
     def __init__(self, rho, theta, relTol):
         self.x = self.x0 = self.xold = self.res = None
@@ -540,31 +580,6 @@ class FISTAState(AbstractSolverState):
         self._plan_d = False   # the plan is a Float64 / ComplexF64 one (rls_fista_*_d)
         self._bufs = None
         self._done = False
-
-    def _refresh(self, lib):
-        h = self._bufs[0].ctx.handle
-        if self._plan_d:
-            st = FistaStatusD()
-            check(h, lib.rls_fista_get_status_d(self._plan, C.byref(st)), "rls_fista_get_status_d")
-            return self._take(st)
-        st = FistaStatus()
-        check(h, lib.rls_fista_get_status(self._plan, C.byref(st)), "rls_fista_get_status")
-        return self._take(st)
-
-    def _step_status(self, lib, n):
-        """advance n iterations and read the status back in ONE call (rls_fista_step_status)"""
-        if self._plan_d:
-            st = FistaStatusD()
-            check(self._bufs[0].ctx.handle, lib.rls_fista_step_status_d(self._plan, int(n), C.byref(st)), "rls_fista_step_status_d")
-            return self._take(st)
-        st = FistaStatus()
-        check(self._bufs[0].ctx.handle, lib.rls_fista_step_status(self._plan, int(n), C.byref(st)), "rls_fista_step_status")
-        return self._take(st)
-
-    def _drop_plan(self, lib):
-        if self._plan:
-            (lib.rls_fista_destroy_d if self._plan_d else lib.rls_fista_destroy)(self._plan)
-        self._plan, self._plan_d = None, False
 
     def _take(self, st):
         self.theta, self.thetaold = st.theta, st.theta_old
@@ -584,14 +599,6 @@ class FISTAState(AbstractSolverState):
             self._refresh(self.x.ctx.lib)
             return {"residual": self._residual}
         return {"residual": self.res.norm()}  # src/FISTA.jl:131
-
-    def __del__(self):
-        try:
-            if self._plan and self._bufs and self._bufs[0].ctx.handle:
-                self._drop_plan(self._bufs[0].ctx.lib)
-        except Exception:
-            pass
-        self._plan = None
 
 
 class FISTA(AbstractProximalGradientSolver):
@@ -658,8 +665,20 @@ class FISTA(AbstractProximalGradientSolver):
         return kind, float(r.lam), slices, pk
 
     def _new_state(self):
-        s = self.state.states[0] if isinstance(self.state, AbstractMatrixSolverState) else self.state
+        s = _scalar_state(self)
         return FISTAState(s.rho, s.theta if s.iteration == 0 else 1.0, s.relTol)
+
+    def _init_batched(self, b, kw, previous):
+        if not (type(self) is FISTA and isinstance(b, DeviceMatrix) and b.N > 1 and self.A is not None and not self._op.double
+                and (fused := self._fused_kinds()) is not None and fused[0] != REG_TV
+                and not isinstance(self.normalizeReg, MeasurementBasedNormalization) and _cold_start_only(kw, "theta")):
+            return None
+        try:
+            st = FistaBatchedState(self, b)
+            st.init(b, _scalar_state(self), fused, kw.get("theta", 1))
+            return st
+        except _lib.RLSError:
+            return None  # e.g. M or N not a multiple of 16
 
     def init_(self, state: FISTAState, b: DeviceVector, x0=0, theta=1):
         """init!(solver, state, b; x0 = 0, theta = 1)   src/FISTA.jl:94-129"""
@@ -712,21 +731,15 @@ class FISTA(AbstractProximalGradientSolver):
                 check(h, st_tv, "rls_fista_set_reg_tv")
         if fused is not None:
             kind, lam_, slices, pk = fused
-            if dbl:
-                check(h, lib.rls_fista_init_d(state._plan, b.ptr, state.rho, float(theta), state.relTol, self.iterations,
-                                              1 if self.restart == "gradient" else 0), "rls_fista_init_d")
-            else:
-                if kind != REG_TV:
-                    check(h, lib.rls_fista_set_reg(state._plan, kind, lam_, slices, pk), "rls_fista_set_reg")
-                check(h, lib.rls_fista_init(state._plan, b.ptr, state.rho, float(theta), state.relTol, self.iterations,
-                                            1 if self.restart == "gradient" else 0), "rls_fista_init")
+            e = state._entries[state._plan_d]
+            if not dbl and kind != REG_TV:   # (the Float64 plan and the TV launch have their regulariser set above)
+                check(h, lib.rls_fista_set_reg(state._plan, kind, lam_, slices, pk), "rls_fista_set_reg")
+            check(h, getattr(lib, e.init)(state._plan, b.ptr, state.rho, float(theta), state.relTol, self.iterations,
+                                          1 if self.restart == "gradient" else 0), e.init)
             if isinstance(start, DeviceVector) or start != 0:
                 # (`state.x .= x0` broadcasts a scalar, src/FISTA.jl:120)
                 xs = start if isinstance(start, DeviceVector) else DeviceVector.from_host(np.full(N, start, dtype=b.dtype), b.ctx)
-                if dbl:
-                    check(h, lib.rls_fista_set_start_d(state._plan, xs.ptr, xs.n), "rls_fista_set_start_d")
-                else:
-                    check(h, lib.rls_fista_set_start(state._plan, xs.ptr, xs.n), "rls_fista_set_start")
+                check(h, getattr(lib, e.set_start)(state._plan, xs.ptr, xs.n), e.set_start)
         else:
             # generic path from primitives (TV prox etc.)
             if self.A is None:
@@ -908,8 +921,21 @@ class ADMM(AbstractPrimalDualSolver):
         self.state = ADMMState(len(self.reg), self.rho, _eps_of(self._op, absTol), _eps_of(self._op, relTol), tolInner)
 
     def _new_state(self):
-        s = self.state.states[0] if isinstance(self.state, AbstractMatrixSolverState) else self.state
+        s = _scalar_state(self)
         return ADMMState(len(self.reg), self.rho, s.absTol, s.relTol, s.tolInner)
+
+    def _init_batched(self, b, kw, previous):
+        if not (type(self) is ADMM and self.precon is None and isinstance(b, DeviceMatrix) and b.N > 1 and self.A is not None and not kw
+                and self.use_device_plan and self._all_identity() and len(self.reg) == 1 and self.vary_rho == "none"
+                and not isinstance(self.normalizeReg, (MeasurementBasedNormalization, SystemMatrixBasedNormalization))):
+            return None
+        try:
+            # (the one batched state that is taken over: plan, state matrices and all, while K stays the same)
+            st = previous if isinstance(previous, AdmmBatchedState) and previous.K == b.N else AdmmBatchedState(self, b)
+            st.init(b)
+            return st
+        except _lib.RLSError:
+            return None  # shape or regulariser not covered by the batched plan
 
     def _all_identity(self):
         return all(getattr(t, "identity", False) for t in self.regTrafo)
@@ -1314,6 +1340,22 @@ class _ProxGradState(AbstractSolverState):
         return {"residual": self.res.norm()}
 
 
+def _pgm_init_batched(self, b, kw, previous):
+    """OptISTA._init_batched and POGM._init_batched"""
+    if not (type(self) in (OptISTA, POGM) and isinstance(b, DeviceMatrix) and b.N > 1 and self.A is not None
+            and isinstance(self._op, OperatorHandle) and not self._op.double
+            and (fus := _fusable_kinds(self.reg, self.proj if type(self) is POGM else [])) is not None
+            and not isinstance(self.normalizeReg, MeasurementBasedNormalization) and _cold_start_only(kw, "theta")):
+        return None
+    ref = _scalar_state(self)
+    try:
+        st = PgmBatchedState(self, b)
+        st.init(b, ref, fus, kw.get("theta", 1))
+        return st
+    except _lib.RLSError:
+        return None  # e.g. M or N not a multiple of 16
+
+
 class OptISTA(AbstractProximalGradientSolver):
     """src/OptISTA.jl:61-110 (ctor), :129-160 (init!), :169-209 (iterate)"""
 
@@ -1330,8 +1372,10 @@ class OptISTA(AbstractProximalGradientSolver):
                                     ("x", "x0", "y", "z", "zold", "res"))
 
     def _new_state(self):
-        s = self.state.states[0] if isinstance(self.state, AbstractMatrixSolverState) else self.state
+        s = _scalar_state(self)
         return _ProxGradState(s.rho, 1.0, s.relTol, s._names)
+
+    _init_batched = _pgm_init_batched
 
     def init_(self, st, b: DeviceVector, x0=0, theta=1):
         f32 = _rt_of(self._op)
@@ -1582,10 +1626,12 @@ class POGM(AbstractProximalGradientSolver):
         self.state.sigma_fac = float(sigma_fac)
 
     def _new_state(self):
-        s = self.state.states[0] if isinstance(self.state, AbstractMatrixSolverState) else self.state
+        s = _scalar_state(self)
         n = _ProxGradState(s.rho, 1.0, s.relTol, s._names)
         n.gamma, n.sigma, n.sigma_fac = s.gamma, 1.0, s.sigma_fac
         return n
+
+    _init_batched = _pgm_init_batched
 
     def init_(self, st, b: DeviceVector, x0=0, theta=1):
         start = _start_vector(x0, b, self._op.N, st)
@@ -2109,6 +2155,14 @@ class Kaczmarz(AbstractRowActionSolver):
     def _new_state(self):
         return KaczmarzState()
 
+    def _init_batched(self, b, kw, previous):
+        """all columns in one launch, one workgroup per column"""
+        if not isinstance(b, DeviceMatrix):
+            return None
+        self.state = st = KaczmarzState()  # (in place at once: the last solve's buffers go before this one's are allocated)
+        self.init_(st, b, **kw)
+        return st
+
     def _upload_order(self, st, order):
         ctx = self.A_in.ctx
         st.usedIndices = np.asarray(order, dtype=np.int64)
@@ -2265,37 +2319,44 @@ class MultiThreadingState(AbstractMatrixSolverState):
 
 
 class BatchedState(AbstractMatrixSolverState):
-    """Backend-specific scheduler for matrix right-hand sides: the K columns advance TOGETHER and share
-    one pass over A per iteration (rls_cgnr_*_batched).  Same semantics as MultiThreadingState --
-    independent per-column scalars and per-column retirement -- so results are those of column-by-column
-    solves.  Solvers / shapes the fused batched plan does not cover fall back to MultiThreadingState."""
+    """Backend-specific scheduler for matrix right-hand sides: the K columns advance TOGETHER and share one pass over A per
+    iteration.  Same semantics as MultiThreadingState -- independent per-column scalars and per-column retirement -- so
+    results are those of column-by-column solves.  Solvers / shapes no shared-A plan covers fall back to MultiThreadingState.
+
+    As `scheduler=BatchedState` this class is the token init_() takes; as a base class it holds what every solver's batched
+    state does the same way.  A subclass allocates its N x K state matrices and creates its plan (`__init__`), initialises
+    every column (`init`), says which vector state the solver goes back to (`_plain`), and names the rest as data."""
+
+    _status = None          # the status struct, one per column
+    _step_fn = None         # entry point that advances every live column: fn(plan, n)
+    _status_fn = None       # entry point that fills K status structs: fn(plan, structs, *_status_args)
+    _status_args = ()
+    _destroy_fns = ()       # (attribute that holds the handle, entry point) in the order of destruction
+    _steps_capped_at_N = False
 
     def __init__(self, solver, B: DeviceMatrix):
         self.states = []
         self.active = [True] * B.N
         self.solver = solver
         self.K = B.N
-        op = solver._op
-        ctx = B.ctx
-        N = op.N
-        self.X, self.R, self.P, self.V = (DeviceMatrix(N, B.N, B.dtype, ctx) for _ in range(4))
-        lib, h = ctx.lib, ctx.handle
-        plan = C.c_void_p()
-        check(h, lib.rls_cgnr_create_batched(op.handle, B.N, self.X.ptr, self.R.ptr, self.P.ptr, self.V.ptr, N,
-                                             C.byref(plan)), "rls_cgnr_create_batched")
-        self._plan = plan
-        self._keep = (op, ctx)
+        self._plan = None
+        self._keep = (solver._op, B.ctx)  # destruction order: plan before operator before context
         self.iteration = 0
 
     def _step(self, n):
-        ctx = self.X.ctx
-        check(ctx.handle, ctx.lib.rls_cgnr_step(self._plan, int(n)), "rls_cgnr_step")
+        ctx = self._keep[1]
+        check(ctx.handle, getattr(ctx.lib, self._step_fn)(self._plan, int(n)), self._step_fn)
 
     def status(self):
-        st = (CgnrStatus * self.K)()
-        ctx = self.X.ctx
-        check(ctx.handle, ctx.lib.rls_cgnr_get_status_batched(self._plan, st), "rls_cgnr_get_status_batched")
+        st = (self._status * self.K)()
+        ctx = self._keep[1]
+        check(ctx.handle, getattr(ctx.lib, self._status_fn)(self._plan, st, *self._status_args), self._status_fn)
         return list(st)
+
+    def _run_steps(self):
+        """the steps a solve without callbacks enqueues at once (columns that are done ignore them)"""
+        it = self.solver.iterations
+        return min(it, self.solver._op.N) if self._steps_capped_at_N else it
 
     def convergence(self):
         return [{"residual": s.residual} for s in self.status()]
@@ -2305,57 +2366,74 @@ class BatchedState(AbstractMatrixSolverState):
 
     def __del__(self):
         try:
-            if self._plan and self.X.ctx.handle:
-                self.X.ctx.lib.rls_cgnr_destroy(self._plan)
+            ctx = self._keep[1]
+            if self._plan and ctx.handle:
+                for attr, fn in self._destroy_fns:
+                    getattr(ctx.lib, fn)(getattr(self, attr))
         except Exception:
             pass
         self._plan = None
+
+
+class CgnrBatchedState(BatchedState):
+    """BatchedState for CGNR (rls_cgnr_*_batched)"""
+
+    _status, _step_fn, _status_fn = CgnrStatus, "rls_cgnr_step", "rls_cgnr_get_status_batched"
+    _destroy_fns = (("_plan", "rls_cgnr_destroy"),)
+    _steps_capped_at_N = True   # done(): iteration >= min(iterations, N)   src/CGNR.jl:181-185
+
+    def __init__(self, solver, B: DeviceMatrix):
+        super().__init__(solver, B)
+        op, ctx, N = solver._op, B.ctx, solver._op.N
+        self.X, self.R, self.P, self.V = (DeviceMatrix(N, B.N, B.dtype, ctx) for _ in range(4))
+        plan = C.c_void_p()
+        check(ctx.handle, ctx.lib.rls_cgnr_create_batched(op.handle, B.N, self.X.ptr, self.R.ptr, self.P.ptr, self.V.ptr, N,
+                                                          C.byref(plan)), "rls_cgnr_create_batched")
+        self._plan = plan
+
+    def init(self, B: DeviceMatrix, ref):
+        """init! of every column.  `ref`: the plain state the solver's scalars come from"""
+        solver, ctx = self.solver, B.ctx
+        self.relTol = ref.relTol
+        check(ctx.handle, ctx.lib.rls_cgnr_init_batched(self._plan, B.ptr, B.lda, float(solver.L2.lam), float(self.relTol),
+                                                        solver.iterations), "rls_cgnr_init_batched")
+
+    def _plain(self):
+        return CGNRState(self.relTol)
 
 
 class FistaBatchedState(BatchedState):
     """BatchedState for FISTA: the K extrapolated points share one pass over A per product (rls_fista_*_batched);
     prox, momentum and `done` are per column, exactly as K independent solves."""
 
+    _status, _step_fn, _status_fn = FistaStatus, "rls_fista_step", "rls_fista_get_status_batched"
+    _destroy_fns = (("_plan", "rls_fista_destroy"),)
+
     def __init__(self, solver, B: DeviceMatrix):
-        self.states = []
-        self.active = [True] * B.N
-        self.solver = solver
-        self.K = B.N
+        super().__init__(solver, B)
         op, ctx, N = solver._op, B.ctx, solver._op.N
         self.X, self.Xold, self.X0, self.RES = (DeviceMatrix(N, B.N, B.dtype, ctx) for _ in range(4))
-        lib, h = ctx.lib, ctx.handle
         plan = C.c_void_p()
-        check(h, lib.rls_fista_create_batched(op.handle, B.N, self.X.ptr, self.X0.ptr, self.Xold.ptr, self.RES.ptr, N,
-                                              C.byref(plan)), "rls_fista_create_batched")
+        check(ctx.handle, ctx.lib.rls_fista_create_batched(op.handle, B.N, self.X.ptr, self.X0.ptr, self.Xold.ptr, self.RES.ptr, N,
+                                                           C.byref(plan)), "rls_fista_create_batched")
         self._plan = plan
-        self._keep = (op, ctx)
-        self.iteration = 0
-        self._destroy = lib.rls_fista_destroy
 
-    def _step(self, n):
-        ctx = self.X.ctx
-        check(ctx.handle, ctx.lib.rls_fista_step(self._plan, int(n)), "rls_fista_step")
-
-    def status(self):
-        st = (FistaStatus * self.K)()
-        ctx = self.X.ctx
-        check(ctx.handle, ctx.lib.rls_fista_get_status_batched(self._plan, st), "rls_fista_get_status_batched")
-        return list(st)
-
-    def convergence(self):
-        return [{"residual": s.residual} for s in self.status()]
+    def init(self, B: DeviceMatrix, ref, fused, theta):
+        """init! of every column.  `ref`: the plain state the solver's scalars come from; `fused`: solver._fused_kinds()"""
+        solver, ctx = self.solver, B.ctx
+        lib, h = ctx.lib, ctx.handle
+        self.rho, self.relTol = ref.rho, ref.relTol
+        kind, lam_, slices, pk = fused
+        check(h, lib.rls_fista_set_reg(self._plan, kind, lam_, slices, pk), "rls_fista_set_reg")
+        check(h, lib.rls_fista_init_batched(self._plan, B.ptr, B.lda, float(self.rho), float(theta), float(self.relTol),
+                                            solver.iterations, 1 if solver.restart == "gradient" else 0), "rls_fista_init_batched")
 
     def solutions(self) -> List[DeviceVector]:
         # state.x of column j is X when its iteration count is even, Xold when odd (src/FISTA.jl:144-146)
         return [(self.Xold if s.iteration & 1 else self.X).column(j) for j, s in enumerate(self.status())]
 
-    def __del__(self):
-        try:
-            if self._plan and self.X.ctx.handle:
-                self.X.ctx.lib.rls_fista_destroy(self._plan)
-        except Exception:
-            pass
-        self._plan = None
+    def _plain(self):
+        return FISTAState(self.rho, 1, self.relTol)
 
 
 def _pgm_batched_table(solver, theta):
@@ -2387,11 +2465,11 @@ class PgmBatchedState(BatchedState):
     buffers every iteration and columns retire at different iterations: column j's x is in X when its own iteration count
     is even, in Y when it is odd."""
 
+    _status, _step_fn, _status_fn = PgmStatus, "rls_pgm_step_batched", "rls_pgm_get_status_batched"
+    _destroy_fns = (("_plan", "rls_pgm_destroy_batched"),)
+
     def __init__(self, solver, B: DeviceMatrix):
-        self.states = []
-        self.active = [True] * B.N
-        self.solver = solver
-        self.K = B.N
+        super().__init__(solver, B)
         op, ctx, N = solver._op, B.ctx, solver._op.N
         self.kind = 0 if isinstance(solver, OptISTA) else 1
         self.restart = self.kind == 1 and solver.restart == "gradient"
@@ -2402,8 +2480,6 @@ class PgmBatchedState(BatchedState):
                                                          self.W.ptr if self.W is not None else None, self.OLD.ptr,
                                                          self.RES.ptr, self.X0.ptr, N, C.byref(plan)), "rls_pgm_create_batched")
         self._plan = plan
-        self._keep = (op, ctx)
-        self.iteration = 0
         self._hist = None
 
     def init(self, B: DeviceMatrix, ref, fus, theta):
@@ -2433,15 +2509,8 @@ class PgmBatchedState(BatchedState):
         self.iteration = 0
         self.active = [True] * self.K
 
-    def _step(self, n):
-        ctx = self.X.ctx
-        check(ctx.handle, ctx.lib.rls_pgm_step_batched(self._plan, int(n)), "rls_pgm_step_batched")
-
     def status(self):
-        st = (PgmStatus * self.K)()
-        ctx = self.X.ctx
-        check(ctx.handle, ctx.lib.rls_pgm_get_status_batched(self._plan, st), "rls_pgm_get_status_batched")
-        out = list(st)
+        out = super().status()
         if self._hist is not None:  # index-only scalars: the host's recurrence at the column's own count
             for s_ in out:
                 hv = self._hist[s_.iteration]
@@ -2468,32 +2537,25 @@ class PgmBatchedState(BatchedState):
             st.sigma, st.sigma_fac = 1.0, self.sigma_fac
         return st
 
-    def __del__(self):
-        try:
-            if self._plan and self.X.ctx.handle:
-                self.X.ctx.lib.rls_pgm_destroy_batched(self._plan)
-        except Exception:
-            pass
-        self._plan = None
-
 
 class AdmmBatchedState(BatchedState):
     """BatchedState for ADMM (one regulariser, identity regTrafo, vary_rho = :none): the K columns' cg! iterations share
     one pass over A per product (rls_cg_create_batched + rls_admm_step on N x K matrices); prox, z / u updates, the
     residual norms and `done` are per column, exactly as K independent solves (src/MultiThreading.jl:30-79)."""
 
+    _status, _step_fn, _status_fn, _status_args = AdmmStatus, "rls_admm_step", "rls_admm_get_status_batched", (None, 0)
+    _destroy_fns = (("_plan", "rls_admm_destroy"), ("_cg", "rls_cg_destroy"))
+    _steps_capped_at_N = True   # (as CGNR's, though ADMM's done() knows no such cap: columns that are done ignore the rest)
+
     def __init__(self, solver, B: DeviceMatrix):
-        self.states = []
-        self.active = [True] * B.N
-        self.solver = solver
-        self.K = B.N
+        super().__init__(solver, B)
         op, ctx, N = solver._op, B.ctx, solver._op.N
         mk = lambda: DeviceMatrix(N, B.N, B.dtype, ctx)
         self.x, self.xold, self.beta, self.beta_y, self.u0 = mk(), mk(), mk(), mk(), mk()
         self._zbufs = (mk(), mk())
         self.cg_u, self.cg_r, self.cg_c = mk(), mk(), mk()
         self.u = [self.u0]
-        ref = solver.state.states[0] if isinstance(solver.state, AbstractMatrixSolverState) and solver.state.states else solver.state
+        ref = _scalar_state(solver)
         self.absTol, self.relTol, self.tolInner = ref.absTol, ref.relTol, ref.tolInner
         self.rho = np.full(1, solver.rho, np.float32)
         self.sigma_abs = np.float32(np.sqrt(np.float32(B.M))) * self.absTol
@@ -2505,8 +2567,6 @@ class AdmmBatchedState(BatchedState):
         plan = C.c_void_p()
         check(h, lib.rls_admm_create(cg, C.byref(plan)), "rls_admm_create")
         self._plan = plan
-        self._keep = (op, ctx)
-        self.iteration = 0
 
     def init(self, B: DeviceMatrix):
         solver, ctx = self.solver, self.x.ctx
@@ -2519,16 +2579,7 @@ class AdmmBatchedState(BatchedState):
             raise _lib.RLSError("batched ADMM: this configuration does not run as a device plan")
         check(ctx.handle, ctx.lib.rls_admm_init(self._plan, C.byref(P)), "rls_admm_init")
         self.iteration = 0
-
-    def _step(self, n):
-        ctx = self.x.ctx
-        check(ctx.handle, ctx.lib.rls_admm_step(self._plan, int(n)), "rls_admm_step")
-
-    def status(self):
-        st = (AdmmStatus * self.K)()
-        ctx = self.x.ctx
-        check(ctx.handle, ctx.lib.rls_admm_get_status_batched(self._plan, st, None, 0), "rls_admm_get_status_batched")
-        return list(st)
+        self.active = [True] * self.K
 
     def cg_iterations(self):
         """per column: the inner cg! iteration counts of its outer iterations"""
@@ -2545,14 +2596,8 @@ class AdmmBatchedState(BatchedState):
     def solutions(self) -> List[DeviceVector]:
         return [self.x.column(j) for j in range(self.K)]
 
-    def __del__(self):
-        try:
-            if self._plan and self.x.ctx.handle:
-                self.x.ctx.lib.rls_admm_destroy(self._plan)
-                self.x.ctx.lib.rls_cg_destroy(self._cg)
-        except Exception:
-            pass
-        self._plan = None
+    def _plain(self):
+        return ADMMState(len(self.solver.reg), self.solver.rho, self.absTol, self.relTol, self.tolInner)
 
 
 def _columns(b) -> List[DeviceVector]:
@@ -2575,97 +2620,34 @@ def _check_eltype(solver, b):
         raise TypeError(f"element types differ: the operator is {np.dtype(want)}, b is {np.dtype(b.dtype)}")
 
 
+def _leave_batched(solver):
+    """a batched state gives way to the solver's vector state with the same scalars (every path of init_ starts from that
+    one); returns the batched state, or None if the solver held none"""
+    st = solver.state
+    if isinstance(st, BatchedState):
+        solver.state = st._plain()
+        return st
+    return None
+
+
 def init_(solver: AbstractLinearSolver, b, scheduler=SequentialState, **kw):
     """init!(solver, b; kwargs...)   src/RegularizedLeastSquares.jl:190, src/MultiThreading.jl:30-43"""
     _check_eltype(solver, b)
-    if isinstance(solver.state, PgmBatchedState):
-        solver.state = solver.state._plain()  # (a matrix right-hand side below builds its state from this one)
-    if isinstance(b, DeviceVector):
-        if isinstance(solver.state, AdmmBatchedState):
-            ref = solver.state
-            solver.state = ADMMState(len(solver.reg), solver.rho, ref.absTol, ref.relTol, ref.tolInner)
-        if isinstance(solver.state, FistaBatchedState):
-            solver.state = FISTAState(solver.state.rho, 1, solver.state.relTol)
-        elif isinstance(solver.state, BatchedState):
-            solver.state = CGNRState(solver.state.relTol)
-        elif isinstance(solver.state, AbstractMatrixSolverState):
+    vector = isinstance(b, DeviceVector)
+    if scheduler is BatchedState and not vector:
+        # (the state that leaves lives until its successor is initialised, and no longer)
+        st = solver._init_batched(b, kw, _leave_batched(solver))
+        if st is not None:
+            solver.state = st
+            return
+        scheduler = MultiThreadingState  # not covered by a shared-A plan: independent per-column plans
+    else:
+        _leave_batched(solver)
+    if vector:
+        if isinstance(solver.state, AbstractMatrixSolverState):
             solver.state = solver.state.states[0]  # :39-43
         solver.init_(solver.state, b, **kw)
         return
-    if scheduler is BatchedState and isinstance(solver, Kaczmarz) and isinstance(b, DeviceMatrix):
-        solver.state = KaczmarzState()
-        solver.init_(solver.state, b, **kw)  # all columns in one launch, one workgroup per column
-        return
-    if scheduler is BatchedState:
-        # the shared-A plans cover only the keyword arguments listed here; anything else (a warm start x0, ...) goes to
-        # the per-column path below, which forwards **kw to the solver's own init_ (and raises what it does not support)
-        kw_cgnr_ok = all(k == "x0" and np.ndim(v) == 0 and v == 0 for k, v in kw.items())
-        kw_fista_ok = all((k == "theta") or (k == "x0" and np.ndim(v) == 0 and not isinstance(v, DeviceVector) and v == 0)
-                          for k, v in kw.items())
-        if (isinstance(solver, CGNR) and isinstance(b, DeviceMatrix) and b.N > 1 and not solver.constr and kw_cgnr_ok
-                and not isinstance(solver.normalizeReg, MeasurementBasedNormalization)):  # per-column lambda: not batched
-            try:
-                st = BatchedState(solver, b)
-                lib, h = b.ctx.lib, b.ctx.handle
-                relTol = (solver.state.states[0] if isinstance(solver.state, AbstractMatrixSolverState) and solver.state.states
-                          else solver.state).relTol if not isinstance(solver.state, BatchedState) else solver.state.relTol
-                st.relTol = relTol
-                check(h, lib.rls_cgnr_init_batched(st._plan, b.ptr, b.lda, float(solver.L2.lam), float(relTol),
-                                                   solver.iterations), "rls_cgnr_init_batched")
-                solver.state = st
-                return
-            except _lib.RLSError:
-                pass  # shape not covered by the one-pass kernel: independent per-column plans instead
-        if (type(solver) is FISTA and isinstance(b, DeviceMatrix) and b.N > 1 and solver.A is not None and not solver._op.double
-                and solver._fused_kinds() is not None and solver._fused_kinds()[0] != REG_TV
-                and not isinstance(solver.normalizeReg, MeasurementBasedNormalization)
-                and kw_fista_ok):
-            try:
-                st = FistaBatchedState(solver, b)
-                lib, h = b.ctx.lib, b.ctx.handle
-                ref = solver.state.states[0] if isinstance(solver.state, AbstractMatrixSolverState) and solver.state.states else solver.state
-                st.rho, st.relTol = ref.rho, ref.relTol
-                kind, lam_, slices, pk = solver._fused_kinds()
-                check(h, lib.rls_fista_set_reg(st._plan, kind, lam_, slices, pk), "rls_fista_set_reg")
-                check(h, lib.rls_fista_init_batched(st._plan, b.ptr, b.lda, float(st.rho), float(kw.get("theta", 1)),
-                                                    float(st.relTol), solver.iterations,
-                                                    1 if solver.restart == "gradient" else 0), "rls_fista_init_batched")
-                solver.state = st
-                return
-            except _lib.RLSError:
-                pass  # e.g. M or N not a multiple of 16: independent per-column plans instead
-        if (type(solver) in (OptISTA, POGM) and isinstance(b, DeviceMatrix) and b.N > 1 and solver.A is not None
-                and isinstance(solver._op, OperatorHandle) and not solver._op.double
-                and _fusable_kinds(solver.reg, solver.proj if type(solver) is POGM else []) is not None
-                and not isinstance(solver.normalizeReg, MeasurementBasedNormalization)
-                and kw_fista_ok):
-            ref = solver.state.states[0] if isinstance(solver.state, AbstractMatrixSolverState) and solver.state.states else solver.state
-            try:
-                st = PgmBatchedState(solver, b)
-                st.init(b, ref, _fusable_kinds(solver.reg, solver.proj if type(solver) is POGM else []), kw.get("theta", 1))
-                solver.state = st
-                return
-            except _lib.RLSError:
-                pass  # e.g. M or N not a multiple of 16: independent per-column plans instead
-        if (type(solver) is ADMM and solver.precon is None and isinstance(b, DeviceMatrix) and b.N > 1 and solver.A is not None and not kw
-                and solver.use_device_plan and solver._all_identity() and len(solver.reg) == 1 and solver.vary_rho == "none"
-                and not isinstance(solver.normalizeReg, (MeasurementBasedNormalization, SystemMatrixBasedNormalization))):
-            try:
-                st = solver.state if isinstance(solver.state, AdmmBatchedState) and solver.state.K == b.N else AdmmBatchedState(solver, b)
-                st.init(b)
-                st.active = [True] * b.N
-                solver.state = st
-                return
-            except _lib.RLSError:
-                pass  # shape or regulariser not covered by the batched plan: independent per-column plans instead
-        scheduler = MultiThreadingState
-    if isinstance(solver.state, AdmmBatchedState):
-        ref = solver.state
-        solver.state = ADMMState(len(solver.reg), solver.rho, ref.absTol, ref.relTol, ref.tolInner)
-    if isinstance(solver.state, FistaBatchedState):
-        solver.state = FISTAState(solver.state.rho, 1, solver.state.relTol)
-    elif isinstance(solver.state, BatchedState):
-        solver.state = CGNRState(solver.state.relTol)
     cols = _columns(b)
     states = [solver._new_state() for _ in cols]  # deep copies of the state  :45-48
     solver.state = scheduler(states)
@@ -2719,7 +2701,7 @@ def solve_(solver: AbstractLinearSolver, b, callbacks=None, **kw):
         cb(solver, 0)
     if not cbs and isinstance(solver.state, BatchedState):
         st = solver.state
-        st._step(solver.iterations if isinstance(st, (FistaBatchedState, PgmBatchedState)) else min(solver.iterations, solver._op.N))
+        st._step(st._run_steps())
         while iterate(solver) is not None:  # normally returns None at once
             pass
         return solversolution(solver)
