@@ -697,6 +697,19 @@ int32_t rls_admm_get_status(rls_admm* a, rls_admm_status* out_h, float* log_h, i
 int32_t rls_admm_step_status(rls_admm* a, int32_t n_outer, rls_admm_status* out_h, float* log_h, int32_t log_records);
 /* batched plans: out_h[nrhs]; log_h (nullable) = nrhs blocks of log_records records, column after column */
 int32_t rls_admm_get_status_batched(rls_admm* a, rls_admm_status* out_h, float* log_h, int32_t log_records);
+/* SplitBregman on a batched plan (src/SplitBregman.jl:205-281; rls_admm on an rls_cg_create_batched plan).  Called after
+ * every rls_admm_init, before the first step.  Y: the N x nrhs matrix of y = A^H b per column, columns ldy elements apart,
+ * owned by the caller and read while the plan steps.  The plan's `iterations` is then the TOTAL number of inner iterations,
+ * iterations x iterationsInner, and its prox_lambda is lambda / rho (:235).  Whenever iterations_inner inner iterations have
+ * passed, the start kernel of the next one first applies the Bregman update of the block that ended (:257-267):
+ * beta_y += y - AHA x, z = x, u = 0, with AHA x taken from the warm-start product of that next iteration -- x does not change
+ * in between, so an inner iteration keeps its iterations_cg + 1 products over A.  Live columns stay in phase: a block ends
+ * after iterations_inner iterations or by `converged`, and a column that met `converged` is `done` (:281).
+ * The update is lazy: a column that is done -- by `converged`, or after its last block -- has no next inner iteration, so
+ * its beta_y, z and u are NOT updated (the reference updates them; they are no part of the result and init! rewrites
+ * them), and its x is untouched, as in the reference.  Status through rls_admm_get_status_batched: `iteration` counts the
+ * inner iterations.  RLS_E_UNSUPPORTED for single-right-hand-side plans and for RLS_REG_TV. */
+int32_t rls_admm_set_bregman(rls_admm* a, int32_t iterations_inner, void* Y, int64_t ldy);
 
 /* ---------------------------------------------------------------------------------------------
  * device pieces of the nested regularisation terms and of the plug-and-play input transforms

@@ -23,7 +23,7 @@ from .regularization import (AbstractParameterizedRegularization, AbstractProjec
 from .solvers import (ADMM, CGNR, DiagonalPreconditioner, FISTA, POGM, Kaczmarz, KaczmarzState, OptISTA, SplitBregman, AbstractKrylovSolver,
                       AbstractPrimalDualSolver, AbstractProximalGradientSolver, AbstractRowActionSolver,
                       applicableSolverList, isapplicable, AbstractLinearSolver, AdmmBatchedState, BatchedState, CgnrBatchedState, FistaBatchedState, PgmBatchedState, CompareSolutionCallback, MultiThreadingState,  # noqa: F401
-                      SequentialState, StoreConvergenceCallback, StoreSolutionCallback, createLinearSolver, init_,
+                      SequentialState, SplitBregmanBatchedState, StoreConvergenceCallback, StoreSolutionCallback, createLinearSolver, init_,
                       iterate, linearSolverList, power_iterations, solve_, solve_group_, solverconvergence, solversolution,
                       solverstate)
 from . import multigpu  # noqa: F401,E402

@@ -277,6 +277,7 @@ PROTOTYPES = {
     "rls_admm_get_status": (_i32, [_vp, C.POINTER(AdmmStatus), _pf, _i32]),
     "rls_admm_step_status": (_i32, [_vp, _i32, C.POINTER(AdmmStatus), _pf, _i32]),
     "rls_admm_get_status_batched": (_i32, [_vp, C.POINTER(AdmmStatus), _pf, _i32]),
+    "rls_admm_set_bregman": (_i32, [_vp, _i32, _vp, _i64]),
 }
 
 _lib = None

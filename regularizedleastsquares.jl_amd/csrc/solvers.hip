@@ -1292,6 +1292,20 @@ __global__ void admm_pre_kernel(E* __restrict__ beta, const E* __restrict__ beta
   }
 }
 
+// the scalars of a cg! that starts with ||r||^2 = rr (thread 0 of the column's workgroup)
+__device__ static inline void cg_start_scalars(cg_scalars* sc, double rr, float rho, float reltol, int maxiter) {
+  const double residual = sqrt(rr);
+  const double tol = fmax((double)((float)reltol * (float)residual), 0.0);
+  sc->residual = residual;
+  sc->prev = 1.0;
+  sc->tol = tol;
+  sc->rho = rho;
+  sc->reltol = reltol;
+  sc->iteration = 0;
+  sc->maxiter = maxiter;
+  sc->done = (0 >= maxiter) || ((float)residual <= (float)tol);
+}
+
 // c = AHA x is in place.  c += rho x ; r = b - c ; residual = ||r|| ; tol ; u = r (= r + beta*0)
 template <typename E>
 __global__ __launch_bounds__(UPD_THREADS) void cg_start_kernel(const E* __restrict__ x, const E* b,
@@ -1329,18 +1343,60 @@ __global__ __launch_bounds__(UPD_THREADS) void cg_start_kernel(const E* __restri
     rr += (double)elem<E>::re(ri) * (double)elem<E>::re(ri) + (double)elem<E>::im(ri) * (double)elem<E>::im(ri);
   }
   rr = block_sum(rr, sm);
-  if (threadIdx.x == 0) {
-    const double residual = sqrt(rr);
-    const double tol = fmax((double)((float)reltol * (float)residual), 0.0);
-    sc->residual = residual;
-    sc->prev = 1.0;
-    sc->tol = tol;
-    sc->rho = rho;
-    sc->reltol = reltol;
-    sc->iteration = 0;
-    sc->maxiter = maxiter;
-    sc->done = (0 >= maxiter) || ((float)residual <= (float)tol);
+  if (threadIdx.x == 0) cg_start_scalars(sc, rr, rho, reltol, maxiter);
+}
+
+// SplitBregman on a batched plan (rls_admm_set_bregman): the start kernel of the first inner iteration of a block.  The
+// partial rows hold AHA x, the product of this iteration's warm start, and x has not changed since the block before
+// ended -- so the Bregman update of that block (src/SplitBregman.jl:257-267) needs no product of its own:
+//   beta_y = (beta_y + y) - AHA x  (two roundings: `.+=`, then the 5-argument mul!) ;  z = x ;  u = 0
+// and then what cg_start_kernel does: beta = beta_y + rho (z - u), xold = x, r = beta - AHA x - rho x.  One workgroup
+// per column.  A column whose `done` is set has no next inner iteration: its x, beta_y, z and u stay as they are.
+template <typename E>
+__global__ __launch_bounds__(UPD_THREADS) void cg_start_bregman_kernel(const E* __restrict__ x, const E* __restrict__ y,
+                                                                       int64_t ldy, E* __restrict__ beta_y,
+                                                                       E* __restrict__ z, E* __restrict__ zu,
+                                                                       E* __restrict__ beta, E* __restrict__ xold,
+                                                                       E* __restrict__ u, E* __restrict__ r, int64_t n,
+                                                                       cg_scalars* sc, float rho, float reltol,
+                                                                       int maxiter, const int* skip, col_batch<E> B) {
+  __shared__ double sm[16];
+  const int bq = blockIdx.x;
+  {
+    const int64_t o = (int64_t)bq * B.ldv;
+    x += o; beta_y += o; z += o; zu += o; beta += o; xold += o; u += o; r += o;
+    y += (int64_t)bq * ldy;
+    skip += (int64_t)bq * B.skip_stride;
+    sc += bq;
   }
+  if (*skip) {
+    if (threadIdx.x == 0) {
+      sc->iteration = 0;
+      sc->maxiter = maxiter;
+      sc->done = 1;
+    }
+    return;
+  }
+  const panel_col<E> up = panel_column<E>(B.panel, n, bq, B.half);
+  double rr = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += UPD_THREADS) {
+    const E cv = col_parts<E>(B, bq, n, i);
+    const E xi = x[i];
+    const E by = elem<E>::sub(elem<E>::add(beta_y[i], y[i]), cv);
+    beta_y[i] = by;
+    z[i] = xi;
+    zu[i] = elem<E>::zero();
+    const E bi = elem<E>::add(by, elem<E>::scale(rho, xi));  // beta_y + rho z - rho u with z = x, u = 0
+    beta[i] = bi;
+    xold[i] = xi;
+    const E ri = elem<E>::sub(bi, elem<E>::add(cv, elem<E>::scale(rho, xi)));
+    r[i] = ri;
+    u[i] = ri;
+    up.put(i, ri);
+    rr += (double)elem<E>::re(ri) * (double)elem<E>::re(ri) + (double)elem<E>::im(ri) * (double)elem<E>::im(ri);
+  }
+  rr = block_sum(rr, sm);
+  if (threadIdx.x == 0) cg_start_scalars(sc, rr, rho, reltol, maxiter);
 }
 
 // after c = AHA u:  c += rho u ; alpha = residual^2 / <u, c> ; x += alpha u ; r -= alpha c ;
@@ -1557,6 +1613,10 @@ struct rls_admm {
   int nrhs = 1;  // batched plans: sc / sc_h / log hold one entry per column
   int requested = 0;  // outer iterations asked for since init (capped at P.iterations)
   int fallbacks = 0;  // resident cg! launches lost and recovered (rls_admm_get_status)
+  // Bregman mode of a batched plan (rls_admm_set_bregman): block length, and y = A^H b per column (N x nrhs, ldy)
+  int breg_inner = 0;
+  const void* breg_y = nullptr;
+  int64_t breg_ldy = 0;
 };
 
 // src/ADMM.jl:246-309 in ONE single-workgroup launch: projections on x, z = prox(x + u) (L1 / L2 inline; a TV prox
@@ -1880,8 +1940,14 @@ static int32_t admm_step_batched_typed(rls_admm* a, int32_t n_outer) {
     F.xold = (E*)P.xold;
     F.rho = P.rho;
     F.skip = &a->sc->done;
-    hipLaunchKernelGGL(cg_start_kernel<E>, dim3(K), dim3(UPD_THREADS), 0, ctx->stream, (const E*)P.x, (const E*)P.beta,
-                       (E*)cg->u, (E*)cg->r, (const E*)cg->c, n, cg->sc, P.rho, P.tol_inner, P.iterations_cg, F, B);
+    if (a->breg_inner > 0 && a->enq > 0 && a->enq % a->breg_inner == 0)
+      // SplitBregman: a block of inner iterations ended here; its Bregman update rides on this start (the product is shared)
+      hipLaunchKernelGGL(cg_start_bregman_kernel<E>, dim3(K), dim3(UPD_THREADS), 0, ctx->stream, (const E*)P.x,
+                         (const E*)a->breg_y, a->breg_ldy, (E*)P.beta_y, zcur, (E*)P.u, (E*)P.beta, (E*)P.xold, (E*)cg->u,
+                         (E*)cg->r, n, cg->sc, P.rho, P.tol_inner, P.iterations_cg, F.skip, B);
+    else
+      hipLaunchKernelGGL(cg_start_kernel<E>, dim3(K), dim3(UPD_THREADS), 0, ctx->stream, (const E*)P.x, (const E*)P.beta,
+                         (E*)cg->u, (E*)cg->r, (const E*)cg->c, n, cg->sc, P.rho, P.tol_inner, P.iterations_cg, F, B);
     for (int it = 0; it < P.iterations_cg; ++it) {
       RLS_TRY(rls_skinny_launch(ctx, dtype, SK, 1 | 2));
       hipLaunchKernelGGL(cg_update_kernel<E>, dim3(K), dim3(UPD_THREADS), 0, ctx->stream, (E*)P.x, (E*)cg->u, (E*)cg->r,
@@ -4289,10 +4355,24 @@ int32_t rls_admm_init(rls_admm* a, const rls_admm_params* p) {
   a->P = *p;
   a->enq = 0;
   a->requested = 0;
+  a->breg_inner = 0;
   hipLaunchKernelGGL(admm_reset_kernel<float>, dim3((unsigned)a->nrhs), dim3(1), 0, ctx->stream, a->sc, p->iterations,
                      p->rho, p->sigma_abs, p->rel_tol);
   RLS_TRY(launch_status(ctx));
   a->ready = true;
+  return 0;
+}
+
+int32_t rls_admm_set_bregman(rls_admm* a, int32_t iterations_inner, void* Y, int64_t ldy) {
+  if (!a) return RLS_E_INVALID;
+  rls_ctx* ctx = a->cg->op->ctx;
+  if (!a->ready || a->enq != 0) return rls_fail(ctx, RLS_E_STATE, "admm_set_bregman: call it right after admm_init");
+  if (!a->cg->Vpart) return rls_fail(ctx, RLS_E_UNSUPPORTED, "admm_set_bregman: batched plans only (rls_cg_create_batched)");
+  if (a->P.reg_kind == RLS_REG_TV) return rls_fail(ctx, RLS_E_UNSUPPORTED, "admm_set_bregman: no TV term in Bregman mode");
+  if (iterations_inner < 1 || !Y || ldy < a->cg->op->N) return rls_fail(ctx, RLS_E_INVALID, "admm_set_bregman: bad argument");
+  a->breg_inner = iterations_inner;
+  a->breg_y = Y;
+  a->breg_ldy = ldy;
   return 0;
 }
 

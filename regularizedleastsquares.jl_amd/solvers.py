@@ -924,18 +924,25 @@ class ADMM(AbstractPrimalDualSolver):
         s = _scalar_state(self)
         return ADMMState(len(self.reg), self.rho, s.absTol, s.relTol, s.tolInner)
 
-    def _init_batched(self, b, kw, previous):
-        if not (type(self) is ADMM and self.precon is None and isinstance(b, DeviceMatrix) and b.N > 1 and self.A is not None and not kw
+    def _batched_ok(self, b, kw):
+        """what the shared-A plan of ADMM and SplitBregman covers, as far as the host can tell"""
+        return (self.precon is None and isinstance(b, DeviceMatrix) and b.N > 1 and self.A is not None and not kw
                 and self.use_device_plan and self._all_identity() and len(self.reg) == 1 and self.vary_rho == "none"
-                and not isinstance(self.normalizeReg, (MeasurementBasedNormalization, SystemMatrixBasedNormalization))):
-            return None
+                and not isinstance(self.normalizeReg, (MeasurementBasedNormalization, SystemMatrixBasedNormalization)))
+
+    def _take_batched(self, cls, b, previous):
         try:
             # (the one batched state that is taken over: plan, state matrices and all, while K stays the same)
-            st = previous if isinstance(previous, AdmmBatchedState) and previous.K == b.N else AdmmBatchedState(self, b)
+            st = previous if type(previous) is cls and previous.K == b.N else cls(self, b)
             st.init(b)
             return st
         except _lib.RLSError:
             return None  # shape or regulariser not covered by the batched plan
+
+    def _init_batched(self, b, kw, previous):
+        if type(self) is not ADMM or not self._batched_ok(b, kw):
+            return None
+        return self._take_batched(AdmmBatchedState, b, previous)
 
     def _all_identity(self):
         return all(getattr(t, "identity", False) for t in self.regTrafo)
@@ -1857,6 +1864,12 @@ class SplitBregman(ADMM):  # AbstractPrimalDualSolver through ADMM
                          tolInner=tolInner, verbose=verbose)
         self.iterationsInner = int(iterationsInner)
 
+    def _init_batched(self, b, kw, previous):
+        # (a TV term keeps the per-column plans: the Bregman mode of the batched plan has no FGP launch)
+        if type(self) is not SplitBregman or not self._batched_ok(b, kw) or type(self.reg[0]) is TVRegularization:
+            return None
+        return self._take_batched(SplitBregmanBatchedState, b, previous)
+
     def init_(self, state, b: DeviceVector, x0=0):
         super().init_(state, b, x0=x0)
         if getattr(state, "ybreg", None) is None or state.ybreg.n != state.x.n or state.ybreg.ctx is not b.ctx:
@@ -2353,9 +2366,13 @@ class BatchedState(AbstractMatrixSolverState):
         check(ctx.handle, getattr(ctx.lib, self._status_fn)(self._plan, st, *self._status_args), self._status_fn)
         return list(st)
 
+    def _max_steps(self):
+        """the most steps a column takes before it is done"""
+        return self.solver.iterations
+
     def _run_steps(self):
         """the steps a solve without callbacks enqueues at once (columns that are done ignore them)"""
-        it = self.solver.iterations
+        it = self._max_steps()
         return min(it, self.solver._op.N) if self._steps_capped_at_N else it
 
     def convergence(self):
@@ -2577,13 +2594,18 @@ class AdmmBatchedState(BatchedState):
         P = solver._plan_params(self)
         if P is None:
             raise _lib.RLSError("batched ADMM: this configuration does not run as a device plan")
+        P.iterations = self._max_steps()
         check(ctx.handle, ctx.lib.rls_admm_init(self._plan, C.byref(P)), "rls_admm_init")
+        self._arm()
         self.iteration = 0
         self.active = [True] * self.K
 
+    def _arm(self):
+        """what follows rls_admm_init before the first step"""
+
     def cg_iterations(self):
         """per column: the inner cg! iteration counts of its outer iterations"""
-        cap = max(self.solver.iterations, 1)
+        cap = max(self._max_steps(), 1)
         st = (AdmmStatus * self.K)()
         log = (C.c_float * (8 * cap * self.K))()
         ctx = self.x.ctx
@@ -2598,6 +2620,44 @@ class AdmmBatchedState(BatchedState):
 
     def _plain(self):
         return ADMMState(len(self.solver.reg), self.solver.rho, self.absTol, self.relTol, self.tolInner)
+
+
+class SplitBregmanBatchedState(AdmmBatchedState):
+    """BatchedState for SplitBregman (one regulariser of kind none / L1 / L2, identity regTrafo): ADMM's batched plan in its
+    Bregman mode (rls_admm_set_bregman).  One step is one INNER iteration of every live column, and a whole solve is
+    iterations x iterationsInner steps enqueued with no read-back: a block of inner iterations ends after iterationsInner of
+    them or by `converged`, and a column that met `converged` is done (src/SplitBregman.jl:257,281), so the live columns are
+    always at the same inner iteration and the host knows where the blocks end.  The Bregman update of a block is applied
+    by the start kernel of the next inner iteration, from that iteration's own warm-start product AHA x.  It is lazy: a
+    column that is done keeps beta_y, z and u as its last inner iteration left them (the reference updates them once more;
+    they are no part of the result and init! rewrites them), and x as the reference leaves it."""
+
+    _steps_capped_at_N = False
+
+    def __init__(self, solver, B: DeviceMatrix):
+        super().__init__(solver, B)
+        self.ybreg = DeviceMatrix(solver._op.N, B.N, B.dtype, B.ctx)  # y = A' b per column   (:180)
+
+    def _max_steps(self):
+        return self.solver.iterations * self.solver.iterationsInner
+
+    def _arm(self):
+        ctx, Y = self.x.ctx, self.ybreg
+        check(ctx.handle, ctx.lib.rls_memcpy_d2d(ctx.handle, Y.ptr, self.beta_y.ptr, Y.lda * Y.N * Y.dtype.itemsize), "rls_memcpy_d2d")
+        check(ctx.handle, ctx.lib.rls_admm_set_bregman(self._plan, self.solver.iterationsInner, Y.ptr, Y.lda), "rls_admm_set_bregman")
+
+    def counters(self):
+        """per column: (iter_cnt, iteration) as the reference's state holds them after the column's inner iterations
+        (:257-269: a block that ends, by its length or by `converged`, starts the next one at iteration 1)"""
+        inner, total = self.solver.iterationsInner, self._max_steps()
+        out = []
+        for s in self.status():
+            it = s.iteration
+            if s.done and 0 < it < total and it % inner:  # retired by `converged` in the middle of a block
+                out.append((it // inner + 2, 1))
+            else:
+                out.append((it // inner + 1, it % inner + 1))
+        return out
 
 
 def _columns(b) -> List[DeviceVector]:
@@ -2664,7 +2724,7 @@ def iterate(solver: AbstractLinearSolver):
         st.active = [not s_.done for s_ in stat]
         if not any(st.active):
             return None
-        if st.iteration > solver.iterations + 1:
+        if st.iteration > st._max_steps() + 1:
             raise _lib.RLSError("batched solve: a column did not reach done() within `iterations` steps")
         st._step(1)
         st.iteration += 1
