@@ -712,6 +712,38 @@ int32_t rls_admm_get_status_batched(rls_admm* a, rls_admm_status* out_h, float* 
 int32_t rls_admm_set_bregman(rls_admm* a, int32_t iterations_inner, void* Y, int64_t ldy);
 
 /* ---------------------------------------------------------------------------------------------
+ * DirectSolver (src/Direct.jl:17-67): x = (A^H A + lambda I) \ A^H b by a blocked Cholesky factorisation on the device
+ * (csrc/direct.hip).  lambda goes on the DIAGONAL: the Tikhonov system CGNR solves (src/Direct.jl:59 broadcasts it onto
+ * every entry; for the default lambda = 0 the two agree).  Float32 / ComplexF32.
+ *   rls_direct_create      the plan on `op`.  It factors the operator's explicit Gram matrix (rls_operator_set_gram) where
+ *                          there is one; otherwise it forms A^H A once (rls_gram) and keeps it.
+ *   rls_direct_factor      G + lambda I = L L^H, L kept in the plan.  A no-op when the plan holds the factor of this lambda
+ *                          and this Gram matrix already AND a rls_direct_get_status behind that factorisation has reported
+ *                          info = 0: factor once, solve many.  (A failed factorisation leaves only a device word behind, so
+ *                          without that status read the host cannot know the factor is good, and factors again.)
+ *   rls_direct_solve       for the K columns of B (M x K, columns ldb apart; for an operator without A: N x K, taken as A^H b):
+ *                          X = A^H B, L Y = X, L^H X = Y, then the projection proj_kind (RLS_PROJ_*).  X: N x K, columns ldx apart.
+ *                          1 <= K <= 16 * 65535.  K + 2 ceil(N / 64) launches: A^H b is one product per column.
+ *   rls_direct_get_status  synchronises.  info = 0, or the 1-based column of the first pivot that was not strictly positive
+ *                          and finite (G + lambda I is not positive definite: use lambda > 0).  The factorisation records
+ *                          it in a device word; every later kernel of that factorisation and of the solves reads the word
+ *                          and does nothing, so X is then NOT written.  A failed factor is never reused: the next
+ *                          rls_direct_factor runs again, whatever its lambda and whether or not the status was read.
+ * All asynchronous on the context's stream but the status.  Null arguments: RLS_E_INVALID.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct rls_direct rls_direct;
+typedef struct rls_direct_status {
+  float lambda;           /* of the factor the plan holds */
+  int32_t factorizations; /* factorisations run so far (rls_direct_factor calls that were no no-ops) */
+  int32_t info;
+} rls_direct_status;
+int32_t rls_direct_create(rls_operator* op, rls_direct** out);
+int32_t rls_direct_factor(rls_direct* s, float lambda);
+int32_t rls_direct_solve(rls_direct* s, int64_t K, const void* B, int64_t ldb, void* X, int64_t ldx, int32_t proj_kind);
+int32_t rls_direct_get_status(rls_direct* s, rls_direct_status* out);
+int32_t rls_direct_destroy(rls_direct* s);
+
+/* ---------------------------------------------------------------------------------------------
  * device pieces of the nested regularisation terms and of the plug-and-play input transforms
  *   rls_gather / rls_scatter   z = view(x, findall(mask)) and back          src/Regularization/MaskedRegularization.jl:27-31
  *   rls_stats                  out_h[5] = min, max, sum, sum of squares of the REAL parts, max |x| (modulus)

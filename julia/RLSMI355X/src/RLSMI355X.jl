@@ -576,4 +576,46 @@ end
 shard_operator(c::Comm, a::Matrix{T}) where {T} =
   [RLSMatrix(a[first(shard_rows(size(a, 1), length(c), r)):last(shard_rows(size(a, 1), length(c), r)), :], c.ctxs[r]) for r in 1:length(c)]
 
+# ---- DirectSolver (src/Direct.jl:17-67): thin wrappers of rls_direct_* (blocked Cholesky of A'A + lambda I on the device) --------
+struct DirectStatus
+  lambda::Float32
+  factorizations::Int32
+  info::Int32
+end
+
+"""
+    DirectPlan(A::RLSMatrix)
+
+The Cholesky factor of `A'A + lambda I` of one operator (`rls_direct_create`): `direct_factor!(p, lambda)` is a no-op while lambda
+stays, `direct_solve!(p, X, B)` solves every column of `B` on the factor.  lambda goes on the diagonal (src/Direct.jl:59
+broadcasts it onto every entry; the two agree for lambda = 0).  Float32 / ComplexF32.
+"""
+mutable struct DirectPlan
+  handle::Ptr{Cvoid}
+  ctx::Context
+  function DirectPlan(A::RLSMatrix)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(A.ctx, ccall((:rls_direct_create, librls[]), Int32, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), A.op, h), "rls_direct_create")
+    p = new(h[], A.ctx)
+    finalizer(q -> (q.handle != C_NULL && ccall((:rls_direct_destroy, librls[]), Int32, (Ptr{Cvoid},), q.handle); q.handle = C_NULL), p)
+  end
+end
+direct_factor!(p::DirectPlan, lambda::Real) =
+  check(p.ctx, ccall((:rls_direct_factor, librls[]), Int32, (Ptr{Cvoid}, Float32), p.handle, Float32(lambda)), "rls_direct_factor")
+function direct_status(p::DirectPlan)
+  st = Ref(DirectStatus(0f0, 0, 0))
+  check(p.ctx, ccall((:rls_direct_get_status, librls[]), Int32, (Ptr{Cvoid}, Ref{DirectStatus}), p.handle, st), "rls_direct_get_status")
+  st[]
+end
+"X (N x K, columns ldx apart) = (A'A + lambda I) \\ A'B for the K columns of B (columns ldb apart), then the projection `proj` (RLS_PROJ_*);
+throws where the factorisation met a pivot that is not positive (`info` = its 1-based column)"
+function direct_solve!(p::DirectPlan, X::Ptr{Cvoid}, ldx::Integer, B::Ptr{Cvoid}, ldb::Integer, K::Integer; proj::Integer = 0)
+  check(p.ctx, ccall((:rls_direct_solve, librls[]), Int32, (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32),
+                     p.handle, K, B, ldb, X, ldx, proj), "rls_direct_solve")
+  st = direct_status(p)
+  st.info == 0 || throw(RLSError(Int32(-4), "DirectSolver: A'A + lambda I is not positive definite (pivot of column $(st.info)); use lambda > 0"))
+  X
+end
+direct_solve!(p::DirectPlan, x::RLSVector, b::RLSVector; proj::Integer = 0) = (direct_solve!(p, x.ptr, length(x), b.ptr, length(b), 1; proj); x)
+
 end # module

@@ -70,6 +70,10 @@ class AdmmStatus(C.Structure):
                 ("fallbacks", C.c_int32)]
 
 
+class DirectStatus(C.Structure):
+    _fields_ = [("lambda_", C.c_float), ("factorizations", C.c_int32), ("info", C.c_int32)]
+
+
 _vp, _i32, _i64, _f, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 _pvp = C.POINTER(C.c_void_p)
 _pf = C.POINTER(C.c_float)
@@ -278,6 +282,12 @@ PROTOTYPES = {
     "rls_admm_step_status": (_i32, [_vp, _i32, C.POINTER(AdmmStatus), _pf, _i32]),
     "rls_admm_get_status_batched": (_i32, [_vp, C.POINTER(AdmmStatus), _pf, _i32]),
     "rls_admm_set_bregman": (_i32, [_vp, _i32, _vp, _i64]),
+    # ---- DirectSolver: blocked Cholesky of the normal equations (csrc/direct.hip) ----
+    "rls_direct_create": (_i32, [_vp, _pvp]),
+    "rls_direct_factor": (_i32, [_vp, _f]),
+    "rls_direct_solve": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32]),
+    "rls_direct_get_status": (_i32, [_vp, C.POINTER(DirectStatus)]),
+    "rls_direct_destroy": (_i32, [_vp]),
 }
 
 _lib = None

@@ -1189,6 +1189,19 @@ void rls_fgramk_sizes(int64_t N, size_t* yx_bytes, size_t* xx_bytes, size_t* dot
 bool rls_fgramk_resident_ok(rls_ctx* ctx, int32_t dtype, int64_t N, int nrhs, const void* G, int64_t ldg);
 int32_t rls_fgramk_resident_launch(rls_ctx* ctx, const rls_fgramk& D, void* sync, int n_steps, unsigned spin_limit);
 
+// ---- DirectSolver (direct.hip): blocked Cholesky of G + lambda I and the triangular solves; plan in solvers.hip -------------
+// The factor is a padded square matrix of rls_direct_padded(N)^2 elements (64 x 64 blocks, identity in the padding) with the
+// factored diagonal blocks in NB tiles of 64 x 64 behind it (rls_direct_factor_elems(N) elements in all); `info` is
+// the plan's device word: 0, or the 1-based column of the first pivot that was not strictly positive and finite -- every
+// kernel reads it at entry and does nothing when it is set.
+int64_t rls_direct_padded(int64_t N);
+size_t rls_direct_factor_elems(int64_t N);
+constexpr int64_t RLS_DIRECT_MAX_RHS = 16 * 65535;  // 16 columns per workgroup, the chunks in gridDim.y
+int32_t rls_direct_launch_factor(rls_ctx* ctx, int32_t dtype, int64_t N, const void* G, int64_t ldg, float lambda, void* W, int* info);
+// X (N x K, columns ldx apart): A^H B in, the solutions out (through the projection); Y: rls_direct_padded(N) x K workspace
+int32_t rls_direct_launch_solve(rls_ctx* ctx, int32_t dtype, int64_t N, const void* W, int K, void* X, int64_t ldx, void* Y, int proj,
+                                const int* info);
+
 // ---------------------------------------------------------------------------------------------
 // comm.hip internals used by the row-sharded solver loops (solvers.hip)
 // ---------------------------------------------------------------------------------------------

@@ -4605,4 +4605,145 @@ int32_t rls_admm_step_status(rls_admm* a, int32_t n_outer, rls_admm_status* out,
   return rls_admm_get_status(a, out, log_h, log_records);
 }
 
+// ---------------------------------------------------------------------------------------------
+// DirectSolver (src/Direct.jl:17-67): x = (A^H A + lambda I) \ A^H b; kernels in direct.hip
+// ---------------------------------------------------------------------------------------------
+// The plan owns the Cholesky factor of G + lambda I and reuses it for every solve until lambda (or the operator's Gram matrix)
+// changes; the reference factors anew on every iterate.  G is the operator's explicit Gram matrix where it carries one,
+// otherwise the plan forms it once (rls_gram) and keeps it.
+struct rls_direct {
+  plan_buffers mem;
+  rls_operator* op = nullptr;
+  rls_ctx* actx = nullptr;
+  uint64_t actx_id = 0;
+  int device = 0;
+  void* L = nullptr;        // rls_direct_factor_elems(N) elements: the padded square, then the factored diagonal tiles
+  int* info = nullptr;      // device word: 0, or the 1-based column of the first bad pivot
+  int* info_h = nullptr;    // its pinned mirror (rls_direct_get_status)
+  void* Gown = nullptr;     // A^H A formed by the plan (operators without an explicit Gram matrix)
+  void* Y = nullptr;        // workspace of the solves: rls_direct_padded(N) x ycols elements; the plan's youngest block
+  int64_t ycols = 0;
+  plan_buffers::mark_t ymark{0, 0};
+  float lambda = 0.f;       // of the factor the plan holds
+  const void* Gfact = nullptr;
+  bool factored = false;    // a factorisation of (lambda, Gfact) has been enqueued ...
+  bool known_good = false;  // ... and a status read behind it found info == 0: only then is it reused (rls_direct_factor)
+  int32_t factorizations = 0;
+};
+
+int32_t rls_direct_create(rls_operator* op, rls_direct** out) {
+  if (!op || !out) return RLS_E_INVALID;
+  rls_ctx* ctx = op->ctx;
+  *out = nullptr;
+  if (!rls_dtype_ok(op->dtype))
+    return rls_fail(ctx, RLS_E_UNSUPPORTED, "direct_create: the Cholesky kernels are Float32 / ComplexF32 (no Float64 / ComplexF64 path)");
+  if (!op->A && !op->G) return rls_fail(ctx, RLS_E_STATE, "direct_create: operator has neither A nor a Gram matrix");
+  RLS_HIP(ctx, rls_enter(ctx));
+  const size_t es = rls_elem_size(op->dtype);
+  rls_direct* s;
+  {
+    rls_alloc_scope alloc_scope(ctx);
+    s = new rls_direct{plan_memory(ctx)};
+    s->op = op;
+    s->actx = ctx;
+    s->actx_id = ctx->id;
+    s->device = ctx->device;
+    s->mem.dev(&s->L, rls_direct_factor_elems(op->N) * es, false);
+    s->mem.dev(&s->info, sizeof(int), true);
+    s->mem.pinned(&s->info_h, sizeof(int), true);
+    if (!op->G) s->mem.dev(&s->Gown, (size_t)op->N * (size_t)op->N * es, false);
+    s->ymark = s->mem.mark();
+  }
+  if (const int e = s->mem.error()) {
+    rls_direct_destroy(s);
+    (void)hipGetLastError();
+    return rls_fail(ctx, e, "direct_create: hipMalloc failed");
+  }
+  if (s->Gown) {
+    const int32_t st = rls_gram(ctx, op->dtype, op->M, op->N, op->A, op->lda, s->Gown, op->N);
+    if (st != 0) {
+      rls_direct_destroy(s);
+      return st;
+    }
+  }
+  *out = s;
+  return 0;
+}
+
+int32_t rls_direct_destroy(rls_direct* s) {
+  if (!s) return RLS_E_INVALID;
+  hipSetDevice(s->device);
+  rls_alloc_scope alloc_scope(alloc_ctx_of(s->actx, s->actx_id));
+  s->mem.release();
+  delete s;
+  return 0;
+}
+
+int32_t rls_direct_factor(rls_direct* s, float lambda) {
+  if (!s) return RLS_E_INVALID;
+  rls_operator* op = s->op;
+  rls_ctx* ctx = op->ctx;
+  const void* G = op->G ? op->G : s->Gown;
+  const int64_t ldg = op->G ? op->ldg : op->N;
+  if (!G) return rls_fail(ctx, RLS_E_STATE, "direct_factor: the operator's Gram matrix was taken away and the plan formed none");
+  // Reuse needs a factor that is KNOWN to be good: a failed one leaves only the device word behind, which the host sees in
+  // rls_direct_get_status alone.  A caller that never reads the status factors on every call (and its solves stay no-ops
+  // after a failure, as documented); one that reads it after a solve -- the Python and Julia bindings do -- factors once.
+  if (s->factored && s->known_good && lambda == s->lambda && G == s->Gfact) return 0;
+  RLS_HIP(ctx, rls_enter(ctx));
+  RLS_TRY(rls_direct_launch_factor(ctx, op->dtype, op->N, G, ldg, lambda, s->L, s->info));
+  s->lambda = lambda;
+  s->Gfact = G;
+  s->factored = true;
+  s->known_good = false;
+  s->factorizations += 1;
+  return 0;
+}
+
+int32_t rls_direct_solve(rls_direct* s, int64_t K, const void* B, int64_t ldb, void* X, int64_t ldx, int32_t proj_kind) {
+  if (!s || !B || !X) return RLS_E_INVALID;
+  rls_operator* op = s->op;
+  rls_ctx* ctx = op->ctx;
+  const int64_t rows = op->A ? op->M : op->N;  // a Gram-only operator takes B = A^H b (as CGNR does, src/CGNR.jl:134)
+  if (K < 1 || K > RLS_DIRECT_MAX_RHS || ldb < rows || ldx < op->N || proj_kind < RLS_PROJ_NONE || proj_kind > RLS_PROJ_POSITIVE)
+    return rls_fail(ctx, RLS_E_INVALID, "direct_solve: bad argument");
+  if (!s->factored) return rls_fail(ctx, RLS_E_STATE, "direct_solve: rls_direct_factor has not run");
+  RLS_HIP(ctx, rls_enter(ctx));
+  const size_t es = rls_elem_size(op->dtype);
+  if (K > s->ycols) {  // the workspace grows with the widest solve seen (stream-ordered: earlier solves still own the old block)
+    rls_alloc_scope alloc_scope(ctx);
+    s->mem.rollback(s->ymark);
+    s->ycols = 0;
+    s->mem.dev(&s->Y, (size_t)rls_direct_padded(op->N) * (size_t)K * es, false);
+    if (const int e = s->mem.error()) {
+      s->mem.rollback(s->ymark);
+      (void)hipGetLastError();
+      return rls_fail(ctx, e, "direct_solve: hipMalloc failed");
+    }
+    s->ycols = K;
+  }
+  // X = A^H B, column by column (each a no-op once the pivot word is set)
+  for (int64_t k = 0; k < K; ++k) {
+    const char* b = (const char*)B + (size_t)k * (size_t)ldb * es;
+    char* x = (char*)X + (size_t)k * (size_t)ldx * es;
+    if (op->A) RLS_TRY(rls_launch_gemv(ctx, op->dtype, RLS_OP_C, op->M, op->N, 1.f, 0.f, op->A, op->lda, b, 0.f, 0.f, x, s->info));
+    else if (b != x) RLS_HIP(ctx, hipMemcpyAsync(x, b, (size_t)op->N * es, hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  return rls_direct_launch_solve(ctx, op->dtype, op->N, s->L, (int)K, X, ldx, s->Y, proj_kind, s->info);
+}
+
+int32_t rls_direct_get_status(rls_direct* s, rls_direct_status* out) {
+  if (!s || !out) return RLS_E_INVALID;
+  rls_ctx* ctx = s->op->ctx;
+  RLS_HIP(ctx, rls_enter(ctx));
+  RLS_HIP(ctx, hipMemcpyAsync(s->info_h, s->info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  RLS_HIP(ctx, rls_stream_wait(ctx->stream));
+  ctx->syncs += 1;
+  out->lambda = s->lambda;
+  out->factorizations = s->factorizations;
+  out->info = *s->info_h;
+  s->known_good = s->factored && out->info == 0;  // (the stream has been waited for: the word belongs to the last factorisation)
+  return 0;
+}
+
 }  // extern "C"

@@ -28,6 +28,7 @@ from .regularization import (AbstractParameterizedRegularization, AbstractProjec
                              L1Regularization, L2Regularization, findsink, findsinks, is_projection, sink,
                              L21Regularization, MeasurementBasedNormalization, NoNormalization, PositiveRegularization,
                              RealRegularization, SystemMatrixBasedNormalization, TVRegularization, normalize)
+from .regularization import prox_ as _prox
 
 _EPS32 = float(np.finfo(np.float32).eps)
 
@@ -2660,6 +2661,224 @@ class SplitBregmanBatchedState(AdmmBatchedState):
         return out
 
 
+# --------------------------------------------------------------------------------------------
+# DirectSolver: src/Direct.jl:4-67
+# --------------------------------------------------------------------------------------------
+
+
+class AbstractDirectSolver(AbstractLinearSolver):
+    """src/RegularizedLeastSquares.jl:135-148 (the category has no isapplicable rule: `False`, as in the reference)"""
+
+
+def _direct_sort_regs(reg, normalizeReg=None, A=None):
+    """the constructor's sorting of `reg` (src/Direct.jl:18-35): (the L2 sink, [the projections ..., at most one further term])"""
+    regs = list(normalize(normalizeReg, [L2Regularization(0.0)] if reg is None else _as_list(reg), A, None))
+    i2 = findsink(L2Regularization, regs)
+    l2 = L2Regularization(0.0) if i2 is None else regs.pop(i2)
+    idx = findsinks(AbstractProjectionRegularization, regs)
+    other = [regs[i] for i in idx]
+    rest = [r for i, r in enumerate(regs) if i not in idx]
+    if len(rest) == 1:
+        other.append(rest[0])
+    elif len(rest) > 1:
+        raise ValueError(f"PseudoInverse does not allow for more than one L2 regularization term, found {len(rest)}")  # :33, verbatim
+    return l2, other
+
+
+def _direct_fused_projection(proj):
+    """(RLS_PROJ_* the solve's last kernel applies, the terms left for prox_): a plain Positive / Real term at the head of `proj`"""
+    if proj and type(proj[0]) is PositiveRegularization:
+        return PROJ_POSITIVE, proj[1:]
+    if proj and type(proj[0]) is RealRegularization:
+        return PROJ_REAL, proj[1:]
+    return PROJ_NONE, proj
+
+
+class _DirectPlan:
+    """rls_direct: the Cholesky factor of G + lambda I of one operator.  It belongs to the SOLVER, not to a state: every state
+    (every column of a matrix right-hand side, every later solve) reuses the factor while lambda stays."""
+
+    def __init__(self, op: OperatorHandle):
+        self._keep = (op, op.ctx)   # destruction order: plan before operator before context
+        h = C.c_void_p()
+        check(op.ctx.handle, op.ctx.lib.rls_direct_create(op.handle, C.byref(h)), "rls_direct_create")
+        self.handle = h
+
+    def solve(self, lam, K, B, ldb, X, ldx, proj_kind):
+        """factor (a no-op while lambda stays), solve the K columns, read the status back; raises where a pivot failed"""
+        ctx = self._keep[1]
+        check(ctx.handle, ctx.lib.rls_direct_factor(self.handle, float(lam)), "rls_direct_factor")
+        check(ctx.handle, ctx.lib.rls_direct_solve(self.handle, int(K), B, int(ldb), X, int(ldx), int(proj_kind)), "rls_direct_solve")
+        st = self.status()
+        if st.info != 0:
+            raise _lib.RLSError(f"DirectSolver: A'A + lambda I is not positive definite for lambda = {float(lam):g}: the pivot of column "
+                                f"{st.info} (1-based) is not strictly positive and finite.  Use lambda > 0 (L2Regularization).")
+        return st
+
+    def status(self):
+        ctx = self._keep[1]
+        st = _lib.DirectStatus()
+        check(ctx.handle, ctx.lib.rls_direct_get_status(self.handle, C.byref(st)), "rls_direct_get_status")
+        return st
+
+    def __del__(self):
+        try:
+            ctx = self._keep[1]
+            if self.handle and ctx.handle:
+                ctx.lib.rls_direct_destroy(self.handle)
+        except Exception:
+            pass
+        self.handle = None
+
+
+def _direct_info(st):
+    """what solverconvergence reports: the record of the state's last solve (rls_direct_status)"""
+    return {"info": int(st.info), "lambda": float(st.lambda_), "factorizations": int(st.factorizations)} if st is not None else {}
+
+
+class DirectSolverState(AbstractSolverState):
+    """src/Direct.jl:12-15, plus lambda as init! normalised it for this b and the record of the solve"""
+
+    def __init__(self):
+        self.x = self.b = None
+        self.lam = 0.0
+        self.iteration = 0
+        self.info = None
+
+    def convergence(self):
+        return _direct_info(self.info)
+
+
+class DirectSolver(AbstractDirectSolver):
+    """src/Direct.jl:4-67: x = (A'A + lambda I) \\ A'b, then prox!(p, x) for every p in `proj`, in order.
+
+    * lambda goes on the DIAGONAL -- the Tikhonov system, the one CGNR and PseudoInverse (s / (s^2 + lambda)) solve and the
+      package documents (l2^2).  src/Direct.jl:59 writes `A'*A .+ lambda`, which broadcasts lambda onto every entry; for the
+      default lambda = 0 the two agree.
+    * Blocked Cholesky on the device (csrc/direct.hip) instead of `lu`.  The factor belongs to the solver and is reused by every
+      later solve -- and by every column of a matrix right-hand side -- while lambda stays; the reference factors on every
+      iterate.  It is formed from the operator's explicit Gram matrix (`AHA=`, e.g. `A.gram()`) where given, else A'A is
+      formed once on the device.
+    * A matrix that is not positive definite raises RLSError naming the column of the failing pivot (no NaN solution).
+    * One `iterate` completes the solve: callbacks fire at iterations 0 and 1.  The result does not depend on x0.
+    * solverconvergence: the record of the last solve, {"info", "lambda", "factorizations"} (no residual is formed).
+    * Float32 / ComplexF32 only; Float64 / ComplexF64 operators raise NotImplementedError.  PseudoInverse is not built."""
+
+    def __init__(self, A=None, *, AHA=None, reg=None, normalizeReg=None):
+        src = A if A is not None else (AHA.A if isinstance(AHA, NormalOperator) else AHA)
+        if isinstance(src, DeviceMatrix) and is_double(src.code):
+            raise NotImplementedError("DirectSolver: the Cholesky kernels are Float32 / ComplexF32; Float64 / ComplexF64 operators "
+                                      "are not supported (use CGNR, or solve on the host)")
+        self.A, self._op = _resolve_operator(A, AHA)
+        self.normalizeReg = normalizeReg or NoNormalization()
+        self.l2, self.proj = _direct_sort_regs(reg, self.normalizeReg, self.A)
+        self._plan = None
+        self.state = DirectSolverState()
+
+    def _new_state(self):
+        return DirectSolverState()
+
+    def _rows(self):
+        return self._op.M if self.A is not None else self._op.N
+
+    def _the_plan(self):
+        if self._plan is None:
+            self._plan = _DirectPlan(self._op)
+        return self._plan
+
+    def _init_batched(self, b, kw, previous):
+        if not (isinstance(b, DeviceMatrix) and _cold_start_only(kw)
+                and not isinstance(self.normalizeReg, MeasurementBasedNormalization)):  # per-column lambda: a factor per column
+            return None
+        st = previous if isinstance(previous, DirectBatchedState) and previous.fits(b) else DirectBatchedState(self, b)
+        st.init(b)
+        return st
+
+    def init_(self, state: DirectSolverState, b: DeviceVector, x0=0):
+        """init!(solver, state, b; x0 = 0)  src/Direct.jl:44-54"""
+        if b.n != self._rows():
+            raise ValueError(f"DimensionMismatch: b has length {b.n}, expected {self._rows()}")
+        N = self._op.N
+        self.l2 = normalize(self.normalizeReg, self.l2, self.A, b, in_solver=True)  # :51
+        start = _start_vector(x0, b, N, state)
+        if state.x is None or state.x.ctx is not b.ctx or state.x.dtype != b.dtype or state.x.n != N or state.b.n != b.n:
+            state.x, state.b = b.similar(N), b.similar()
+        state.b.copy_from(b)      # :52
+        _set_start(state.x, start)  # :53
+        state.lam = float(self.l2.lam)
+        state.iteration = 0
+        state.info = None
+
+    def iterate(self, state: Optional[DirectSolverState] = None):
+        """iterate(solver, state)  src/Direct.jl:56-67: the whole solve; None on the call after it"""
+        state = state or self.state
+        if state.iteration >= 1:
+            return None
+        kind, rest = _direct_fused_projection(self.proj)
+        state.info = self._the_plan().solve(state.lam, 1, state.b.ptr, state.b.n, state.x.ptr, state.x.n, kind)
+        for p in rest:
+            _prox(p, state.x)   # :62-64
+        state.iteration = 1
+        return state.x, state
+
+    def _run(self, state: DirectSolverState):
+        while self.iterate(state) is not None:
+            pass
+
+
+class _DirectColumnStatus:
+    def __init__(self, done):
+        self.done = done
+
+
+class DirectBatchedState(BatchedState):
+    """BatchedState for DirectSolver: all K columns through ONE rls_direct_solve on the solver's factor"""
+
+    def __init__(self, solver, B: DeviceMatrix):
+        super().__init__(solver, B)
+        self.X = DeviceMatrix(solver._op.N, B.N, B.dtype, B.ctx)
+        self.B = DeviceMatrix(B.M, B.N, B.dtype, B.ctx, lda=B.lda)
+        self.info = None
+
+    def fits(self, B: DeviceMatrix):
+        return (self.B.M, self.B.N, self.B.lda, self.B.dtype, self.B.ctx) == (B.M, B.N, B.lda, B.dtype, B.ctx)
+
+    def init(self, B: DeviceMatrix):
+        solver, ctx = self.solver, B.ctx
+        if B.M != solver._rows():
+            raise ValueError(f"DimensionMismatch: b has {B.M} rows, expected {solver._rows()}")
+        solver.l2 = normalize(solver.normalizeReg, solver.l2, solver.A, None, in_solver=True)
+        check(ctx.handle, ctx.lib.rls_memcpy_d2d(ctx.handle, self.B.ptr, B.ptr, B.lda * B.N * B.dtype.itemsize), "rls_memcpy_d2d")
+        self.X.fill_(0)
+        self.lam = float(solver.l2.lam)
+        self.iteration = 0
+        self.info = None
+        self.active = [True] * self.K
+
+    def _max_steps(self):
+        return 1
+
+    def _step(self, n):
+        if self.info is not None or n < 1:
+            return
+        solver = self.solver
+        kind, rest = _direct_fused_projection(solver.proj)
+        self.info = solver._the_plan().solve(self.lam, self.K, self.B.ptr, self.B.lda, self.X.ptr, self.X.lda, kind)
+        for j in range(self.K if rest else 0):
+            x = self.X.column_view(j)
+            for p in rest:
+                _prox(p, x)
+
+    def status(self):
+        return [_DirectColumnStatus(self.info is not None)] * self.K
+
+    def convergence(self):
+        return [_direct_info(self.info)] * self.K
+
+    def _plain(self):
+        return DirectSolverState()
+
+
 def _columns(b) -> List[DeviceVector]:
     if isinstance(b, DeviceMatrix):
         return [b.column(j) for j in range(b.N)]
@@ -2825,8 +3044,9 @@ def applicableSolverList(*args):
 
 
 def linearSolverList():
-    """the solvers of the reference's linearSolverList() that this backend covers (the direct solvers, DAX and
-    the primal-dual solver are outside the scope)"""
+    """the iterative solvers of the reference's linearSolverList() that this backend covers.  DirectSolver exists
+    (AbstractDirectSolver) but is not listed: the reference's own device loops skip the direct solvers, and no isapplicable
+    rule covers their category.  PseudoInverse, DAX and the primal-dual solver are outside the scope"""
     return [CGNR, Kaczmarz, FISTA, OptISTA, POGM, ADMM, SplitBregman]
 
 
