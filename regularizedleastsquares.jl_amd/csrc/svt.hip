@@ -129,10 +129,21 @@ __global__ __launch_bounds__(64 * NW) void svt_blocks_kernel(E* __restrict__ x, 
         const float gabs = elem<E>::cplx ? hypotf(gr, gi) : fabsf(gr);
         const float na = sqrtf(a), nb = sqrtf(bb);
         if (gabs > tol * na * nb && na > null_tol && nb > null_tol) {  // uniform per group: its 16 lanes hold the same sums
-          const float er = gr / gabs, ei = gi / gabs;       // e^{i phi}
+          float er = gr / gabs, ei = gi / gabs;             // e^{i phi}
           const float zeta = (bb - a) / (2.f * gabs);
           const float tt = (zeta >= 0.f ? 1.f : -1.f) / (fabsf(zeta) + sqrtf(1.f + zeta * zeta));
-          const float c = 1.f / sqrtf(1.f + tt * tt), s = c * tt;
+          const float c0 = 1.f / sqrtf(1.f + tt * tt), s0 = c0 * tt;
+          // c0^2 + s0^2 misses 1 by an ulp or so and mostly to the same side (1 + tt^2 rounds to 1 for every small tt, so c0 = 1 and
+          // s0 = tt); the same (c, s) goes into W and V, so each of a vector's few hundred rotations rescaled its part of W V^H and
+          // the misses added up: |V V^H - I| 1e-4 and |W V^H - X| / |X| 9e-6 at 64 x 64, more than a rotation's own rounding does.
+          // One Newton step on the norm, the residual taken by fma (exact where it cancels); the same for the phase's modulus.
+          const float hn = -0.5f * fmaf(s0, s0, fmaf(c0, c0, -1.f));
+          const float c = fmaf(hn, c0, c0), s = fmaf(hn, s0, s0);
+          if constexpr (elem<E>::cplx) {
+            const float hp = -0.5f * fmaf(ei, ei, fmaf(er, er, -1.f));
+            er = fmaf(hp, er, er);
+            ei = fmaf(hp, ei, ei);
+          }
           const E ph = elem<E>::make(er, ei);
           for (int t = sl; t < len; t += SVT_SG) {
             const E wp = W[p * len + t];
@@ -172,8 +183,8 @@ __global__ __launch_bounds__(64 * NW) void svt_blocks_kernel(E* __restrict__ x, 
     }
   }
   __syncthreads();
-  // Y = sum_u fac_u w_u V_u^H.  W and V carry the rounding of every rotation applied to them (about 1e-5 relative
-  // at 96 x 96 in Float32), so the result is assembled from whichever part is SMALLER: the kept part directly, or
+  // Y = sum_u fac_u w_u V_u^H.  W and V carry the rounding of every rotation applied to them (about 1e-6 relative
+  // at 64 x 64 in Float32), so the result is assembled from whichever part is SMALLER: the kept part directly, or
   // the input minus the removed part, Y = X - sum_u (1 - fac_u) w_u V_u^H with X re-read from memory -- the
   // accumulated rounding then scales with the smaller of the two norms (uniform choice per matrix; the direct form
   // also gives exact zeros when everything is thresholded away).
