@@ -744,6 +744,38 @@ int32_t rls_direct_get_status(rls_direct* s, rls_direct_status* out);
 int32_t rls_direct_destroy(rls_direct* s);
 
 /* ---------------------------------------------------------------------------------------------
+ * PseudoInverse (src/Direct.jl:70-162): x = V diag(sigma / (sigma^2 + lambda)) U^H b from a one-sided (Hestenes) Jacobi SVD of A
+ * on the device (csrc/pinv.hip): A = W V^H, the columns of W orthogonal and of norm sigma_j.  lambda is an argument of the SOLVE,
+ * never of the factorisation, and a rank-deficient A (wide, repeated or zero columns, lambda = 0) is no error.  Float32 / ComplexF32.
+ *   rls_pinv_create           the plan on `op`, which must carry an explicit A (a Gram-only operator: RLS_E_INVALID with a message).
+ *   rls_pinv_factor           runs the Jacobi sweeps (one launch per tournament round, one read-back per sweep: it synchronises).
+ *                             A no-op once the plan holds a good factor.  At most 40 sweeps; hitting the cap sets info = 1.
+ *   rls_pinv_solve            for the K columns of B (M x K, columns ldb apart): t_j = w_j^H b / (sigma_j^2 + lambda), x = V t,
+ *                             then the projection proj_kind (RLS_PROJ_*).  X: N x K, columns ldx apart.  Two launches per column,
+ *                             so a column's bits do not depend on K.  Column j is DROPPED (t_j = 0) when sigma_j <= 1e-6 |A|_F,
+ *                             the level below which the factorisation stops orthogonalising -- the one deviation from
+ *                             src/Direct.jl:158, which has no truncation.  With info = 1 nothing is launched and X is NOT written.
+ *   rls_pinv_singular_values  host_out[N]: the singular values, descending (dropped ones included); synchronises.
+ *   rls_pinv_get_status       lambda of the last solve, the factorisations and sweeps run so far, info (0, or 1: sweep cap hit).
+ *   rls_pinv_get_factor       the device pointers and leading dimensions of W (M x N) and V (N x N), valid while the plan lives.
+ * Null arguments: RLS_E_INVALID.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct rls_pinv rls_pinv;
+typedef struct rls_pinv_status {
+  float lambda;           /* of the last solve */
+  int32_t factorizations; /* factorisations run so far (rls_pinv_factor calls that were no no-ops) */
+  int32_t sweeps;         /* Jacobi sweeps of the last factorisation, the one that found nothing to rotate included */
+  int32_t info;
+} rls_pinv_status;
+int32_t rls_pinv_create(rls_operator* op, rls_pinv** out);
+int32_t rls_pinv_factor(rls_pinv* s);
+int32_t rls_pinv_solve(rls_pinv* s, float lambda, int64_t K, const void* B, int64_t ldb, void* X, int64_t ldx, int32_t proj_kind);
+int32_t rls_pinv_singular_values(rls_pinv* s, float* host_out);
+int32_t rls_pinv_get_status(rls_pinv* s, rls_pinv_status* out);
+int32_t rls_pinv_get_factor(rls_pinv* s, void** W, int64_t* ldw, void** V, int64_t* ldv);
+int32_t rls_pinv_destroy(rls_pinv* s);
+
+/* ---------------------------------------------------------------------------------------------
  * device pieces of the nested regularisation terms and of the plug-and-play input transforms
  *   rls_gather / rls_scatter   z = view(x, findall(mask)) and back          src/Regularization/MaskedRegularization.jl:27-31
  *   rls_stats                  out_h[5] = min, max, sum, sum of squares of the REAL parts, max |x| (modulus)

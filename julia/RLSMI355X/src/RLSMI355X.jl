@@ -618,4 +618,62 @@ function direct_solve!(p::DirectPlan, X::Ptr{Cvoid}, ldx::Integer, B::Ptr{Cvoid}
 end
 direct_solve!(p::DirectPlan, x::RLSVector, b::RLSVector; proj::Integer = 0) = (direct_solve!(p, x.ptr, length(x), b.ptr, length(b), 1; proj); x)
 
+# ---- PseudoInverse (src/Direct.jl:70-162): thin wrappers of rls_pinv_* (one-sided Jacobi SVD A = W V' on the device) -------------
+struct PinvStatus
+  lambda::Float32
+  factorizations::Int32
+  sweeps::Int32
+  info::Int32
+end
+
+"""
+    PinvPlan(A::RLSMatrix)
+
+The one-sided Jacobi SVD `A = W V'` of one operator (`rls_pinv_create`; the columns of `W` orthogonal and of norm `s_j`):
+`pinv_factor!(p)` runs the sweeps once, `pinv_solve!(p, X, B, lambda)` is `x = V diag(s / (s^2 + lambda)) U'b` for every column of
+`B` with any lambda, on the one factor.  Columns with `s_j <= 1e-6 ||A||_F` are dropped, so rank-deficient systems are solved
+(src/Direct.jl:158 has no truncation).  Float32 / ComplexF32.
+"""
+mutable struct PinvPlan
+  handle::Ptr{Cvoid}
+  ctx::Context
+  n::Int
+  function PinvPlan(A::RLSMatrix)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(A.ctx, ccall((:rls_pinv_create, librls[]), Int32, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), A.op, h), "rls_pinv_create")
+    p = new(h[], A.ctx, A.N)
+    finalizer(q -> (q.handle != C_NULL && ccall((:rls_pinv_destroy, librls[]), Int32, (Ptr{Cvoid},), q.handle); q.handle = C_NULL), p)
+  end
+end
+function pinv_status(p::PinvPlan)
+  st = Ref(PinvStatus(0f0, 0, 0, 0))
+  check(p.ctx, ccall((:rls_pinv_get_status, librls[]), Int32, (Ptr{Cvoid}, Ref{PinvStatus}), p.handle, st), "rls_pinv_get_status")
+  st[]
+end
+"runs the Jacobi sweeps (a no-op once a good factor is held); throws where the sweep cap was hit"
+function pinv_factor!(p::PinvPlan)
+  check(p.ctx, ccall((:rls_pinv_factor, librls[]), Int32, (Ptr{Cvoid},), p.handle), "rls_pinv_factor")
+  st = pinv_status(p)
+  st.info == 0 || throw(RLSError(Int32(-4), "PseudoInverse: the Jacobi sweeps did not converge within $(st.sweeps) sweeps"))
+  p
+end
+"the singular values of A, descending"
+function pinv_singular_values(p::PinvPlan)
+  pinv_factor!(p)
+  s = Vector{Float32}(undef, p.n)
+  check(p.ctx, ccall((:rls_pinv_singular_values, librls[]), Int32, (Ptr{Cvoid}, Ptr{Float32}), p.handle, s), "rls_pinv_singular_values")
+  s
+end
+"X (N x K, columns ldx apart) = V diag(s / (s^2 + lambda)) U'B for the K columns of B (columns ldb apart), then the projection `proj` (RLS_PROJ_*)"
+function pinv_solve!(p::PinvPlan, X::Ptr{Cvoid}, ldx::Integer, B::Ptr{Cvoid}, ldb::Integer, K::Integer, lambda::Real; proj::Integer = 0)
+  pinv_factor!(p)
+  check(p.ctx, ccall((:rls_pinv_solve, librls[]), Int32, (Ptr{Cvoid}, Float32, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32),
+                     p.handle, Float32(lambda), K, B, ldb, X, ldx, proj), "rls_pinv_solve")
+  X
+end
+pinv_solve!(p::PinvPlan, x::RLSVector, b::RLSVector, lambda::Real; proj::Integer = 0) =
+  (pinv_solve!(p, x.ptr, length(x), b.ptr, length(b), 1, lambda; proj); x)
+pinv_solve!(p::PinvPlan, X::RLSMatrix, B::RLSMatrix, lambda::Real; proj::Integer = 0) =
+  (pinv_solve!(p, X.ptr, X.lda, B.ptr, B.lda, B.N, lambda; proj); X)
+
 end # module

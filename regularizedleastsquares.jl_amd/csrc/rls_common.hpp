@@ -1202,6 +1202,18 @@ int32_t rls_direct_launch_factor(rls_ctx* ctx, int32_t dtype, int64_t N, const v
 int32_t rls_direct_launch_solve(rls_ctx* ctx, int32_t dtype, int64_t N, const void* W, int K, void* X, int64_t ldx, void* Y, int proj,
                                 const int* info);
 
+// ---- PseudoInverse (pinv.hip): one-sided Jacobi SVD A = W V^H and the two products of a solve; plan in solvers.hip ----------
+// W: rls_pinv_padded(dtype, M) x N, V: rls_pinv_padded(dtype, N) x N (leading dimensions padded to 16 bytes, padding rows zero);
+// stats: N + 1 floats, sigma_j^2 and behind them |A|_F^2; rotated: the plan's sweep word (a workgroup that rotated stores 1).
+int64_t rls_pinv_padded(int32_t dtype, int64_t n);
+int64_t rls_pinv_lds_rows(int32_t dtype);  // the largest M whose column pair stays in LDS during a round
+constexpr int RLS_PINV_MAX_SWEEPS = 40;    // as svt.hip
+int32_t rls_pinv_launch_load(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* A, int64_t lda, void* W, void* V, float* stats);
+int32_t rls_pinv_launch_sweep(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, void* W, void* V, const float* stats, int* rotated);
+int32_t rls_pinv_launch_finish(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* W, float* stats);
+int32_t rls_pinv_launch_solve(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* W, const void* V, const float* stats, float lambda,
+                              const void* b, void* t, void* x, int proj);
+
 // ---------------------------------------------------------------------------------------------
 // comm.hip internals used by the row-sharded solver loops (solvers.hip)
 // ---------------------------------------------------------------------------------------------

@@ -4746,4 +4746,154 @@ int32_t rls_direct_get_status(rls_direct* s, rls_direct_status* out) {
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// PseudoInverse (src/Direct.jl:70-162): x = V diag(1 / (sigma^2 + lambda)) W^H b on A = W V^H; kernels in pinv.hip
+// ---------------------------------------------------------------------------------------------
+// The plan owns W, V and the singular values of one operator's A; lambda belongs to a solve.  The reference calls LAPACK's
+// svd in the constructor; here the sweeps run on the first rls_pinv_factor.
+struct rls_pinv {
+  plan_buffers mem;
+  rls_operator* op = nullptr;
+  rls_ctx* actx = nullptr;
+  uint64_t actx_id = 0;
+  int device = 0;
+  void* W = nullptr;        // rls_pinv_padded(M) x N
+  void* V = nullptr;        // rls_pinv_padded(N) x N
+  void* t = nullptr;        // N elements: W^H b, scaled, of the column being solved
+  float* stats = nullptr;   // sigma_j^2 [N], then |A|_F^2
+  float* stats_h = nullptr; // pinned mirror (rls_pinv_singular_values)
+  int* rotated = nullptr;   // the sweep word: a workgroup that rotated stores 1
+  int* rotated_h = nullptr; // its pinned mirror
+  const void* Afact = nullptr;
+  bool factored = false;
+  float lambda = 0.f;
+  int32_t factorizations = 0, sweeps = 0, info = 0;
+};
+
+int32_t rls_pinv_create(rls_operator* op, rls_pinv** out) {
+  if (!op || !out) return RLS_E_INVALID;
+  rls_ctx* ctx = op->ctx;
+  *out = nullptr;
+  if (!rls_dtype_ok(op->dtype))
+    return rls_fail(ctx, RLS_E_UNSUPPORTED, "pinv_create: the Jacobi kernels are Float32 / ComplexF32 (no Float64 / ComplexF64 path)");
+  if (!op->A) return rls_fail(ctx, RLS_E_INVALID, "pinv_create: the operator has no explicit A (a Gram matrix alone has no SVD of A)");
+  if (op->N > 0x7ffffffe) return rls_fail(ctx, RLS_E_INVALID, "pinv_create: too many columns");
+  RLS_HIP(ctx, rls_enter(ctx));
+  const size_t es = rls_elem_size(op->dtype);
+  const size_t N = (size_t)op->N;
+  rls_pinv* s;
+  {
+    rls_alloc_scope alloc_scope(ctx);
+    s = new rls_pinv{plan_memory(ctx)};
+    s->op = op;
+    s->actx = ctx;
+    s->actx_id = ctx->id;
+    s->device = ctx->device;
+    s->mem.dev(&s->W, (size_t)rls_pinv_padded(op->dtype, op->M) * N * es, false);
+    s->mem.dev(&s->V, (size_t)rls_pinv_padded(op->dtype, op->N) * N * es, false);
+    s->mem.dev(&s->t, N * es, false);
+    s->mem.dev(&s->stats, (N + 1) * sizeof(float), true);
+    s->mem.pinned(&s->stats_h, (N + 1) * sizeof(float), true);
+    s->mem.dev(&s->rotated, sizeof(int), true);
+    s->mem.pinned(&s->rotated_h, sizeof(int), true);
+  }
+  if (const int e = s->mem.error()) {
+    rls_pinv_destroy(s);
+    (void)hipGetLastError();
+    return rls_fail(ctx, e, "pinv_create: hipMalloc failed");
+  }
+  *out = s;
+  return 0;
+}
+
+int32_t rls_pinv_destroy(rls_pinv* s) {
+  if (!s) return RLS_E_INVALID;
+  hipSetDevice(s->device);
+  rls_alloc_scope alloc_scope(alloc_ctx_of(s->actx, s->actx_id));
+  s->mem.release();
+  delete s;
+  return 0;
+}
+
+int32_t rls_pinv_factor(rls_pinv* s) {
+  if (!s) return RLS_E_INVALID;
+  rls_operator* op = s->op;
+  rls_ctx* ctx = op->ctx;
+  if (!op->A) return rls_fail(ctx, RLS_E_STATE, "pinv_factor: the operator's A was taken away");
+  if (s->factored && s->info == 0 && s->Afact == op->A) return 0;
+  RLS_HIP(ctx, rls_enter(ctx));
+  s->factored = false;
+  RLS_TRY(rls_pinv_launch_load(ctx, op->dtype, op->M, op->N, op->A, op->lda, s->W, s->V, s->stats));
+  s->factorizations += 1;
+  s->sweeps = 0;
+  s->info = 1;  // until a sweep finds nothing to rotate
+  while (s->sweeps < RLS_PINV_MAX_SWEEPS) {
+    RLS_HIP(ctx, hipMemsetAsync(s->rotated, 0, sizeof(int), ctx->stream));
+    RLS_TRY(rls_pinv_launch_sweep(ctx, op->dtype, op->M, op->N, s->W, s->V, s->stats, s->rotated));
+    RLS_HIP(ctx, hipMemcpyAsync(s->rotated_h, s->rotated, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    RLS_HIP(ctx, rls_stream_wait(ctx->stream));
+    ctx->syncs += 1;
+    s->sweeps += 1;
+    if (*s->rotated_h == 0) {
+      s->info = 0;
+      break;
+    }
+  }
+  RLS_TRY(rls_pinv_launch_finish(ctx, op->dtype, op->M, op->N, s->W, s->stats));
+  s->Afact = op->A;
+  s->factored = true;
+  return 0;
+}
+
+int32_t rls_pinv_solve(rls_pinv* s, float lambda, int64_t K, const void* B, int64_t ldb, void* X, int64_t ldx, int32_t proj_kind) {
+  if (!s || !B || !X) return RLS_E_INVALID;
+  rls_operator* op = s->op;
+  rls_ctx* ctx = op->ctx;
+  if (K < 1 || ldb < op->M || ldx < op->N || proj_kind < RLS_PROJ_NONE || proj_kind > RLS_PROJ_POSITIVE || !(lambda >= 0.f))
+    return rls_fail(ctx, RLS_E_INVALID, "pinv_solve: bad argument");
+  if (!s->factored) return rls_fail(ctx, RLS_E_STATE, "pinv_solve: rls_pinv_factor has not run");
+  s->lambda = lambda;
+  if (s->info != 0) return 0;  // the sweep cap was hit: W's columns are not orthogonal, nothing is written (rls_pinv_get_status)
+  RLS_HIP(ctx, rls_enter(ctx));
+  const size_t es = rls_elem_size(op->dtype);
+  for (int64_t k = 0; k < K; ++k) {
+    const char* b = (const char*)B + (size_t)k * (size_t)ldb * es;
+    char* x = (char*)X + (size_t)k * (size_t)ldx * es;
+    RLS_TRY(rls_pinv_launch_solve(ctx, op->dtype, op->M, op->N, s->W, s->V, s->stats, lambda, b, s->t, x, proj_kind));
+  }
+  return 0;
+}
+
+int32_t rls_pinv_singular_values(rls_pinv* s, float* host_out) {
+  if (!s || !host_out) return RLS_E_INVALID;
+  rls_ctx* ctx = s->op->ctx;
+  if (!s->factored) return rls_fail(ctx, RLS_E_STATE, "pinv_singular_values: rls_pinv_factor has not run");
+  RLS_HIP(ctx, rls_enter(ctx));
+  const size_t N = (size_t)s->op->N;
+  RLS_HIP(ctx, hipMemcpyAsync(s->stats_h, s->stats, (N + 1) * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  RLS_HIP(ctx, rls_stream_wait(ctx->stream));
+  ctx->syncs += 1;
+  for (size_t j = 0; j < N; ++j) host_out[j] = sqrtf(s->stats_h[j]);
+  std::sort(host_out, host_out + N, [](float a, float b) { return a > b; });
+  return 0;
+}
+
+int32_t rls_pinv_get_status(rls_pinv* s, rls_pinv_status* out) {
+  if (!s || !out) return RLS_E_INVALID;
+  out->lambda = s->lambda;
+  out->factorizations = s->factorizations;
+  out->sweeps = s->sweeps;
+  out->info = s->info;
+  return 0;
+}
+
+int32_t rls_pinv_get_factor(rls_pinv* s, void** W, int64_t* ldw, void** V, int64_t* ldv) {
+  if (!s || !W || !ldw || !V || !ldv) return RLS_E_INVALID;
+  *W = s->W;
+  *ldw = rls_pinv_padded(s->op->dtype, s->op->M);
+  *V = s->V;
+  *ldv = rls_pinv_padded(s->op->dtype, s->op->N);
+  return 0;
+}
+
 }  // extern "C"

@@ -2762,7 +2762,8 @@ class DirectSolver(AbstractDirectSolver):
     * A matrix that is not positive definite raises RLSError naming the column of the failing pivot (no NaN solution).
     * One `iterate` completes the solve: callbacks fire at iterations 0 and 1.  The result does not depend on x0.
     * solverconvergence: the record of the last solve, {"info", "lambda", "factorizations"} (no residual is formed).
-    * Float32 / ComplexF32 only; Float64 / ComplexF64 operators raise NotImplementedError.  PseudoInverse is not built."""
+    * Float32 / ComplexF32 only; Float64 / ComplexF64 operators raise NotImplementedError.
+    * PseudoInverse (below) solves the same system from an SVD of A: lambda is free there and rank-deficient systems are solved."""
 
     def __init__(self, A=None, *, AHA=None, reg=None, normalizeReg=None):
         src = A if A is not None else (AHA.A if isinstance(AHA, NormalOperator) else AHA)
@@ -2877,6 +2878,235 @@ class DirectBatchedState(BatchedState):
 
     def _plain(self):
         return DirectSolverState()
+
+
+# --------------------------------------------------------------------------------------------
+# PseudoInverse: src/Direct.jl:70-162
+# --------------------------------------------------------------------------------------------
+
+
+class _PinvPlan:
+    """rls_pinv: the one-sided Jacobi SVD A = W V' of one operator (csrc/pinv.hip).  It belongs to the SOLVER and is factored on
+    first use; lambda is an argument of every solve, so no change of lambda (or of b) ever factors again."""
+
+    def __init__(self, op: OperatorHandle):
+        self._keep = (op, op.ctx)   # destruction order: plan before operator before context
+        h = C.c_void_p()
+        check(op.ctx.handle, op.ctx.lib.rls_pinv_create(op.handle, C.byref(h)), "rls_pinv_create")
+        self.handle = h
+
+    def factor(self):
+        """a no-op once a good factor is held; raises where the sweep cap was hit"""
+        ctx = self._keep[1]
+        check(ctx.handle, ctx.lib.rls_pinv_factor(self.handle), "rls_pinv_factor")
+        st = self.status()
+        if st.info != 0:
+            raise _lib.RLSError(f"PseudoInverse: the Jacobi sweeps did not converge within {st.sweeps} sweeps (info = {st.info}); "
+                                "no solution is written")
+        return st
+
+    def solve(self, lam, K, B, ldb, X, ldx, proj_kind):
+        """factor (once), solve the K columns with this lambda; returns the status behind the solve"""
+        ctx = self._keep[1]
+        self.factor()
+        check(ctx.handle, ctx.lib.rls_pinv_solve(self.handle, float(lam), int(K), B, int(ldb), X, int(ldx), int(proj_kind)), "rls_pinv_solve")
+        return self.status()
+
+    def status(self):
+        ctx = self._keep[1]
+        st = _lib.PinvStatus()
+        check(ctx.handle, ctx.lib.rls_pinv_get_status(self.handle, C.byref(st)), "rls_pinv_get_status")
+        return st
+
+    def singular_values(self):
+        op, ctx = self._keep
+        self.factor()
+        out = np.empty(op.N, dtype=np.float32)
+        check(ctx.handle, ctx.lib.rls_pinv_singular_values(self.handle, out.ctypes.data_as(C.POINTER(C.c_float))), "rls_pinv_singular_values")
+        return out
+
+    def factor_to_host(self):
+        """(W, V) of A = W V' as host arrays (M x N and N x N): for tests and diagnostics"""
+        op, ctx = self._keep
+        self.factor()
+        W, V, ldw, ldv = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int64()
+        check(ctx.handle, ctx.lib.rls_pinv_get_factor(self.handle, C.byref(W), C.byref(ldw), C.byref(V), C.byref(ldv)), "rls_pinv_get_factor")
+        out = []
+        for ptr, ld, rows in ((W, ldw.value, op.M), (V, ldv.value, op.N)):
+            host = np.empty((ld, op.N), dtype=op.dtype, order="F")
+            check(ctx.handle, ctx.lib.rls_memcpy_d2h(ctx.handle, host.ctypes.data, ptr, host.nbytes), "rls_memcpy_d2h")
+            out.append(np.ascontiguousarray(host[:rows]))
+        return tuple(out)
+
+    def __del__(self):
+        try:
+            ctx = self._keep[1]
+            if self.handle and ctx.handle:
+                ctx.lib.rls_pinv_destroy(self.handle)
+        except Exception:
+            pass
+        self.handle = None
+
+
+def _pinv_info(st):
+    """what solverconvergence reports: the record of the state's last solve (rls_pinv_status)"""
+    if st is None:
+        return {}
+    return {"info": int(st.info), "lambda": float(st.lambda_), "factorizations": int(st.factorizations), "sweeps": int(st.sweeps)}
+
+
+class PseudoInverseState(AbstractSolverState):
+    """src/Direct.jl:79-82, plus lambda as init! normalised it for this b and the record of the solve"""
+
+    def __init__(self):
+        self.x = self.b = None
+        self.lam = 0.0
+        self.iteration = 0
+        self.info = None
+
+    def convergence(self):
+        return _pinv_info(self.info)
+
+
+class PseudoInverse(AbstractDirectSolver):
+    """src/Direct.jl:70-162: x = V diag(s / (s^2 + lambda)) U' b, then prox!(p, x) for every p in `proj`, in order.
+
+    * One-sided (Hestenes) Jacobi SVD on the device (csrc/pinv.hip) instead of LAPACK's `svd`: A = W V' with orthogonal columns
+      w_j of norm s_j, so x = V diag(1 / (s^2 + lambda)) W' b -- two products and a scale.  The factor belongs to the solver and
+      is formed on the first solve (the reference factors in the constructor).
+    * lambda belongs to the SOLVE: `solver.l2 = ...`, a new b under MeasurementBasedNormalization and the columns of a matrix
+      right-hand side with per-column lambda all run on the one factor.
+    * Rank-deficient systems (wide A, repeated or zero columns, lambda = 0) are solved, not refused: column j is dropped when
+      s_j <= 1e-6 ||A||_F, the level below which the factorisation stops orthogonalising.  That truncation is the one
+      deviation from src/Direct.jl:158 (LAPACK hands the reference noise-level s there).
+    * One `iterate` completes the solve: callbacks fire at iterations 0 and 1.  The result does not depend on x0.
+    * solverconvergence: {"info", "lambda", "factorizations", "sweeps"}; `singular_values()` gives s, descending, on the host.
+    * Needs A itself (`AHA=` alone raises ValueError); Float32 / ComplexF32 only (Float64 / ComplexF64: NotImplementedError)."""
+
+    def __init__(self, A=None, *, AHA=None, reg=None, normalizeReg=None):
+        src = A if A is not None else (AHA.A if isinstance(AHA, NormalOperator) else None)
+        if src is None:
+            raise ValueError("PseudoInverse needs the matrix A itself: a Gram matrix (AHA=) alone has no singular value decomposition of A")
+        if isinstance(src, DeviceMatrix) and is_double(src.code):
+            raise NotImplementedError("PseudoInverse: the Jacobi kernels are Float32 / ComplexF32; Float64 / ComplexF64 operators "
+                                      "are not supported (use CGNR, or solve on the host)")
+        self.A, self._op = _resolve_operator(A, AHA)
+        self.normalizeReg = normalizeReg or NoNormalization()
+        self.l2, self.proj = _direct_sort_regs(reg, self.normalizeReg, self.A)
+        self._plan = None
+        self.state = PseudoInverseState()
+
+    def _new_state(self):
+        return PseudoInverseState()
+
+    def _rows(self):
+        return self._op.M
+
+    def _the_plan(self):
+        if self._plan is None:
+            self._plan = _PinvPlan(self._op)
+        return self._plan
+
+    def singular_values(self):
+        """the singular values of A, descending (a host array; factors on first use)"""
+        return self._the_plan().singular_values()
+
+    def _init_batched(self, b, kw, previous):
+        if not (isinstance(b, DeviceMatrix) and _cold_start_only(kw)):
+            return None
+        st = previous if isinstance(previous, PseudoInverseBatchedState) and previous.fits(b) else PseudoInverseBatchedState(self, b)
+        st.init(b)
+        return st
+
+    def init_(self, state: PseudoInverseState, b: DeviceVector, x0=0):
+        """init!(solver, state, b; x0 = 0)  src/Direct.jl:139-149"""
+        if b.n != self._rows():
+            raise ValueError(f"DimensionMismatch: b has length {b.n}, expected {self._rows()}")
+        N = self._op.N
+        self.l2 = normalize(self.normalizeReg, self.l2, self.A, b, in_solver=True)  # :146
+        start = _start_vector(x0, b, N, state)
+        if state.x is None or state.x.ctx is not b.ctx or state.x.dtype != b.dtype or state.x.n != N or state.b.n != b.n:
+            state.x, state.b = b.similar(N), b.similar()
+        state.b.copy_from(b)      # :147
+        _set_start(state.x, start)  # :148
+        state.lam = float(self.l2.lam)
+        state.iteration = 0
+        state.info = None
+
+    def iterate(self, state: Optional[PseudoInverseState] = None):
+        """iterate(solver, state)  src/Direct.jl:151-162: the whole solve; None on the call after it"""
+        state = state or self.state
+        if state.iteration >= 1:
+            return None
+        kind, rest = _direct_fused_projection(self.proj)
+        state.info = self._the_plan().solve(state.lam, 1, state.b.ptr, state.b.n, state.x.ptr, state.x.n, kind)
+        for p in rest:
+            _prox(p, state.x)   # :157-159
+        state.iteration = 1
+        return state.x, state
+
+    def _run(self, state: PseudoInverseState):
+        while self.iterate(state) is not None:
+            pass
+
+
+class PseudoInverseBatchedState(BatchedState):
+    """BatchedState for PseudoInverse: the K columns on the solver's one factor -- ONE rls_pinv_solve where they share lambda,
+    K single-column calls where MeasurementBasedNormalization gives every column its own"""
+
+    def __init__(self, solver, B: DeviceMatrix):
+        super().__init__(solver, B)
+        self.X = DeviceMatrix(solver._op.N, B.N, B.dtype, B.ctx)
+        self.B = DeviceMatrix(B.M, B.N, B.dtype, B.ctx, lda=B.lda)
+        self.lams = [0.0] * self.K
+        self.infos = None
+
+    def fits(self, B: DeviceMatrix):
+        return (self.B.M, self.B.N, self.B.lda, self.B.dtype, self.B.ctx) == (B.M, B.N, B.lda, B.dtype, B.ctx)
+
+    def init(self, B: DeviceMatrix):
+        solver, ctx = self.solver, B.ctx
+        if B.M != solver._rows():
+            raise ValueError(f"DimensionMismatch: b has {B.M} rows, expected {solver._rows()}")
+        check(ctx.handle, ctx.lib.rls_memcpy_d2d(ctx.handle, self.B.ptr, B.ptr, B.lda * B.N * B.dtype.itemsize), "rls_memcpy_d2d")
+        if isinstance(solver.normalizeReg, MeasurementBasedNormalization):   # every column normalises lambda by its own b
+            self.lams = [float(normalize(solver.normalizeReg, solver.l2, solver.A, self.B.column_view(j), in_solver=True).lam)
+                         for j in range(self.K)]
+        else:
+            solver.l2 = normalize(solver.normalizeReg, solver.l2, solver.A, None, in_solver=True)
+            self.lams = [float(solver.l2.lam)] * self.K
+        self.X.fill_(0)
+        self.iteration = 0
+        self.infos = None
+        self.active = [True] * self.K
+
+    def _max_steps(self):
+        return 1
+
+    def _step(self, n):
+        if self.infos is not None or n < 1:
+            return
+        solver, plan = self.solver, self.solver._the_plan()
+        kind, rest = _direct_fused_projection(solver.proj)
+        es = self.B.dtype.itemsize
+        if len(set(self.lams)) == 1:
+            self.infos = [plan.solve(self.lams[0], self.K, self.B.ptr, self.B.lda, self.X.ptr, self.X.lda, kind)] * self.K
+        else:
+            self.infos = [plan.solve(self.lams[j], 1, self.B.ptr + j * self.B.lda * es, self.B.lda, self.X.ptr + j * self.X.lda * es,
+                                     self.X.lda, kind) for j in range(self.K)]
+        for j in range(self.K if rest else 0):
+            x = self.X.column_view(j)
+            for p in rest:
+                _prox(p, x)
+
+    def status(self):
+        return [_DirectColumnStatus(self.infos is not None)] * self.K
+
+    def convergence(self):
+        return [_pinv_info(i) for i in self.infos] if self.infos is not None else [{}] * self.K
+
+    def _plain(self):
+        return PseudoInverseState()
 
 
 def _columns(b) -> List[DeviceVector]:
@@ -3046,7 +3276,7 @@ def applicableSolverList(*args):
 def linearSolverList():
     """the iterative solvers of the reference's linearSolverList() that this backend covers.  DirectSolver exists
     (AbstractDirectSolver) but is not listed: the reference's own device loops skip the direct solvers, and no isapplicable
-    rule covers their category.  PseudoInverse, DAX and the primal-dual solver are outside the scope"""
+    rule covers their category; the same holds for PseudoInverse.  DAX and the primal-dual solver are outside the scope"""
     return [CGNR, Kaczmarz, FISTA, OptISTA, POGM, ADMM, SplitBregman]
 
 
