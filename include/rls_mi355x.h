@@ -750,6 +750,11 @@ int32_t rls_direct_destroy(rls_direct* s);
  *   rls_pinv_create           the plan on `op`, which must carry an explicit A (a Gram-only operator: RLS_E_INVALID with a message).
  *   rls_pinv_factor           runs the Jacobi sweeps (one launch per tournament round, one read-back per sweep: it synchronises).
  *                             A no-op once the plan holds a good factor.  At most 40 sweeps; hitting the cap sets info = 1.
+ *                             Ahead of them it may run BLOCKED sweeps on the matrix cores (blocks of 16 or 32 columns play the
+ *                             tournament; per round the Gram matrix of every block pair, its Jacobi diagonalisation in LDS, and
+ *                             the update of the pair as a GEMM): rls_tune_set "pinv_block" = -1 automatic (the default; never for
+ *                             N < 256), 0 plain sweeps only, 16 or 32 that width wherever there are two blocks.  The key is read
+ *                             here.  The blocked sweeps only shorten the work: the plain sweeps decide convergence and info.
  *   rls_pinv_solve            for the K columns of B (M x K, columns ldb apart): t_j = w_j^H b / (sigma_j^2 + lambda), x = V t,
  *                             then the projection proj_kind (RLS_PROJ_*).  X: N x K, columns ldx apart.  Two launches per column,
  *                             so a column's bits do not depend on K.  Column j is DROPPED (t_j = 0) when sigma_j <= 1e-6 |A|_F,
@@ -757,6 +762,9 @@ int32_t rls_direct_destroy(rls_direct* s);
  *                             src/Direct.jl:158, which has no truncation.  With info = 1 nothing is launched and X is NOT written.
  *   rls_pinv_singular_values  host_out[N]: the singular values, descending (dropped ones included); synchronises.
  *   rls_pinv_get_status       lambda of the last solve, the factorisations and sweeps run so far, info (0, or 1: sweep cap hit).
+ *   rls_pinv_get_block_status what the blocked sweeps of the last factorisation did: the block width (0: they did not run), the
+ *                             blocked sweeps and the rounds (three launches each) they took.  rls_pinv_status.sweeps counts the
+ *                             plain sweeps alone.
  *   rls_pinv_get_factor       the device pointers and leading dimensions of W (M x N) and V (N x N), valid while the plan lives.
  * Null arguments: RLS_E_INVALID.
  * ------------------------------------------------------------------------------------------- */
@@ -767,11 +775,18 @@ typedef struct rls_pinv_status {
   int32_t sweeps;         /* Jacobi sweeps of the last factorisation, the one that found nothing to rotate included */
   int32_t info;
 } rls_pinv_status;
+typedef struct rls_pinv_block_status {
+  int32_t block;        /* block width of the last factorisation's blocked sweeps; 0: they did not run */
+  int32_t block_sweeps; /* blocked sweeps, the one that found nothing to rotate included */
+  int32_t block_rounds; /* rounds of the block tournament launched */
+  int32_t reserved;
+} rls_pinv_block_status;
 int32_t rls_pinv_create(rls_operator* op, rls_pinv** out);
 int32_t rls_pinv_factor(rls_pinv* s);
 int32_t rls_pinv_solve(rls_pinv* s, float lambda, int64_t K, const void* B, int64_t ldb, void* X, int64_t ldx, int32_t proj_kind);
 int32_t rls_pinv_singular_values(rls_pinv* s, float* host_out);
 int32_t rls_pinv_get_status(rls_pinv* s, rls_pinv_status* out);
+int32_t rls_pinv_get_block_status(rls_pinv* s, rls_pinv_block_status* out);
 int32_t rls_pinv_get_factor(rls_pinv* s, void** W, int64_t* ldw, void** V, int64_t* ldv);
 int32_t rls_pinv_destroy(rls_pinv* s);
 

@@ -650,6 +650,18 @@ function pinv_status(p::PinvPlan)
   check(p.ctx, ccall((:rls_pinv_get_status, librls[]), Int32, (Ptr{Cvoid}, Ref{PinvStatus}), p.handle, st), "rls_pinv_get_status")
   st[]
 end
+struct PinvBlockStatus
+  block::Int32
+  block_sweeps::Int32
+  block_rounds::Int32
+  reserved::Int32
+end
+"what the blocked sweeps of the last factorisation did (rls_tune_set "pinv_block"); `block == 0`: they did not run"
+function pinv_block_status(p::PinvPlan)
+  st = Ref(PinvBlockStatus(0, 0, 0, 0))
+  check(p.ctx, ccall((:rls_pinv_get_block_status, librls[]), Int32, (Ptr{Cvoid}, Ref{PinvBlockStatus}), p.handle, st), "rls_pinv_get_block_status")
+  st[]
+end
 "runs the Jacobi sweeps (a no-op once a good factor is held); throws where the sweep cap was hit"
 function pinv_factor!(p::PinvPlan)
   check(p.ctx, ccall((:rls_pinv_factor, librls[]), Int32, (Ptr{Cvoid},), p.handle), "rls_pinv_factor")

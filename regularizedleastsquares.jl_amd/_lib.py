@@ -78,6 +78,10 @@ class PinvStatus(C.Structure):
     _fields_ = [("lambda_", C.c_float), ("factorizations", C.c_int32), ("sweeps", C.c_int32), ("info", C.c_int32)]
 
 
+class PinvBlockStatus(C.Structure):
+    _fields_ = [("block", C.c_int32), ("block_sweeps", C.c_int32), ("block_rounds", C.c_int32), ("reserved", C.c_int32)]
+
+
 _vp, _i32, _i64, _f, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 _pvp = C.POINTER(C.c_void_p)
 _pf = C.POINTER(C.c_float)
@@ -298,6 +302,7 @@ PROTOTYPES = {
     "rls_pinv_solve": (_i32, [_vp, _f, _i64, _vp, _i64, _vp, _i64, _i32]),
     "rls_pinv_singular_values": (_i32, [_vp, _pf]),
     "rls_pinv_get_status": (_i32, [_vp, C.POINTER(PinvStatus)]),
+    "rls_pinv_get_block_status": (_i32, [_vp, C.POINTER(PinvBlockStatus)]),
     "rls_pinv_get_factor": (_i32, [_vp, _pvp, _pi64, _pvp, _pi64]),
     "rls_pinv_destroy": (_i32, [_vp]),
 }

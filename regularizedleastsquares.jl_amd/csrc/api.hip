@@ -324,6 +324,12 @@ int32_t rls_tune_set(rls_ctx* ctx, const char* key, int32_t value) {
   else if (!strcmp(key, "red_threads")) ctx->tune.red_threads = value;
   else if (!strcmp(key, "slab_multi")) ctx->tune.slab_multi = value ? 1 : 0;
   else if (!strcmp(key, "resident_barrier")) ctx->tune.resident_barrier = value == 1 ? 1 : 2;
+  else if (!strcmp(key, "pinv_block")) {  // read by rls_pinv_factor
+    if (value != -1 && value != 0 && value != 16 && value != 32) return rls_fail(ctx, RLS_E_INVALID, "tune_set: pinv_block: -1, 0, 16 or 32");
+    ctx->tune.pinv_block = value;
+  }
+  else if (!strcmp(key, "pinv_block_tol")) ctx->tune.pinv_block_tol = value < 0 ? 0 : (value > 7 ? 7 : value);
+  else if (!strcmp(key, "pinv_block_cap")) ctx->tune.pinv_block_cap = value < 0 ? 0 : (value > 40 ? 40 : value);
   else return rls_fail(ctx, RLS_E_INVALID, "tune_set: unknown key");
   return 0;
 }

@@ -61,6 +61,8 @@ struct rls_tuning {
   int kaczmarz_nt = 0;         // kaczmarz.hip: workgroup size override (0 = heuristic)
   int kaczmarz_fused = 1;      // 0: rls_kaczmarz_solve takes neither end-of-sweep maps nor per-sweep orders (RLS_E_UNSUPPORTED); the
                                // solver bindings then run their host loop (a launch per sweep and per prox): measurement / escape hatch
+  int pinv_block = -1;         // PseudoInverse, blocked sweeps ahead of the plain ones: -1 automatic, 0 plain only, 16 / 32 that width
+  int pinv_block_tol = 0, pinv_block_cap = 0;  // measurement: tau_b = 10^-v and the cap of blocked sweeps (0: the constants)
   int resident_spin = 100000;  // bound of every in-kernel wait, in polls (~1 us each: a wall-clock bound of ~0.1 s per
                                // wait); a launch that runs into it is a no-op and the host re-runs its iterations on the
                                // per-iteration pipeline (solvers.hip, *_recover)
@@ -1213,6 +1215,16 @@ int32_t rls_pinv_launch_sweep(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N,
 int32_t rls_pinv_launch_finish(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* W, float* stats);
 int32_t rls_pinv_launch_solve(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* W, const void* V, const float* stats, float lambda,
                               const void* b, void* t, void* x, int proj);
+// Phase 1 of the factorisation: blocked sweeps on the matrix cores, block = 16 or 32 columns.  The constants are the choices
+// measured in profiles/pseudo_inverse_blocked.txt.
+constexpr int RLS_PINV_BLOCK = 16;            // the block width of the automatic mode (32 costs 1.3 x the plain path)
+constexpr float RLS_PINV_BLOCK_TOL = 1e-5f;   // tau_b: a pair of G rotates where |g_pq| > tau_b sqrt(g_pp g_qq)
+constexpr int RLS_PINV_BLOCK_CAP = 12;        // blocked sweeps at most; reaching it is no error (the plain sweeps decide)
+constexpr int64_t RLS_PINV_BLOCK_AUTO_N = 2048;  // the automatic mode uses blocks from this N on (never below 256); 0: never.
+                                                 // 0.77 x the plain path at 4096 x 2048, 1.34 x at 2048 x 1024
+size_t rls_pinv_block_scratch_bytes(int32_t dtype, int64_t M, int64_t N, int block);
+int32_t rls_pinv_launch_block_sweep(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, int block, float tol, void* W, void* V, const float* stats,
+                                    void* scratch, int* rotated, int* rounds);
 
 // ---------------------------------------------------------------------------------------------
 // comm.hip internals used by the row-sharded solver loops (solvers.hip)

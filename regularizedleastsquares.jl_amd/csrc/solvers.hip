@@ -4768,7 +4768,37 @@ struct rls_pinv {
   bool factored = false;
   float lambda = 0.f;
   int32_t factorizations = 0, sweeps = 0, info = 0;
+  // phase 1 (blocked sweeps): the scratch is asked for by the first factorisation that runs it -- always the arena's youngest block
+  void* scratch = nullptr;
+  size_t scratch_bytes = 0;
+  plan_buffers::mark_t scratch_mark{0, 0};
+  int32_t block = 0, block_sweeps = 0, block_rounds = 0;
 };
+
+// the block width phase 1 of this factorisation runs with (0: none): rls_tuning::pinv_block, read here
+static int pinv_block_width(const rls_ctx* ctx, int64_t N) {
+  const int v = ctx->tune.pinv_block;
+  int b = 0;
+  if (v == 16 || v == 32) b = v;
+  else if (v == -1 && RLS_PINV_BLOCK_AUTO_N > 0 && N >= 256 && N >= RLS_PINV_BLOCK_AUTO_N) b = RLS_PINV_BLOCK;
+  return b > 0 && N > b ? b : 0;  // one block: nothing to pair
+}
+
+static int32_t pinv_block_scratch(rls_pinv* s, rls_ctx* ctx, size_t bytes) {
+  if (bytes <= s->scratch_bytes) return 0;
+  rls_alloc_scope alloc_scope(ctx);
+  if (s->scratch) s->mem.rollback(s->scratch_mark);
+  s->scratch_bytes = 0;
+  s->scratch_mark = s->mem.mark();
+  s->mem.dev(&s->scratch, bytes, false);
+  if (const int e = s->mem.error()) {
+    s->mem.rollback(s->scratch_mark);
+    (void)hipGetLastError();
+    return rls_fail(ctx, e, "pinv_factor: hipMalloc failed (scratch of the blocked sweeps)");
+  }
+  s->scratch_bytes = bytes;
+  return 0;
+}
 
 int32_t rls_pinv_create(rls_operator* op, rls_pinv** out) {
   if (!op || !out) return RLS_E_INVALID;
@@ -4827,6 +4857,26 @@ int32_t rls_pinv_factor(rls_pinv* s) {
   s->factorizations += 1;
   s->sweeps = 0;
   s->info = 1;  // until a sweep finds nothing to rotate
+  // phase 1: blocked sweeps until one rotates nothing, or the cap (no error: phase 2 decides convergence)
+  s->block = pinv_block_width(ctx, op->N);
+  s->block_sweeps = s->block_rounds = 0;
+  if (s->block) {
+    RLS_TRY(pinv_block_scratch(s, ctx, rls_pinv_block_scratch_bytes(op->dtype, op->M, op->N, s->block)));
+    const int cap = ctx->tune.pinv_block_cap > 0 ? ctx->tune.pinv_block_cap : RLS_PINV_BLOCK_CAP;
+    float tol = RLS_PINV_BLOCK_TOL;
+    if (ctx->tune.pinv_block_tol > 0) tol = powf(10.f, -(float)ctx->tune.pinv_block_tol);
+    while (s->block_sweeps < cap) {
+      int rounds = 0;
+      RLS_HIP(ctx, hipMemsetAsync(s->rotated, 0, sizeof(int), ctx->stream));
+      RLS_TRY(rls_pinv_launch_block_sweep(ctx, op->dtype, op->M, op->N, s->block, tol, s->W, s->V, s->stats, s->scratch, s->rotated, &rounds));
+      RLS_HIP(ctx, hipMemcpyAsync(s->rotated_h, s->rotated, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+      RLS_HIP(ctx, rls_stream_wait(ctx->stream));
+      ctx->syncs += 1;
+      s->block_sweeps += 1;
+      s->block_rounds += rounds;
+      if (*s->rotated_h == 0) break;
+    }
+  }
   while (s->sweeps < RLS_PINV_MAX_SWEEPS) {
     RLS_HIP(ctx, hipMemsetAsync(s->rotated, 0, sizeof(int), ctx->stream));
     RLS_TRY(rls_pinv_launch_sweep(ctx, op->dtype, op->M, op->N, s->W, s->V, s->stats, s->rotated));
@@ -4884,6 +4934,15 @@ int32_t rls_pinv_get_status(rls_pinv* s, rls_pinv_status* out) {
   out->factorizations = s->factorizations;
   out->sweeps = s->sweeps;
   out->info = s->info;
+  return 0;
+}
+
+int32_t rls_pinv_get_block_status(rls_pinv* s, rls_pinv_block_status* out) {
+  if (!s || !out) return RLS_E_INVALID;
+  out->block = s->block;
+  out->block_sweeps = s->block_sweeps;
+  out->block_rounds = s->block_rounds;
+  out->reserved = 0;
   return 0;
 }
 

@@ -2916,7 +2916,16 @@ class _PinvPlan:
         ctx = self._keep[1]
         st = _lib.PinvStatus()
         check(ctx.handle, ctx.lib.rls_pinv_get_status(self.handle, C.byref(st)), "rls_pinv_get_status")
+        bs = self.block_status()
+        st.block, st.block_sweeps = int(bs.block), int(bs.block_sweeps)   # (solverconvergence reports them beside the plain sweeps)
         return st
+
+    def block_status(self):
+        """what the blocked sweeps of the last factorisation did (rls_pinv_block_status); block == 0: they did not run"""
+        ctx = self._keep[1]
+        bs = _lib.PinvBlockStatus()
+        check(ctx.handle, ctx.lib.rls_pinv_get_block_status(self.handle, C.byref(bs)), "rls_pinv_get_block_status")
+        return bs
 
     def singular_values(self):
         op, ctx = self._keep
@@ -2952,7 +2961,8 @@ def _pinv_info(st):
     """what solverconvergence reports: the record of the state's last solve (rls_pinv_status)"""
     if st is None:
         return {}
-    return {"info": int(st.info), "lambda": float(st.lambda_), "factorizations": int(st.factorizations), "sweeps": int(st.sweeps)}
+    return {"info": int(st.info), "lambda": float(st.lambda_), "factorizations": int(st.factorizations), "sweeps": int(st.sweeps),
+            "block": int(st.block), "block_sweeps": int(st.block_sweeps)}
 
 
 class PseudoInverseState(AbstractSolverState):
@@ -2980,7 +2990,10 @@ class PseudoInverse(AbstractDirectSolver):
       s_j <= 1e-6 ||A||_F, the level below which the factorisation stops orthogonalising.  That truncation is the one
       deviation from src/Direct.jl:158 (LAPACK hands the reference noise-level s there).
     * One `iterate` completes the solve: callbacks fire at iterations 0 and 1.  The result does not depend on x0.
-    * solverconvergence: {"info", "lambda", "factorizations", "sweeps"}; `singular_values()` gives s, descending, on the host.
+    * Ahead of the plain sweeps the factorisation can run blocked sweeps on the matrix cores: `ctx.tune(pinv_block=16)`
+      or 32 forces them, 0 switches them off, -1 (the default) is automatic.  They shorten the plain sweeps and decide nothing.
+    * solverconvergence: {"info", "lambda", "factorizations", "sweeps", "block", "block_sweeps"} (`sweeps` counts the plain ones;
+      `block` = 0: no blocked sweeps ran); `singular_values()` gives s, descending, on the host.
     * Needs A itself (`AHA=` alone raises ValueError); Float32 / ComplexF32 only (Float64 / ComplexF64: NotImplementedError)."""
 
     def __init__(self, A=None, *, AHA=None, reg=None, normalizeReg=None):

@@ -9,7 +9,8 @@
 Every step runs under a time limit of its own (SIGALRM with its default action: the process ends there, a hung device call
 included), sized from the cost estimate of one round -- W and V moved once each way, about 200 MB at 4096 x 2048 ComplexF32 --
 times N - 1 rounds times at most 40 sweeps, at a pessimistic 500 GB/s.  Lines are written as they are measured.
-Times of different machines of one pool differ by up to 15 %: compare the legs of one run.   usage: bench_pinv.py [out.txt]"""
+Times of different machines of one pool differ by up to 15 %: compare the legs of one run.   usage: bench_pinv.py [out.txt]
+       bench_pinv.py --block b:tol_exp:cap[,b:tol_exp:cap...] [out.txt]   the blocked sweeps against the plain ones (block_ab below)"""
 import os
 import signal
 import sys
@@ -25,7 +26,7 @@ REPS, LAM = 9, 1e-2
 LAMS = [float(l) for l in np.logspace(-4, 0, 16)]
 ctx = rls.Context(0)
 lib, h = ctx.lib, ctx.handle
-out_path = sys.argv[1] if len(sys.argv) > 1 else None
+out_path = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] != "--block" else None
 if out_path:
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     open(out_path, "w").close()
@@ -79,6 +80,62 @@ def wall_ms(fn, reps):
 def rel(a, b):
     return float(np.linalg.norm(a.astype(np.complex128) - b) / np.linalg.norm(b))
 
+
+def block_ab(settings):
+    """--block: the blocked sweeps against the plain ones, alternately in this process, median of 5 factorisations
+    each, at 4096 x 2048 ComplexF32 and 1024 x 512 Float32.  A setting is b:tol_exp:cap (tau_b = 10^-tol_exp).  The time of
+    phase 2 is the plain sweeps times the plain run's time per sweep, and phase 1 is the rest: the library times neither."""
+    for M, N, dt in ((4096, 2048, np.complex64), (2048, 1024, np.complex64), (1024, 512, np.float32)):
+        name = f"{M} x {N} {np.dtype(dt).name}"
+        es = np.dtype(dt).itemsize
+        factor_limit = max(20.0, 2 * (M + N) * N * es * (N - 1) * 40 / 500e9 + 40 * (N - 1) * 20e-6)
+        A = make_A(M, N, 4, dt)
+        rng = np.random.default_rng(5)
+        x0 = rng.standard_normal(N) + (1j * rng.standard_normal(N) if np.dtype(dt).kind == "c" else 0)
+        A64 = A.astype(np.complex128 if np.dtype(dt).kind == "c" else np.float64)
+        b = (A64 @ x0).astype(dt)
+        truth = np.linalg.solve(A64.conj().T @ A64 + LAM * np.eye(N), A64.conj().T @ b.astype(A64.dtype))
+        Ad, bd = rls.DeviceMatrix.from_host(A, ctx), rls.DeviceVector.from_host(b, ctx)
+
+        def one(block, tol, cap):
+            ctx.tune(pinv_block=block, pinv_block_tol=tol, pinv_block_cap=cap)
+            solver = rls.PseudoInverse(Ad, reg=[rls.L2Regularization(LAM)])
+            ctx.sync()
+            t0 = time.perf_counter()
+            solver._the_plan().factor()
+            ctx.sync()
+            ms = (time.perf_counter() - t0) * 1e3
+            st, bs = solver._plan.status(), solver._plan.block_status()
+            return ms, st.sweeps, bs.block_sweeps, rel(rls.solve_(solver, bd).to_host(), truth)
+
+        say(f"{name}: b tau_b cap | blocked sweeps, plain sweeps | total ms (median of 5; min, max) = phase 1 + phase 2 | error vs float64 || "
+            f"plain alone: sweeps, ms, error | blocked / plain")
+        with limit(2 * factor_limit):
+            one(0, 0, 0)
+        for b_, tol, cap in settings:
+            with limit(12 * factor_limit):
+                one(b_, tol, cap)                      # warm-up (the scratch, the kernels' first launch)
+                tb, tp = [], []
+                for _ in range(5):
+                    tp.append(one(0, 0, 0))
+                    tb.append(one(b_, tol, cap))
+            mb_, mp = float(np.median([t[0] for t in tb])), float(np.median([t[0] for t in tp]))
+            per_sweep = mp / tp[0][1]
+            p2 = tb[0][1] * per_sweep
+            say(f"{name}: {b_:2d} 1e-{tol} {cap:2d} | {tb[0][2]:2d}, {tb[0][1]:2d} | {mb_:8.2f} ({min(t[0] for t in tb):.2f}, {max(t[0] for t in tb):.2f}) "
+                f"= {mb_ - p2:7.2f} + {p2:7.2f} | {tb[0][3]:.2e} || {tp[0][1]:2d}, {mp:8.2f}, {tp[0][3]:.2e} | {mb_ / mp:.3f}")
+        ctx.tune(pinv_block=-1, pinv_block_tol=0, pinv_block_cap=0)
+
+
+if "--block" in sys.argv:
+    i = sys.argv.index("--block")
+    spec = sys.argv[i + 1]
+    out_path = sys.argv[i + 2] if len(sys.argv) > i + 2 else None
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        open(out_path, "a").close()
+    block_ab([tuple(int(v) for v in s.split(":")) for s in spec.split(",")])
+    sys.exit(0)
 
 for M, N, dt in ((4096, 2048, np.complex64), (256, 128, np.float32)):
     name = f"{M} x {N} {np.dtype(dt).name}"
