@@ -2662,12 +2662,8 @@ class SplitBregmanBatchedState(AdmmBatchedState):
 
 
 # --------------------------------------------------------------------------------------------
-# DirectSolver: src/Direct.jl:4-67
+# the direct solvers: src/Direct.jl (DirectSolver :4-67, PseudoInverse :70-162)
 # --------------------------------------------------------------------------------------------
-
-
-class AbstractDirectSolver(AbstractLinearSolver):
-    """src/RegularizedLeastSquares.jl:135-148 (the category has no isapplicable rule: `False`, as in the reference)"""
 
 
 def _direct_sort_regs(reg, normalizeReg=None, A=None):
@@ -2694,21 +2690,43 @@ def _direct_fused_projection(proj):
     return PROJ_NONE, proj
 
 
-class _DirectPlan:
-    """rls_direct: the Cholesky factor of G + lambda I of one operator.  It belongs to the SOLVER, not to a state: every state
-    (every column of a matrix right-hand side, every later solve) reuses the factor while lambda stays."""
+class _FactorPlan:
+    """A factorisation of one operator, held on the device.  It belongs to the SOLVER, not to a state: every state (every column
+    of a matrix right-hand side, every later solve) reuses the factor.  A subclass names its create / destroy entry points and
+    says what `solve(lam, K, B, ldb, X, ldx, proj_kind)` and `status()` are."""
+
+    _create_fn = _destroy_fn = None
 
     def __init__(self, op: OperatorHandle):
         self._keep = (op, op.ctx)   # destruction order: plan before operator before context
         h = C.c_void_p()
-        check(op.ctx.handle, op.ctx.lib.rls_direct_create(op.handle, C.byref(h)), "rls_direct_create")
+        check(op.ctx.handle, getattr(op.ctx.lib, self._create_fn)(op.handle, C.byref(h)), self._create_fn)
         self.handle = h
+
+    def _call(self, fn, *args):
+        """the entry point `fn` on this plan; raises on its error code"""
+        ctx = self._keep[1]
+        check(ctx.handle, getattr(ctx.lib, fn)(self.handle, *args), fn)
+
+    def __del__(self):
+        try:
+            ctx = self._keep[1]
+            if self.handle and ctx.handle:
+                getattr(ctx.lib, self._destroy_fn)(self.handle)
+        except Exception:
+            pass
+        self.handle = None
+
+
+class _DirectPlan(_FactorPlan):
+    """rls_direct: the Cholesky factor of G + lambda I of one operator, reused while lambda stays"""
+
+    _create_fn, _destroy_fn = "rls_direct_create", "rls_direct_destroy"
 
     def solve(self, lam, K, B, ldb, X, ldx, proj_kind):
         """factor (a no-op while lambda stays), solve the K columns, read the status back; raises where a pivot failed"""
-        ctx = self._keep[1]
-        check(ctx.handle, ctx.lib.rls_direct_factor(self.handle, float(lam)), "rls_direct_factor")
-        check(ctx.handle, ctx.lib.rls_direct_solve(self.handle, int(K), B, int(ldb), X, int(ldx), int(proj_kind)), "rls_direct_solve")
+        self._call("rls_direct_factor", float(lam))
+        self._call("rls_direct_solve", int(K), B, int(ldb), X, int(ldx), int(proj_kind))
         st = self.status()
         if st.info != 0:
             raise _lib.RLSError(f"DirectSolver: A'A + lambda I is not positive definite for lambda = {float(lam):g}: the pivot of column "
@@ -2716,189 +2734,20 @@ class _DirectPlan:
         return st
 
     def status(self):
-        ctx = self._keep[1]
         st = _lib.DirectStatus()
-        check(ctx.handle, ctx.lib.rls_direct_get_status(self.handle, C.byref(st)), "rls_direct_get_status")
+        self._call("rls_direct_get_status", C.byref(st))
         return st
 
-    def __del__(self):
-        try:
-            ctx = self._keep[1]
-            if self.handle and ctx.handle:
-                ctx.lib.rls_direct_destroy(self.handle)
-        except Exception:
-            pass
-        self.handle = None
 
+class _PinvPlan(_FactorPlan):
+    """rls_pinv: the one-sided Jacobi SVD A = W V' of one operator (csrc/pinv.hip), factored on first use; lambda is an argument
+    of every solve, so no change of lambda (or of b) ever factors again."""
 
-def _direct_info(st):
-    """what solverconvergence reports: the record of the state's last solve (rls_direct_status)"""
-    return {"info": int(st.info), "lambda": float(st.lambda_), "factorizations": int(st.factorizations)} if st is not None else {}
-
-
-class DirectSolverState(AbstractSolverState):
-    """src/Direct.jl:12-15, plus lambda as init! normalised it for this b and the record of the solve"""
-
-    def __init__(self):
-        self.x = self.b = None
-        self.lam = 0.0
-        self.iteration = 0
-        self.info = None
-
-    def convergence(self):
-        return _direct_info(self.info)
-
-
-class DirectSolver(AbstractDirectSolver):
-    """src/Direct.jl:4-67: x = (A'A + lambda I) \\ A'b, then prox!(p, x) for every p in `proj`, in order.
-
-    * lambda goes on the DIAGONAL -- the Tikhonov system, the one CGNR and PseudoInverse (s / (s^2 + lambda)) solve and the
-      package documents (l2^2).  src/Direct.jl:59 writes `A'*A .+ lambda`, which broadcasts lambda onto every entry; for the
-      default lambda = 0 the two agree.
-    * Blocked Cholesky on the device (csrc/direct.hip) instead of `lu`.  The factor belongs to the solver and is reused by every
-      later solve -- and by every column of a matrix right-hand side -- while lambda stays; the reference factors on every
-      iterate.  It is formed from the operator's explicit Gram matrix (`AHA=`, e.g. `A.gram()`) where given, else A'A is
-      formed once on the device.
-    * A matrix that is not positive definite raises RLSError naming the column of the failing pivot (no NaN solution).
-    * One `iterate` completes the solve: callbacks fire at iterations 0 and 1.  The result does not depend on x0.
-    * solverconvergence: the record of the last solve, {"info", "lambda", "factorizations"} (no residual is formed).
-    * Float32 / ComplexF32 only; Float64 / ComplexF64 operators raise NotImplementedError.
-    * PseudoInverse (below) solves the same system from an SVD of A: lambda is free there and rank-deficient systems are solved."""
-
-    def __init__(self, A=None, *, AHA=None, reg=None, normalizeReg=None):
-        src = A if A is not None else (AHA.A if isinstance(AHA, NormalOperator) else AHA)
-        if isinstance(src, DeviceMatrix) and is_double(src.code):
-            raise NotImplementedError("DirectSolver: the Cholesky kernels are Float32 / ComplexF32; Float64 / ComplexF64 operators "
-                                      "are not supported (use CGNR, or solve on the host)")
-        self.A, self._op = _resolve_operator(A, AHA)
-        self.normalizeReg = normalizeReg or NoNormalization()
-        self.l2, self.proj = _direct_sort_regs(reg, self.normalizeReg, self.A)
-        self._plan = None
-        self.state = DirectSolverState()
-
-    def _new_state(self):
-        return DirectSolverState()
-
-    def _rows(self):
-        return self._op.M if self.A is not None else self._op.N
-
-    def _the_plan(self):
-        if self._plan is None:
-            self._plan = _DirectPlan(self._op)
-        return self._plan
-
-    def _init_batched(self, b, kw, previous):
-        if not (isinstance(b, DeviceMatrix) and _cold_start_only(kw)
-                and not isinstance(self.normalizeReg, MeasurementBasedNormalization)):  # per-column lambda: a factor per column
-            return None
-        st = previous if isinstance(previous, DirectBatchedState) and previous.fits(b) else DirectBatchedState(self, b)
-        st.init(b)
-        return st
-
-    def init_(self, state: DirectSolverState, b: DeviceVector, x0=0):
-        """init!(solver, state, b; x0 = 0)  src/Direct.jl:44-54"""
-        if b.n != self._rows():
-            raise ValueError(f"DimensionMismatch: b has length {b.n}, expected {self._rows()}")
-        N = self._op.N
-        self.l2 = normalize(self.normalizeReg, self.l2, self.A, b, in_solver=True)  # :51
-        start = _start_vector(x0, b, N, state)
-        if state.x is None or state.x.ctx is not b.ctx or state.x.dtype != b.dtype or state.x.n != N or state.b.n != b.n:
-            state.x, state.b = b.similar(N), b.similar()
-        state.b.copy_from(b)      # :52
-        _set_start(state.x, start)  # :53
-        state.lam = float(self.l2.lam)
-        state.iteration = 0
-        state.info = None
-
-    def iterate(self, state: Optional[DirectSolverState] = None):
-        """iterate(solver, state)  src/Direct.jl:56-67: the whole solve; None on the call after it"""
-        state = state or self.state
-        if state.iteration >= 1:
-            return None
-        kind, rest = _direct_fused_projection(self.proj)
-        state.info = self._the_plan().solve(state.lam, 1, state.b.ptr, state.b.n, state.x.ptr, state.x.n, kind)
-        for p in rest:
-            _prox(p, state.x)   # :62-64
-        state.iteration = 1
-        return state.x, state
-
-    def _run(self, state: DirectSolverState):
-        while self.iterate(state) is not None:
-            pass
-
-
-class _DirectColumnStatus:
-    def __init__(self, done):
-        self.done = done
-
-
-class DirectBatchedState(BatchedState):
-    """BatchedState for DirectSolver: all K columns through ONE rls_direct_solve on the solver's factor"""
-
-    def __init__(self, solver, B: DeviceMatrix):
-        super().__init__(solver, B)
-        self.X = DeviceMatrix(solver._op.N, B.N, B.dtype, B.ctx)
-        self.B = DeviceMatrix(B.M, B.N, B.dtype, B.ctx, lda=B.lda)
-        self.info = None
-
-    def fits(self, B: DeviceMatrix):
-        return (self.B.M, self.B.N, self.B.lda, self.B.dtype, self.B.ctx) == (B.M, B.N, B.lda, B.dtype, B.ctx)
-
-    def init(self, B: DeviceMatrix):
-        solver, ctx = self.solver, B.ctx
-        if B.M != solver._rows():
-            raise ValueError(f"DimensionMismatch: b has {B.M} rows, expected {solver._rows()}")
-        solver.l2 = normalize(solver.normalizeReg, solver.l2, solver.A, None, in_solver=True)
-        check(ctx.handle, ctx.lib.rls_memcpy_d2d(ctx.handle, self.B.ptr, B.ptr, B.lda * B.N * B.dtype.itemsize), "rls_memcpy_d2d")
-        self.X.fill_(0)
-        self.lam = float(solver.l2.lam)
-        self.iteration = 0
-        self.info = None
-        self.active = [True] * self.K
-
-    def _max_steps(self):
-        return 1
-
-    def _step(self, n):
-        if self.info is not None or n < 1:
-            return
-        solver = self.solver
-        kind, rest = _direct_fused_projection(solver.proj)
-        self.info = solver._the_plan().solve(self.lam, self.K, self.B.ptr, self.B.lda, self.X.ptr, self.X.lda, kind)
-        for j in range(self.K if rest else 0):
-            x = self.X.column_view(j)
-            for p in rest:
-                _prox(p, x)
-
-    def status(self):
-        return [_DirectColumnStatus(self.info is not None)] * self.K
-
-    def convergence(self):
-        return [_direct_info(self.info)] * self.K
-
-    def _plain(self):
-        return DirectSolverState()
-
-
-# --------------------------------------------------------------------------------------------
-# PseudoInverse: src/Direct.jl:70-162
-# --------------------------------------------------------------------------------------------
-
-
-class _PinvPlan:
-    """rls_pinv: the one-sided Jacobi SVD A = W V' of one operator (csrc/pinv.hip).  It belongs to the SOLVER and is factored on
-    first use; lambda is an argument of every solve, so no change of lambda (or of b) ever factors again."""
-
-    def __init__(self, op: OperatorHandle):
-        self._keep = (op, op.ctx)   # destruction order: plan before operator before context
-        h = C.c_void_p()
-        check(op.ctx.handle, op.ctx.lib.rls_pinv_create(op.handle, C.byref(h)), "rls_pinv_create")
-        self.handle = h
+    _create_fn, _destroy_fn = "rls_pinv_create", "rls_pinv_destroy"
 
     def factor(self):
         """a no-op once a good factor is held; raises where the sweep cap was hit"""
-        ctx = self._keep[1]
-        check(ctx.handle, ctx.lib.rls_pinv_factor(self.handle), "rls_pinv_factor")
+        self._call("rls_pinv_factor")
         st = self.status()
         if st.info != 0:
             raise _lib.RLSError(f"PseudoInverse: the Jacobi sweeps did not converge within {st.sweeps} sweeps (info = {st.info}); "
@@ -2907,31 +2756,27 @@ class _PinvPlan:
 
     def solve(self, lam, K, B, ldb, X, ldx, proj_kind):
         """factor (once), solve the K columns with this lambda; returns the status behind the solve"""
-        ctx = self._keep[1]
         self.factor()
-        check(ctx.handle, ctx.lib.rls_pinv_solve(self.handle, float(lam), int(K), B, int(ldb), X, int(ldx), int(proj_kind)), "rls_pinv_solve")
+        self._call("rls_pinv_solve", float(lam), int(K), B, int(ldb), X, int(ldx), int(proj_kind))
         return self.status()
 
     def status(self):
-        ctx = self._keep[1]
         st = _lib.PinvStatus()
-        check(ctx.handle, ctx.lib.rls_pinv_get_status(self.handle, C.byref(st)), "rls_pinv_get_status")
+        self._call("rls_pinv_get_status", C.byref(st))
         bs = self.block_status()
         st.block, st.block_sweeps = int(bs.block), int(bs.block_sweeps)   # (solverconvergence reports them beside the plain sweeps)
         return st
 
     def block_status(self):
         """what the blocked sweeps of the last factorisation did (rls_pinv_block_status); block == 0: they did not run"""
-        ctx = self._keep[1]
         bs = _lib.PinvBlockStatus()
-        check(ctx.handle, ctx.lib.rls_pinv_get_block_status(self.handle, C.byref(bs)), "rls_pinv_get_block_status")
+        self._call("rls_pinv_get_block_status", C.byref(bs))
         return bs
 
     def singular_values(self):
-        op, ctx = self._keep
         self.factor()
-        out = np.empty(op.N, dtype=np.float32)
-        check(ctx.handle, ctx.lib.rls_pinv_singular_values(self.handle, out.ctypes.data_as(C.POINTER(C.c_float))), "rls_pinv_singular_values")
+        out = np.empty(self._keep[0].N, dtype=np.float32)
+        self._call("rls_pinv_singular_values", out.ctypes.data_as(C.POINTER(C.c_float)))
         return out
 
     def factor_to_host(self):
@@ -2939,7 +2784,7 @@ class _PinvPlan:
         op, ctx = self._keep
         self.factor()
         W, V, ldw, ldv = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int64()
-        check(ctx.handle, ctx.lib.rls_pinv_get_factor(self.handle, C.byref(W), C.byref(ldw), C.byref(V), C.byref(ldv)), "rls_pinv_get_factor")
+        self._call("rls_pinv_get_factor", C.byref(W), C.byref(ldw), C.byref(V), C.byref(ldv))
         out = []
         for ptr, ld, rows in ((W, ldw.value, op.M), (V, ldv.value, op.N)):
             host = np.empty((ld, op.N), dtype=op.dtype, order="F")
@@ -2947,14 +2792,10 @@ class _PinvPlan:
             out.append(np.ascontiguousarray(host[:rows]))
         return tuple(out)
 
-    def __del__(self):
-        try:
-            ctx = self._keep[1]
-            if self.handle and ctx.handle:
-                ctx.lib.rls_pinv_destroy(self.handle)
-        except Exception:
-            pass
-        self.handle = None
+
+def _direct_info(st):
+    """what solverconvergence reports: the record of the state's last solve (rls_direct_status)"""
+    return {"info": int(st.info), "lambda": float(st.lambda_), "factorizations": int(st.factorizations)} if st is not None else {}
 
 
 def _pinv_info(st):
@@ -2965,8 +2806,10 @@ def _pinv_info(st):
             "block": int(st.block), "block_sweeps": int(st.block_sweeps)}
 
 
-class PseudoInverseState(AbstractSolverState):
-    """src/Direct.jl:79-82, plus lambda as init! normalised it for this b and the record of the solve"""
+class _DirectFamilyState(AbstractSolverState):
+    """x and b, plus lambda as init! normalised it for this b and the record of the solve; a subclass names its `_info` formatter"""
+
+    _info = None
 
     def __init__(self):
         self.x = self.b = None
@@ -2975,97 +2818,31 @@ class PseudoInverseState(AbstractSolverState):
         self.info = None
 
     def convergence(self):
-        return _pinv_info(self.info)
+        return self._info(self.info)
 
 
-class PseudoInverse(AbstractDirectSolver):
-    """src/Direct.jl:70-162: x = V diag(s / (s^2 + lambda)) U' b, then prox!(p, x) for every p in `proj`, in order.
+class DirectSolverState(_DirectFamilyState):
+    """src/Direct.jl:12-15"""
 
-    * One-sided (Hestenes) Jacobi SVD on the device (csrc/pinv.hip) instead of LAPACK's `svd`: A = W V' with orthogonal columns
-      w_j of norm s_j, so x = V diag(1 / (s^2 + lambda)) W' b -- two products and a scale.  The factor belongs to the solver and
-      is formed on the first solve (the reference factors in the constructor).
-    * lambda belongs to the SOLVE: `solver.l2 = ...`, a new b under MeasurementBasedNormalization and the columns of a matrix
-      right-hand side with per-column lambda all run on the one factor.
-    * Rank-deficient systems (wide A, repeated or zero columns, lambda = 0) are solved, not refused: column j is dropped when
-      s_j <= 1e-6 ||A||_F, the level below which the factorisation stops orthogonalising.  That truncation is the one
-      deviation from src/Direct.jl:158 (LAPACK hands the reference noise-level s there).
-    * One `iterate` completes the solve: callbacks fire at iterations 0 and 1.  The result does not depend on x0.
-    * Ahead of the plain sweeps the factorisation can run blocked sweeps on the matrix cores (DESIGN 4.13): `ctx.tune(pinv_block=16)`
-      or 32 forces them, 0 switches them off, -1 (the default) is automatic.  They shorten the plain sweeps and decide nothing.
-    * solverconvergence: {"info", "lambda", "factorizations", "sweeps", "block", "block_sweeps"} (`sweeps` counts the plain ones;
-      `block` = 0: no blocked sweeps ran); `singular_values()` gives s, descending, on the host.
-    * Needs A itself (`AHA=` alone raises ValueError); Float32 / ComplexF32 only (Float64 / ComplexF64: NotImplementedError)."""
-
-    def __init__(self, A=None, *, AHA=None, reg=None, normalizeReg=None):
-        src = A if A is not None else (AHA.A if isinstance(AHA, NormalOperator) else None)
-        if src is None:
-            raise ValueError("PseudoInverse needs the matrix A itself: a Gram matrix (AHA=) alone has no singular value decomposition of A")
-        if isinstance(src, DeviceMatrix) and is_double(src.code):
-            raise NotImplementedError("PseudoInverse: the Jacobi kernels are Float32 / ComplexF32; Float64 / ComplexF64 operators "
-                                      "are not supported (use CGNR, or solve on the host)")
-        self.A, self._op = _resolve_operator(A, AHA)
-        self.normalizeReg = normalizeReg or NoNormalization()
-        self.l2, self.proj = _direct_sort_regs(reg, self.normalizeReg, self.A)
-        self._plan = None
-        self.state = PseudoInverseState()
-
-    def _new_state(self):
-        return PseudoInverseState()
-
-    def _rows(self):
-        return self._op.M
-
-    def _the_plan(self):
-        if self._plan is None:
-            self._plan = _PinvPlan(self._op)
-        return self._plan
-
-    def singular_values(self):
-        """the singular values of A, descending (a host array; factors on first use)"""
-        return self._the_plan().singular_values()
-
-    def _init_batched(self, b, kw, previous):
-        if not (isinstance(b, DeviceMatrix) and _cold_start_only(kw)):
-            return None
-        st = previous if isinstance(previous, PseudoInverseBatchedState) and previous.fits(b) else PseudoInverseBatchedState(self, b)
-        st.init(b)
-        return st
-
-    def init_(self, state: PseudoInverseState, b: DeviceVector, x0=0):
-        """init!(solver, state, b; x0 = 0)  src/Direct.jl:139-149"""
-        if b.n != self._rows():
-            raise ValueError(f"DimensionMismatch: b has length {b.n}, expected {self._rows()}")
-        N = self._op.N
-        self.l2 = normalize(self.normalizeReg, self.l2, self.A, b, in_solver=True)  # :146
-        start = _start_vector(x0, b, N, state)
-        if state.x is None or state.x.ctx is not b.ctx or state.x.dtype != b.dtype or state.x.n != N or state.b.n != b.n:
-            state.x, state.b = b.similar(N), b.similar()
-        state.b.copy_from(b)      # :147
-        _set_start(state.x, start)  # :148
-        state.lam = float(self.l2.lam)
-        state.iteration = 0
-        state.info = None
-
-    def iterate(self, state: Optional[PseudoInverseState] = None):
-        """iterate(solver, state)  src/Direct.jl:151-162: the whole solve; None on the call after it"""
-        state = state or self.state
-        if state.iteration >= 1:
-            return None
-        kind, rest = _direct_fused_projection(self.proj)
-        state.info = self._the_plan().solve(state.lam, 1, state.b.ptr, state.b.n, state.x.ptr, state.x.n, kind)
-        for p in rest:
-            _prox(p, state.x)   # :157-159
-        state.iteration = 1
-        return state.x, state
-
-    def _run(self, state: PseudoInverseState):
-        while self.iterate(state) is not None:
-            pass
+    _info = staticmethod(_direct_info)
 
 
-class PseudoInverseBatchedState(BatchedState):
-    """BatchedState for PseudoInverse: the K columns on the solver's one factor -- ONE rls_pinv_solve where they share lambda,
-    K single-column calls where MeasurementBasedNormalization gives every column its own"""
+class PseudoInverseState(_DirectFamilyState):
+    """src/Direct.jl:79-82"""
+
+    _info = staticmethod(_pinv_info)
+
+
+class _DirectColumnStatus:
+    def __init__(self, done):
+        self.done = done
+
+
+class _DirectFamilyBatchedState(BatchedState):
+    """BatchedState of the direct solvers: the K columns on the solver's one factor -- ONE `solve` where they share lambda, K
+    single-column calls where MeasurementBasedNormalization gives every column its own.  A subclass names its vector state."""
+
+    _state_cls = None
 
     def __init__(self, solver, B: DeviceMatrix):
         super().__init__(solver, B)
@@ -3116,10 +2893,158 @@ class PseudoInverseBatchedState(BatchedState):
         return [_DirectColumnStatus(self.infos is not None)] * self.K
 
     def convergence(self):
-        return [_pinv_info(i) for i in self.infos] if self.infos is not None else [{}] * self.K
+        return [self._state_cls._info(i) for i in self.infos] if self.infos is not None else [{}] * self.K
 
     def _plain(self):
-        return PseudoInverseState()
+        return self._state_cls()
+
+
+class DirectBatchedState(_DirectFamilyBatchedState):
+    """BatchedState for DirectSolver: all K columns through ONE rls_direct_solve on the solver's factor (lambda is the solver's:
+    DirectSolver hands a matrix right-hand side with per-column lambda to the per-column scheduler)"""
+
+    _state_cls = DirectSolverState
+
+
+class PseudoInverseBatchedState(_DirectFamilyBatchedState):
+    """BatchedState for PseudoInverse: ONE rls_pinv_solve where the columns share lambda, one per column where they do not"""
+
+    _state_cls = PseudoInverseState
+
+
+class AbstractDirectSolver(AbstractLinearSolver):
+    """src/RegularizedLeastSquares.jl:135-148 (the category has no isapplicable rule: `False`, as in the reference).
+
+    It holds what DirectSolver and PseudoInverse do the same way: x = (factor of A, lambda) applied to b, then prox!(p, x) for
+    every p in `proj`.  A subclass names its plan, vector state and batched state, says how long b is (`_rows`), refuses in its
+    constructor what its kernels do not cover, and then calls `_setup`.  The category itself has no constructor."""
+
+    _plan_cls = _state_cls = _batched_cls = None
+    _batched_per_column_lambda = False   # True: a matrix right-hand side under MeasurementBasedNormalization stays batched
+
+    def _setup(self, A, AHA, reg, normalizeReg):
+        """the constructor once the subclass has refused what it must  (src/Direct.jl:17-42, :84-137)"""
+        self.A, self._op = _resolve_operator(A, AHA)
+        self.normalizeReg = normalizeReg or NoNormalization()
+        self.l2, self.proj = _direct_sort_regs(reg, self.normalizeReg, self.A)
+        self._plan = None
+        self.state = self._state_cls()
+
+    def _new_state(self):
+        return self._state_cls()
+
+    def _the_plan(self):
+        if self._plan is None:
+            self._plan = self._plan_cls(self._op)
+        return self._plan
+
+    def _init_batched(self, b, kw, previous):
+        if not (isinstance(b, DeviceMatrix) and _cold_start_only(kw)):
+            return None
+        if isinstance(self.normalizeReg, MeasurementBasedNormalization) and not self._batched_per_column_lambda:
+            return None   # per-column lambda, and the factor holds lambda: a factor per column
+        st = previous if isinstance(previous, self._batched_cls) and previous.fits(b) else self._batched_cls(self, b)
+        st.init(b)
+        return st
+
+    def init_(self, state, b: DeviceVector, x0=0):
+        """init!(solver, state, b; x0 = 0)  src/Direct.jl:44-54 (DirectSolver), :139-149 (PseudoInverse)"""
+        if b.n != self._rows():
+            raise ValueError(f"DimensionMismatch: b has length {b.n}, expected {self._rows()}")
+        N = self._op.N
+        self.l2 = normalize(self.normalizeReg, self.l2, self.A, b, in_solver=True)  # :51, :146
+        start = _start_vector(x0, b, N, state)
+        if state.x is None or state.x.ctx is not b.ctx or state.x.dtype != b.dtype or state.x.n != N or state.b.n != b.n:
+            state.x, state.b = b.similar(N), b.similar()
+        state.b.copy_from(b)      # :52, :147
+        _set_start(state.x, start)  # :53, :148
+        state.lam = float(self.l2.lam)
+        state.iteration = 0
+        state.info = None
+
+    def iterate(self, state=None):
+        """iterate(solver, state)  src/Direct.jl:56-67 (DirectSolver), :151-162 (PseudoInverse): the whole solve; None on the
+        call after it"""
+        state = state or self.state
+        if state.iteration >= 1:
+            return None
+        kind, rest = _direct_fused_projection(self.proj)
+        state.info = self._the_plan().solve(state.lam, 1, state.b.ptr, state.b.n, state.x.ptr, state.x.n, kind)
+        for p in rest:
+            _prox(p, state.x)   # :62-64, :157-159
+        state.iteration = 1
+        return state.x, state
+
+    def _run(self, state):
+        while self.iterate(state) is not None:
+            pass
+
+
+class DirectSolver(AbstractDirectSolver):
+    """src/Direct.jl:4-67: x = (A'A + lambda I) \\ A'b, then prox!(p, x) for every p in `proj`, in order.
+
+    * lambda goes on the DIAGONAL -- the Tikhonov system, the one CGNR and PseudoInverse (s / (s^2 + lambda)) solve and the
+      package documents (l2^2).  src/Direct.jl:59 writes `A'*A .+ lambda`, which broadcasts lambda onto every entry; for the
+      default lambda = 0 the two agree.
+    * Blocked Cholesky on the device (csrc/direct.hip) instead of `lu`.  The factor belongs to the solver and is reused by every
+      later solve -- and by every column of a matrix right-hand side -- while lambda stays; the reference factors on every
+      iterate.  It is formed from the operator's explicit Gram matrix (`AHA=`, e.g. `A.gram()`) where given, else A'A is
+      formed once on the device.
+    * A matrix that is not positive definite raises RLSError naming the column of the failing pivot (no NaN solution).
+    * One `iterate` completes the solve: callbacks fire at iterations 0 and 1.  The result does not depend on x0.
+    * solverconvergence: the record of the last solve, {"info", "lambda", "factorizations"} (no residual is formed).
+    * Float32 / ComplexF32 only; Float64 / ComplexF64 operators raise NotImplementedError.
+    * PseudoInverse (below) solves the same system from an SVD of A: lambda is free there and rank-deficient systems are solved."""
+
+    _plan_cls, _state_cls, _batched_cls = _DirectPlan, DirectSolverState, DirectBatchedState
+
+    def __init__(self, A=None, *, AHA=None, reg=None, normalizeReg=None):
+        src = A if A is not None else (AHA.A if isinstance(AHA, NormalOperator) else AHA)
+        if isinstance(src, DeviceMatrix) and is_double(src.code):
+            raise NotImplementedError("DirectSolver: the Cholesky kernels are Float32 / ComplexF32; Float64 / ComplexF64 operators "
+                                      "are not supported (use CGNR, or solve on the host)")
+        self._setup(A, AHA, reg, normalizeReg)
+
+    def _rows(self):
+        return self._op.M if self.A is not None else self._op.N
+
+
+class PseudoInverse(AbstractDirectSolver):
+    """src/Direct.jl:70-162: x = V diag(s / (s^2 + lambda)) U' b, then prox!(p, x) for every p in `proj`, in order.
+
+    * One-sided (Hestenes) Jacobi SVD on the device (csrc/pinv.hip) instead of LAPACK's `svd`: A = W V' with orthogonal columns
+      w_j of norm s_j, so x = V diag(1 / (s^2 + lambda)) W' b -- two products and a scale.  The factor belongs to the solver and
+      is formed on the first solve (the reference factors in the constructor).
+    * lambda belongs to the SOLVE: `solver.l2 = ...`, a new b under MeasurementBasedNormalization and the columns of a matrix
+      right-hand side with per-column lambda all run on the one factor.
+    * Rank-deficient systems (wide A, repeated or zero columns, lambda = 0) are solved, not refused: column j is dropped when
+      s_j <= 1e-6 ||A||_F, the level below which the factorisation stops orthogonalising.  That truncation is the one
+      deviation from src/Direct.jl:158 (LAPACK hands the reference noise-level s there).
+    * One `iterate` completes the solve: callbacks fire at iterations 0 and 1.  The result does not depend on x0.
+    * Ahead of the plain sweeps the factorisation can run blocked sweeps on the matrix cores (DESIGN 4.13): `ctx.tune(pinv_block=16)`
+      or 32 forces them, 0 switches them off, -1 (the default) is automatic.  They shorten the plain sweeps and decide nothing.
+    * solverconvergence: {"info", "lambda", "factorizations", "sweeps", "block", "block_sweeps"} (`sweeps` counts the plain ones;
+      `block` = 0: no blocked sweeps ran); `singular_values()` gives s, descending, on the host.
+    * Needs A itself (`AHA=` alone raises ValueError); Float32 / ComplexF32 only (Float64 / ComplexF64: NotImplementedError)."""
+
+    _plan_cls, _state_cls, _batched_cls = _PinvPlan, PseudoInverseState, PseudoInverseBatchedState
+    _batched_per_column_lambda = True
+
+    def __init__(self, A=None, *, AHA=None, reg=None, normalizeReg=None):
+        src = A if A is not None else (AHA.A if isinstance(AHA, NormalOperator) else None)
+        if src is None:
+            raise ValueError("PseudoInverse needs the matrix A itself: a Gram matrix (AHA=) alone has no singular value decomposition of A")
+        if isinstance(src, DeviceMatrix) and is_double(src.code):
+            raise NotImplementedError("PseudoInverse: the Jacobi kernels are Float32 / ComplexF32; Float64 / ComplexF64 operators "
+                                      "are not supported (use CGNR, or solve on the host)")
+        self._setup(A, AHA, reg, normalizeReg)
+
+    def _rows(self):
+        return self._op.M
+
+    def singular_values(self):
+        """the singular values of A, descending (a host array; factors on first use)"""
+        return self._the_plan().singular_values()
 
 
 def _columns(b) -> List[DeviceVector]:

@@ -52,6 +52,26 @@ def test_classes_are_public(rls):
         assert not issubclass(rls.DirectSolver, cat)
 
 
+def test_the_two_direct_solvers_share_one_python_path(rls):
+    """DirectSolver and PseudoInverse differ in their plans and refusals; the rest is ONE function each, held by the category"""
+    from rls_amd.solvers import _DirectPlan, _PinvPlan
+
+    D, P = rls.DirectSolver, rls.PseudoInverse
+    for name in ("init_", "iterate", "_run", "_init_batched", "_new_state", "_the_plan"):
+        assert getattr(D, name) is getattr(P, name) is getattr(rls.AbstractDirectSolver, name), name
+    assert _DirectPlan.__del__ is _PinvPlan.__del__ and _DirectPlan.__init__ is _PinvPlan.__init__
+    assert _DirectPlan.solve is not _PinvPlan.solve and _DirectPlan.status is not _PinvPlan.status
+    for name in ("_step", "fits", "init", "status", "convergence", "_max_steps", "_plain"):
+        assert getattr(rls.DirectBatchedState, name) is getattr(rls.PseudoInverseBatchedState, name), name
+    assert rls.DirectSolverState.convergence is rls.PseudoInverseState.convergence
+    assert rls.DirectSolverState is not rls.PseudoInverseState and rls.DirectBatchedState is not rls.PseudoInverseBatchedState
+    assert not issubclass(P, D) and not issubclass(D, P)
+    assert not issubclass(rls.PseudoInverseBatchedState, rls.DirectBatchedState)
+    # the category stays a category: it names no plan and has no constructor of its own
+    assert rls.AbstractDirectSolver._plan_cls is None and "__init__" not in vars(rls.AbstractDirectSolver)
+    assert not rls.isapplicable(rls.AbstractDirectSolver, [rls.L2Regularization(0.1)])
+
+
 def test_linear_solver_list_is_unchanged(rls):
     assert rls.linearSolverList() == [rls.CGNR, rls.Kaczmarz, rls.FISTA, rls.OptISTA, rls.POGM, rls.ADMM, rls.SplitBregman]
     assert rls.DirectSolver not in rls.applicableSolverList([rls.L2Regularization(0.1)])

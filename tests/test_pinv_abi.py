@@ -74,12 +74,16 @@ def test_linear_solver_list_is_unchanged(rls):
 
 
 def test_constructor_sorts_reg_and_keeps_the_error_text(rls):
-    """PseudoInverse.__init__ goes through _direct_sort_regs (the source says so: no device is needed to read it)"""
+    """PseudoInverse.__init__ goes through _direct_sort_regs: in the one function both direct solvers' constructors end in (the
+    source says so: no device is needed to read it)"""
     import inspect
 
     from rls_amd.solvers import _direct_sort_regs
 
-    src = inspect.getsource(rls.PseudoInverse.__init__)
+    assert rls.PseudoInverse._setup is rls.DirectSolver._setup is rls.AbstractDirectSolver._setup
+    assert "self._setup(A, AHA, reg, normalizeReg)" in inspect.getsource(rls.PseudoInverse.__init__)
+    assert "self._setup(A, AHA, reg, normalizeReg)" in inspect.getsource(rls.DirectSolver.__init__)
+    src = inspect.getsource(rls.AbstractDirectSolver._setup)
     assert "_direct_sort_regs(reg, self.normalizeReg, self.A)" in src
     assert list(inspect.signature(rls.PseudoInverse.__init__).parameters) == list(inspect.signature(rls.DirectSolver.__init__).parameters)
     given, pos, real, l1 = rls.L2Regularization(0.25), rls.PositiveRegularization(), rls.RealRegularization(), rls.L1Regularization(0.3)
