@@ -219,13 +219,6 @@ __global__ __launch_bounds__(PGM_THREADS) void pogm_auto_kernel(E* __restrict__ 
 // ---------------------------------------------------------------------------------------------
 constexpr int PGMB_THREADS = 1024;
 
-template <typename E>
-__device__ static inline E pgmb_parts(const E* __restrict__ Vpart, int S, int nrhs_pad, int b, int64_t N, int64_t i) {
-  E v = Vpart[(int64_t)b * N + i];
-  for (int s = 1; s < S; ++s) v = elem<E>::add(v, Vpart[((int64_t)s * nrhs_pad + b) * N + i]);
-  return v;
-}
-
 // x0 = A^H b from the partial rows, ||x0||, the state vectors as OptISTA.init_ / POGM.init_ leave them (x = 0 and every
 // other vector 0, res = Inf), the first gradient point (x = 0) in the panel, the column's record
 template <typename E>
@@ -236,11 +229,12 @@ __global__ __launch_bounds__(PGMB_THREADS) void pgmb_init_kernel(rls_pgmb D) {
   E* x0 = (E*)D.x0 + off;
   E* res = (E*)D.res + off;
   E* v[5] = {(E*)D.v0 + off, (E*)D.v1 + off, (E*)D.v2 + off, (E*)D.o0 + off, D.v3 ? (E*)D.v3 + off : nullptr};
-  const panel_col<E> pc = panel_column<E>((E*)D.panel, n, b, D.half);
+  const operand_view<E> O(D.ops);
+  const panel_col<E> pc = O.column(n, b);
   const float inf = __builtin_huge_valf();
   double nn = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += PGMB_THREADS) {
-    const E a = pgmb_parts<E>((const E*)D.Vpart, D.S, D.nrhs_pad, b, n, i);
+    const E a = O.sum(b, n, i);
     x0[i] = a;
     nn += redot<E>(a, a);
 #pragma unroll
@@ -285,8 +279,8 @@ __global__ __launch_bounds__(PGMB_THREADS) void pgmb_update_kernel(rls_pgmb D) {
   E* res = (E*)D.res + off;
   E* w = RESTART ? (E*)D.v3 + off : nullptr;
   const E* x0 = (const E*)D.x0 + off;
-  const E* Vpart = (const E*)D.Vpart;
-  const panel_col<E> pc = panel_column<E>((E*)D.panel, n, b, D.half);
+  const operand_view<E> O(D.ops);
+  const panel_col<E> pc = O.column(n, b);
   optista_coefs oc = {};
   pogm_coefs gc = {};
   pogm_auto_coefs au = {};
@@ -310,7 +304,7 @@ __global__ __launch_bounds__(PGMB_THREADS) void pgmb_update_kernel(rls_pgmb D) {
     for (int e = 0; e < EPT; ++e) {
       const int64_t i = base + threadIdx.x + (int64_t)e * PGMB_THREADS;
       const int64_t ic = i < n ? i : n - 1;
-      raw[e] = pgmb_parts<E>(Vpart, D.S, D.nrhs_pad, b, n, ic);
+      raw[e] = O.sum(b, n, ic);
       x0v[e] = x0[ic];
       p0[e] = a0[ic];
       p1[e] = a1[ic];
@@ -377,7 +371,7 @@ static void pgmb_launch_update_typed(rls_ctx* ctx, const rls_pgmb& D) {
 
 static bool pgmb_desc_ok(const rls_pgmb& D) {
   return D.kind >= RLS_PGMB_OPTISTA && D.kind <= RLS_PGMB_POGM_RESTART && D.N > 0 && D.ldv >= D.N && D.nrhs >= 1 && D.v0 && D.v1 &&
-         D.v2 && D.o0 && D.res && D.x0 && D.Vpart && D.panel && D.sc && D.S >= 1 && D.nrhs_pad >= D.nrhs &&
+         D.v2 && D.o0 && D.res && D.x0 && D.ops.Vpart && D.ops.panel && D.sc && D.ops.S >= 1 && D.ops.nrhs_pad >= D.nrhs &&
          (D.kind != RLS_PGMB_POGM_RESTART || D.v3) && (D.kind == RLS_PGMB_POGM_RESTART || D.table) &&
          D.reg_kind >= RLS_REG_NONE && D.reg_kind <= RLS_REG_L2 && D.proj_kind >= RLS_PROJ_NONE && D.proj_kind <= RLS_PROJ_POSITIVE;
 }

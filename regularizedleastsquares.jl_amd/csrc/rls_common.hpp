@@ -1007,6 +1007,16 @@ bool rls_pgm_resident_ok(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, cons
 int32_t rls_pgm_resident_launch(rls_ctx* ctx, int32_t dtype, const rls_pgm_desc& D, const rls_pgm_coefs& C, void* sync,
                                 int n_steps, unsigned spin_limit);
 
+// What the per-column kernels of a shared-A batched plan get of its matrix-core operands (skinny.hip): AHA u as `S` partial rows
+// per column, and the operand panel their next point goes into.  Type-erased, for descriptors that cross translation units; the
+// kernels use operand_view<E> (below).  Both pointers null (the default) = the single-column plans.
+struct rls_operands {
+  const void* Vpart = nullptr;  // [S][nrhs_pad][N]
+  int S = 1, nrhs_pad = 16;
+  void* panel = nullptr;        // layout: panel_col (below)
+  int half = 0;
+};
+
 // ---- batched OptISTA / POGM (K right-hand sides sharing A): kernels in pgm.hip, plan in solvers.hip ----------------------
 // one column's scalar record
 struct pgmb_scalars {
@@ -1024,10 +1034,7 @@ struct rls_pgmb {
                              // iteration parity: x is v0 when it is even), z
   void* v3;                  // POGM with restart: w
   void *o0, *res, *x0;       // OptISTA zold / POGM xold; state.res; A^H b
-  const void* Vpart;         // the skinny product's partial rows [S][nrhs_pad][N]
-  int S, nrhs_pad;
-  float* panel;              // operand panel of the next gradient points
-  int half;
+  rls_operands ops;          // the partial rows of AHA x and the operand panel of the next gradient points
   pgmb_scalars* sc;          // [nrhs]
   const float* table;        // [max_iter][8] index-only coefficients (rls_pgm_coefs' rows); unused by RLS_PGMB_POGM_RESTART
   int reg_kind, proj_kind, max_iter;
@@ -1086,13 +1093,32 @@ struct panel_col {
     }
   }
 };
+// rls_operands with its element type.  The project's results are bit-reproducible, and a column's bits do not depend on how many
+// columns ride along: every kernel that reads the partial rows sums them HERE, in the one fixed order s = 0, 1, 2, ...
+// (skinny_u_kernel's register form issues the loads in batches of four and adds in the same order).
 template <typename E>
-__device__ static inline panel_col<E> panel_column(E* panel, int64_t n, int b, int half) {
-  panel_col<E> c;
-  c.full = half ? nullptr : panel + (int64_t)(b >> 4) * n * 16 + (b & 15);
-  c.half = half ? reinterpret_cast<float*>(panel) + (b & 7) : nullptr;
-  return c;
-}
+struct operand_view {
+  const E* Vpart = nullptr;
+  int S = 1, nrhs_pad = 16;
+  E* panel = nullptr;
+  int half = 0;
+  operand_view() = default;
+  __host__ __device__ explicit operand_view(const rls_operands& o)
+      : Vpart((const E*)o.Vpart), S(o.S), nrhs_pad(o.nrhs_pad), panel((E*)o.panel), half(o.half) {}
+  // element i of column b's AHA u (columns N elements apart)
+  __device__ inline E sum(int b, int64_t N, int64_t i) const {
+    E v = Vpart[(int64_t)b * N + i];
+    for (int s = 1; s < S; ++s) v = elem<E>::add(v, Vpart[((int64_t)s * nrhs_pad + b) * N + i]);
+    return v;
+  }
+  // column b's slot in the panel of n-element columns
+  __device__ inline panel_col<E> column(int64_t n, int b) const {
+    panel_col<E> c;
+    c.full = half ? nullptr : panel + (int64_t)(b >> 4) * n * 16 + (b & 15);
+    c.half = half ? reinterpret_cast<float*>(panel) + (b & 7) : nullptr;
+    return c;
+  }
+};
 #endif
 
 // everything the matrix-core batched kernels need (skinny.hip)

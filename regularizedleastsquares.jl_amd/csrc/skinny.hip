@@ -451,13 +451,6 @@ __device__ static inline double abs2d(E a) {
   return (double)elem<E>::re(a) * (double)elem<E>::re(a) + (double)elem<E>::im(a) * (double)elem<E>::im(a);
 }
 
-template <typename E>
-__device__ static inline E sum_parts(const E* __restrict__ Vpart, int S, int nrhs_pad, int b, int64_t N, int64_t i) {
-  E v = Vpart[(int64_t)b * N + i];
-  for (int s = 1; s < S; ++s) v = elem<E>::add(v, Vpart[((int64_t)s * nrhs_pad + b) * N + i]);
-  return v;
-}
-
 __device__ static inline void cg_scalars_init(cgnr_scalars* sc, double rr, float lambda, float rel_tol, int max_iter) {
   sc->rr = rr;
   sc->z0 = sqrt(rr);
@@ -489,11 +482,9 @@ __device__ static inline void cg_scalars_step(cgnr_scalars* sc, double zeta, dou
 
 template <typename E, bool INIT, int EPT, int NT>
 __global__ __launch_bounds__(NT) void skinny_u_kernel(E* __restrict__ X, E* __restrict__ R, E* __restrict__ P,
-                                                               E* __restrict__ V, int64_t ldv,
-                                                               const E* __restrict__ Vpart, int S, int nrhs_pad,
-                                                               int64_t N, E* __restrict__ Pp, int half,
-                                                               cgnr_scalars* scv, float lambda_in, float rel_tol,
-                                                               int max_iter) {
+                                                               E* __restrict__ V, int64_t ldv, int64_t N,
+                                                               operand_view<E> O, cgnr_scalars* scv, float lambda_in,
+                                                               float rel_tol, int max_iter) {
   __shared__ double sm[48];
   const int b = blockIdx.x;
   cgnr_scalars* sc = scv + b;
@@ -501,11 +492,11 @@ __global__ __launch_bounds__(NT) void skinny_u_kernel(E* __restrict__ X, E* __re
   E* r = R + (int64_t)b * ldv;
   E* p = P + (int64_t)b * ldv;
   E* v = V + (int64_t)b * ldv;
-  const panel_col<E> pp_out = panel_column<E>(Pp, N, b, half);
+  const panel_col<E> pp_out = O.column(N, b);
   if constexpr (INIT) {
     double rr = 0.0;
     for (int64_t i = threadIdx.x; i < N; i += NT) {
-      const E ri = sum_parts<E>(Vpart, S, nrhs_pad, b, N, i);
+      const E ri = O.sum(b, N, i);
       x[i] = elem<E>::zero();
       v[i] = elem<E>::zero();
       r[i] = ri;
@@ -521,6 +512,8 @@ __global__ __launch_bounds__(NT) void skinny_u_kernel(E* __restrict__ X, E* __re
     // scalars.  Written the obvious way -- scalars, then vectors, then one split after the other -- this was
     // five dependent memory round trips (8.8 us per launch at K = 16).
     const cgnr_scalars S0 = *sc;  // one scalar fetch, requested first, used after the vector loads are out
+    const E* __restrict__ Vpart = O.Vpart;
+    const int S = O.S, nrhs_pad = O.nrhs_pad;
     E pv[EPT], xv[EPT], rv[EPT], vv[EPT];
     int64_t ic[EPT];
 #pragma unroll
@@ -615,7 +608,7 @@ __global__ __launch_bounds__(NT) void skinny_u_kernel(E* __restrict__ X, E* __re
     const double zeta = sc->rr;
     double nre = 0.0, nim = 0.0, pp = 0.0;
     for (int64_t i = threadIdx.x; i < N; i += NT) {
-      const E vi = sum_parts<E>(Vpart, S, nrhs_pad, b, N, i);
+      const E vi = O.sum(b, N, i);
       v[i] = vi;
       const E pi = p[i];
       nre += (double)elem<E>::re(pi) * (double)elem<E>::re(vi) + (double)elem<E>::im(pi) * (double)elem<E>::im(vi);
@@ -803,8 +796,9 @@ static void launch_g(rls_ctx* ctx, const rls_skinny& K) {
 template <typename E, bool INIT, int EPT, int NT>
 static void launch_u_ept(rls_ctx* ctx, const rls_skinny& K, float lambda, float rel_tol, int max_iter) {
   hipLaunchKernelGGL((skinny_u_kernel<E, INIT, EPT, NT>), dim3((unsigned)K.nrhs), dim3(NT), 0, ctx->stream,
-                     (E*)K.X, (E*)K.R, (E*)K.P, (E*)K.V, K.ldv, (const E*)K.Vpart, K.splits,
-                     rls_skinny_pad(K.nrhs, K.half), K.N, (E*)K.Ppack, K.half, K.sc, lambda, rel_tol, max_iter);
+                     (E*)K.X, (E*)K.R, (E*)K.P, (E*)K.V, K.ldv, K.N,
+                     operand_view<E>(rls_operands{K.Vpart, K.splits, rls_skinny_pad(K.nrhs, K.half), K.Ppack, K.half}), K.sc,
+                     lambda, rel_tol, max_iter);
 }
 
 template <typename E, bool INIT>

@@ -46,6 +46,58 @@ struct rls_operator {
   void* slab = nullptr;     // per-workgroup partial-v slab of the fused one-pass normal operator (or null)
 };
 
+// The matrix-core operands of a shared-A batched plan (skinny.hip): K right-hand sides over one pass of A.  The plan's
+// per-column kernels write their next points into `panel`, the T kernel reads it and leaves T = A P in Tpack, the V kernel
+// leaves A^H T as `splits` partial rows per column in Vpart (with an explicit AHA: one product, panel -> Vpart).
+struct shared_operands {
+  float *panel = nullptr, *Tpack = nullptr;
+  void* Vpart = nullptr;
+  int splits = 1;
+  int half = 0;  // operand-panel layout, fixed at creation (rls_skinny_half)
+
+  // the shapes the matrix-core kernels take: A, and AHA when it is explicit
+  static bool supported(const rls_operator* op) {
+    return op->A && rls_skinny_ok(op->dtype, op->M, op->N, op->A, op->lda) &&
+           (!op->G || rls_skinny_ok(op->dtype, op->N, op->N, op->G, op->ldg));
+  }
+  void alloc(plan_buffers& mem, const rls_operator* op, int nrhs) {
+    size_t pb, tb, vb;
+    rls_skinny_sizes(op->ctx, op->dtype, op->M, op->N, nrhs, &pb, &tb, &vb, &splits);
+    half = rls_skinny_half(op->ctx, op->dtype, nrhs);
+    mem.dev(&panel, pb, true);  // the padding columns of the last group stay zero
+    mem.dev(&Tpack, tb, false);
+    mem.dev(&Vpart, vb, false);
+  }
+  bool allocated() const { return Vpart != nullptr; }  // "this plan is a batched one", whatever its nrhs
+
+  // the products' descriptor; X / R / P / V / sc are the batched CGNR update's (skinny_u_kernel), null for every other plan
+  rls_skinny desc(const rls_operator* op, int nrhs, int64_t ldv) const {
+    rls_skinny K;
+    K.A = op->A;
+    K.lda = op->lda;
+    K.M = op->M;
+    K.N = op->N;
+    K.G = op->G;  // explicit AHA (src/CGNR.jl:49): every operator apply of the batched loop is ONE product over it
+    K.ldg = op->ldg;
+    K.nrhs = nrhs;
+    K.half = half;
+    K.ngroups = rls_skinny_groups(nrhs, half);
+    K.splits = splits;
+    K.X = K.R = K.P = K.V = nullptr;
+    K.ldv = ldv;
+    K.Ppack = panel;
+    K.Tpack = Tpack;
+    K.Vpart = Vpart;
+    K.ldvp = op->N;
+    K.sc = nullptr;
+    return K;
+  }
+  // what the per-column kernels get (rls_common.hpp)
+  rls_operands erased(int nrhs) const { return rls_operands{Vpart, splits, rls_skinny_pad(nrhs, half), panel, half}; }
+  template <typename E>
+  operand_view<E> view(int nrhs) const { return operand_view<E>(erased(nrhs)); }
+};
+
 static int32_t op_normal(rls_operator* op, const void* p, void* v, const int* skip) {
   rls_ctx* ctx = op->ctx;
   if (op->G) return rls_launch_gemv(ctx, op->dtype, RLS_OP_N, op->N, op->N, 1.f, 0.f, op->G, op->ldg, p, 0.f, 0.f, v, skip);
@@ -287,10 +339,7 @@ struct rls_cgnr {
   double* gdots = nullptr;
   // batched plans on the matrix cores (skinny.hip): packed operands + row-split partials
   bool skinny = false;
-  float *Ppack = nullptr, *Tpack = nullptr;
-  void* Vpart = nullptr;
-  int splits = 1;
-  int half = 0;  // operand-panel layout, fixed at creation (rls_skinny_half)
+  shared_operands ops;
   // resident mode (normal.hip, cgnr_resident_kernel): sync block + lost-launch bookkeeping, per-workgroup partial dots
   resident_slot resident;
   double* rdots = nullptr;
@@ -343,26 +392,11 @@ static rls_gram_pipe cgnr_gram_desc(const rls_cgnr* s) {
 }
 
 static rls_skinny cgnr_skinny_desc(const rls_cgnr* s) {
-  rls_skinny K;
-  K.A = s->op->A;
-  K.lda = s->op->lda;
-  K.M = s->op->M;
-  K.N = s->op->N;
-  K.G = s->op->G;  // explicit AHA (src/CGNR.jl:49): every operator apply of the batched loop is ONE product over it
-  K.ldg = s->op->ldg;
-  K.nrhs = s->nrhs;
-  K.half = s->half;
-  K.ngroups = rls_skinny_groups(s->nrhs, s->half);
-  K.splits = s->splits;
+  rls_skinny K = s->ops.desc(s->op, s->nrhs, s->ldv);
   K.X = s->x;
   K.R = s->r;
   K.P = s->p;
   K.V = s->v;
-  K.ldv = s->ldv;
-  K.Ppack = s->Ppack;
-  K.Tpack = s->Tpack;
-  K.Vpart = s->Vpart;
-  K.ldvp = s->op->N;
   K.sc = s->sc;
   return K;
 }
@@ -395,7 +429,7 @@ static rls_gramk cgnr_gramk_desc(const rls_cgnr* s) {
   D.Vx = s->gk_vx;
   D.Xx = s->gk_xx;
   D.dots = s->gk_dots;
-  D.Ppack = s->half ? s->Ppack : nullptr;  // (<= 8 complex columns: the half layout, unless switched off by the tools)
+  D.Ppack = s->ops.half ? s->ops.panel : nullptr;  // (<= 8 complex columns: the half layout, unless switched off by the tools)
   return D;
 }
 
@@ -695,10 +729,7 @@ struct rls_fista {
   // MFMA operand panel, T = A Y and the partial rows of A^H T (skinny.hip)
   int nrhs = 1;
   int64_t ldv = 0;
-  float *Ypack = nullptr, *Tpack = nullptr;
-  void* Vpart = nullptr;
-  int splits = 1;
-  int half = 0;  // operand-panel layout, fixed at creation (rls_skinny_half)
+  shared_operands ops;             // (the panel: the extrapolated points)
   fista_scalars* scb_h = nullptr;  // pinned [nrhs]
   int enq = 0;           // iterations enqueued since init (== the device's count unless the plan stopped early); its parity at
                          // capture is the key of the cached graph (step_graph::mode): the buffer hints belong to it
@@ -724,22 +755,18 @@ struct rls_fista {
   float rho_h = 0.f;  // rho of the last init (the prox threshold rho * lambda is a launch argument of the FGP kernel)
 };
 
-// batched launches: workgroup b = column b.  Vpart non-null: AHA y arrives as `S` partial rows per column and is
-// summed here (fixed order); Yp non-null: the extrapolated point also goes into the operand panel Yp[g][n][j].
+// Batched plans (shared A: rls_fista_create_batched, rls_cg_create_batched): the per-column kernels of FISTA, cg! and ADMM run
+// one workgroup per column (blockIdx.x = column, state matrices N x K with leading dimension ldv, one scalar struct per
+// column); the operator apply in front of them is the pair of skinny matrix-core products.  ops.Vpart non-null: AHA y arrives
+// as partial rows and is summed here; ops.panel non-null: the kernel's next point also goes into the operand panel.
+// The default = the single-column plans.
 template <typename E>
-struct fista_batch {
-  int64_t ldv;
-  const E* Vpart;
-  int S, nrhs_pad;
-  E* Yp;
-  int half;  // operand-panel layout (rls_common.hpp, panel_col)
+struct col_batch {
+  int64_t ldv = 0;
+  operand_view<E> ops;
+  int skip_stride = 0;      // ints between the columns' skip flags (ADMM)
+  int64_t log_stride = 0;   // floats between the columns' ADMM logs
 };
-template <typename E>
-__device__ static inline E fista_parts(const fista_batch<E>& B, int b, int64_t N, int64_t i) {
-  E v = B.Vpart[(int64_t)b * N + i];
-  for (int s = 1; s < B.S; ++s) v = elem<E>::add(v, B.Vpart[((int64_t)s * B.nrhs_pad + b) * N + i]);
-  return v;
-}
 
 // x0 = A^H b is already in place.  x = x_init (zero), xold = 0, res = Inf, y = x   (src/FISTA.jl:110-129)
 template <typename E>
@@ -748,7 +775,7 @@ __global__ __launch_bounds__(UPD_THREADS) void fista_init_kernel(E* __restrict__
                                                                  E* __restrict__ y, int64_t n, fista_scalars* sc,
                                                                  float rho, float theta, float rel_tol, int max_iter,
                                                                  int restart, int reg_kind, int proj_kind,
-                                                                 float lambda, long long slices, fista_batch<E> Bt,
+                                                                 float lambda, long long slices, col_batch<E> Bt,
                                                                  unsigned* clear_words = nullptr, int n_clear = 0) {
   __shared__ double sm[16];
   for (int i = threadIdx.x; i < n_clear; i += UPD_THREADS) clear_words[i] = 0u;  // (cgnr_init_kernel)
@@ -759,13 +786,13 @@ __global__ __launch_bounds__(UPD_THREADS) void fista_init_kernel(E* __restrict__
   res += b * Bt.ldv;
   y += b * Bt.ldv;
   sc += b;
-  const panel_col<E> yp = panel_column<E>(Bt.Yp, n, b, Bt.half);
+  const panel_col<E> yp = Bt.ops.column(n, b);
   double nn = 0.0;
   const float inf = __builtin_huge_valf();
   for (int64_t i = threadIdx.x; i < n; i += UPD_THREADS) {
     E v;
-    if (Bt.Vpart) {  // x0 = A^H b from the partial rows of the skinny product
-      v = fista_parts<E>(Bt, b, n, i);
+    if (Bt.ops.Vpart) {  // x0 = A^H b from the partial rows of the skinny product
+      v = Bt.ops.sum(b, n, i);
       x0[i] = v;
     } else {
       v = x0[i];
@@ -774,7 +801,7 @@ __global__ __launch_bounds__(UPD_THREADS) void fista_init_kernel(E* __restrict__
     b0[i] = elem<E>::zero();
     b1[i] = elem<E>::zero();
     y[i] = elem<E>::zero();
-    if (Bt.Yp) yp.put(i, elem<E>::zero());
+    if (Bt.ops.panel) yp.put(i, elem<E>::zero());
     res[i] = elem<E>::make(inf, 0.f);
   }
   nn = block_sum_n<UPD_THREADS / 64>(nn, sm);
@@ -808,7 +835,7 @@ template <typename E>
 __global__ __launch_bounds__(UPD_THREADS) void fista_update_kernel(E* __restrict__ b0, E* __restrict__ b1,
                                                                    const E* __restrict__ x0, E* __restrict__ res,
                                                                    E* __restrict__ y, int64_t n, fista_scalars* sc,
-                                                                   fista_batch<E> Bt, int phase = 0, E* __restrict__ tv_in = nullptr,
+                                                                   col_batch<E> Bt, int phase = 0, E* __restrict__ tv_in = nullptr,
                                                                    const E* __restrict__ tv_out = nullptr) {
   const int b = blockIdx.x;
   b0 += b * Bt.ldv;
@@ -817,7 +844,7 @@ __global__ __launch_bounds__(UPD_THREADS) void fista_update_kernel(E* __restrict
   res += b * Bt.ldv;
   y += b * Bt.ldv;
   sc += b;
-  const panel_col<E> yp = panel_column<E>(Bt.Yp, n, b, Bt.half);
+  const panel_col<E> yp = Bt.ops.column(n, b);
   if (sc->done) return;  // a retired column keeps its panel entry (src/MultiThreading.jl:60-78)
   __shared__ double sm[16];
   const int it = sc->iteration;
@@ -832,7 +859,7 @@ __global__ __launch_bounds__(UPD_THREADS) void fista_update_kernel(E* __restrict
     __syncthreads();
   } else {
   for (int64_t i = threadIdx.x; i < n; i += UPD_THREADS) {
-    const E ri = elem<E>::sub(Bt.Vpart ? fista_parts<E>(Bt, b, n, i) : res[i], x0[i]);  // res .-= x0      :153
+    const E ri = elem<E>::sub(Bt.ops.Vpart ? Bt.ops.sum(b, n, i) : res[i], x0[i]);  // res .-= x0      :153
     res[i] = ri;
     rn += (double)elem<E>::re(ri) * (double)elem<E>::re(ri) + (double)elem<E>::im(ri) * (double)elem<E>::im(ri);
     E xi = elem<E>::sub(y[i], elem<E>::scale(rho, ri));             // x .-= rho .* res :154
@@ -885,7 +912,7 @@ __global__ __launch_bounds__(UPD_THREADS) void fista_update_kernel(E* __restrict
     for (int64_t i = threadIdx.x; i < n; i += UPD_THREADS) {
       const E yi = elem<E>::add(elem<E>::scale(c1, xold[i]), elem<E>::scale(c2, xnew[i]));
       y[i] = yi;
-      if (Bt.Yp) yp.put(i, yi);
+      if (Bt.ops.panel) yp.put(i, yi);
     }
   }
   if (threadIdx.x == 0) {
@@ -904,7 +931,7 @@ template <typename E, int EPT>
 __global__ __launch_bounds__(UPD_THREADS) void fista_update_reg_kernel(E* __restrict__ b0, E* __restrict__ b1,
                                                                        const E* __restrict__ x0, E* __restrict__ res,
                                                                        E* __restrict__ y, int64_t n, fista_scalars* sc,
-                                                                       fista_batch<E> Bt) {
+                                                                       col_batch<E> Bt) {
   const int b = blockIdx.x;
   b0 += b * Bt.ldv;
   b1 += b * Bt.ldv;
@@ -912,7 +939,7 @@ __global__ __launch_bounds__(UPD_THREADS) void fista_update_reg_kernel(E* __rest
   res += b * Bt.ldv;
   y += b * Bt.ldv;
   sc += b;
-  const panel_col<E> yp = panel_column<E>(Bt.Yp, n, b, Bt.half);
+  const panel_col<E> yp = Bt.ops.column(n, b);
   __shared__ double sm[16];
   const int done0 = sc->done, it = sc->iteration, reg_kind = sc->reg_kind, proj_kind = sc->proj_kind;
   const int restart = sc->restart, max_iter = sc->max_iter;
@@ -925,7 +952,7 @@ __global__ __launch_bounds__(UPD_THREADS) void fista_update_reg_kernel(E* __rest
   for (int e = 0; e < EPT; ++e) {
     const int64_t i = threadIdx.x + (int64_t)e * UPD_THREADS;
     const int64_t ic = i < n ? i : n - 1;
-    raw[e] = Bt.Vpart ? fista_parts<E>(Bt, b, n, ic) : res[ic];
+    raw[e] = Bt.ops.Vpart ? Bt.ops.sum(b, n, ic) : res[ic];
     x0v[e] = x0[ic];
     yv[e] = y[ic];
     xo[e] = xold[ic];
@@ -971,7 +998,7 @@ __global__ __launch_bounds__(UPD_THREADS) void fista_update_reg_kernel(E* __rest
       if (!done) {  // next iteration's Nesterov step, formed out of place in y                         :147-148
         const E yi = elem<E>::add(elem<E>::scale(c1, xo[e]), elem<E>::scale(c2, xn[e]));
         y[i] = yi;
-        if (Bt.Yp) yp.put(i, yi);
+        if (Bt.ops.panel) yp.put(i, yi);
       }
     }
   }
@@ -987,7 +1014,7 @@ __global__ __launch_bounds__(UPD_THREADS) void fista_update_reg_kernel(E* __rest
 
 // launch of the update half of an unfused / batched FISTA iteration: the register form when it applies
 template <typename E>
-static int32_t fista_launch_update(rls_fista* s, unsigned nblocks, const fista_batch<E>& Bt) {
+static int32_t fista_launch_update(rls_fista* s, unsigned nblocks, const col_batch<E>& Bt) {
   rls_operator* op = s->op;
   const int64_t n = op->N;
   int32_t tv_status = 0;
@@ -1069,7 +1096,7 @@ static int32_t fista_enqueue_iteration(rls_fista* s) {
   RLS_TRY(op_normal(op, s->y, s->res, &s->sc->done));
   RLS_TRY(rls_with_elem(op->dtype, [&](auto t) {
     using E = typename decltype(t)::type;
-    return fista_launch_update<E>(s, 1, fista_batch<E>{0, nullptr, 1, 0, nullptr, 0});
+    return fista_launch_update<E>(s, 1, col_batch<E>());
   }));
   return launch_status(op->ctx);
 }
@@ -1106,10 +1133,7 @@ struct rls_cg {
   // skinny matrix-core products (skinny.hip); sc / sc_h hold nrhs structs
   int nrhs = 1;
   int64_t ldv = 0;
-  float *Ppack = nullptr, *Tpack = nullptr;
-  int half = 0;  // operand-panel layout, fixed at creation (rls_skinny_half)
-  void* Vpart = nullptr;
-  int splits = 1;
+  shared_operands ops;
   // resident mode: cg! on (AHA + rho I) IS the CGNR recurrence, so after the start kernel the whole inner solve runs as
   // ONE launch of cgnr_resident_kernel with A in registers (normal.hip)
   resident_slot resident;
@@ -1156,33 +1180,12 @@ struct admm_fuse {
   float rho;
   const int* skip;
 };
-// Batched plans (shared A, rls_cg_create_batched): the per-column kernels below run one workgroup per column
-// (blockIdx.x = column, state matrices N x K with leading dimension ldv, one scalar struct per column); the
-// operator apply in front of them is the pair of skinny matrix-core products, which leaves AHA u as S partial rows
-// per column (summed here in a fixed order) and reads its right operand from the MFMA panel the kernels write.
-// All zero = the single-column plans.
-template <typename E>
-struct col_batch {
-  int64_t ldv = 0;
-  const E* Vpart = nullptr;
-  int S = 1, nrhs_pad = 16;
-  E* panel = nullptr;       // operand panel [group][n][16]: column b -> panel + (b >> 4) * n * 16 + (b & 15), stride 16
-  int half = 0;             // ... or the (8 re | 8 im) layout of at most 8 complex columns (rls_common.hpp, panel_col)
-  int skip_stride = 0;      // ints between the columns' skip flags
-  int64_t log_stride = 0;   // floats between the columns' ADMM logs
-};
-template <typename E>
-__device__ static inline E col_parts(const col_batch<E>& B, int b, int64_t N, int64_t i) {
-  E v = B.Vpart[(int64_t)b * N + i];
-  for (int s = 1; s < B.S; ++s) v = elem<E>::add(v, B.Vpart[((int64_t)s * B.nrhs_pad + b) * N + i]);
-  return v;
-}
+// Batched plans (rls_cg_create_batched): col_batch above.
 // X (N x K) -> operand panel, ahead of the warm-start apply AHA x of every outer iteration
 template <typename E>
-__global__ __launch_bounds__(256) void pack_panel_kernel(const E* __restrict__ X, int64_t ldv, E* __restrict__ panel, int64_t n,
-                                                         int half) {
+__global__ __launch_bounds__(256) void pack_panel_kernel(const E* __restrict__ X, int64_t ldv, operand_view<E> O, int64_t n) {
   const int b = blockIdx.y;
-  const panel_col<E> up = panel_column<E>(panel, n, b, half);
+  const panel_col<E> up = O.column(n, b);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     up.put(i, X[(int64_t)b * ldv + i]);
 }
@@ -1323,7 +1326,7 @@ __global__ __launch_bounds__(UPD_THREADS) void cg_start_kernel(const E* __restri
     if (F.skip) F.skip += (int64_t)bq * B.skip_stride;
     sc += bq;
   }
-  const panel_col<E> up = panel_column<E>(B.panel, n, bq, B.half);
+  const panel_col<E> up = B.ops.column(n, bq);
   if (F.skip && *F.skip) {
     if (threadIdx.x == 0) {
       sc->iteration = 0;
@@ -1334,12 +1337,12 @@ __global__ __launch_bounds__(UPD_THREADS) void cg_start_kernel(const E* __restri
   }
   double rr = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += UPD_THREADS) {
-    const E cv = B.Vpart ? col_parts<E>(B, bq, n, i) : c[i];
+    const E cv = B.ops.Vpart ? B.ops.sum(bq, n, i) : c[i];
     const E ci = elem<E>::add(cv, elem<E>::scale(rho, x[i]));
     const E ri = elem<E>::sub(admm_rhs<E>(F, b, x, i), ci);
     r[i] = ri;
     u[i] = ri;  // first iteration: beta = residual^2 / 1^2 multiplies u == 0
-    if (B.panel) up.put(i, ri);
+    if (B.ops.panel) up.put(i, ri);
     rr += (double)elem<E>::re(ri) * (double)elem<E>::re(ri) + (double)elem<E>::im(ri) * (double)elem<E>::im(ri);
   }
   rr = block_sum(rr, sm);
@@ -1377,10 +1380,10 @@ __global__ __launch_bounds__(UPD_THREADS) void cg_start_bregman_kernel(const E* 
     }
     return;
   }
-  const panel_col<E> up = panel_column<E>(B.panel, n, bq, B.half);
+  const panel_col<E> up = B.ops.column(n, bq);
   double rr = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += UPD_THREADS) {
-    const E cv = col_parts<E>(B, bq, n, i);
+    const E cv = B.ops.sum(bq, n, i);
     const E xi = x[i];
     const E by = elem<E>::sub(elem<E>::add(beta_y[i], y[i]), cv);
     beta_y[i] = by;
@@ -1412,13 +1415,13 @@ __global__ __launch_bounds__(UPD_THREADS) void cg_update_kernel(E* __restrict__ 
     sc += bq;
   }
   if (sc->done) return;
-  const panel_col<E> up = panel_column<E>(B.panel, n, bq, B.half);
+  const panel_col<E> up = B.ops.column(n, bq);
   __shared__ double sm[16];
   const float rho = sc->rho;
   double dre = 0.0, dim_ = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += UPD_THREADS) {
     const E ui = u[i];
-    const E cv = B.Vpart ? col_parts<E>(B, bq, n, i) : c[i];
+    const E cv = B.ops.Vpart ? B.ops.sum(bq, n, i) : c[i];
     const E ci = elem<E>::add(cv, elem<E>::scale(rho, ui));
     c[i] = ci;
     dre += (double)elem<E>::re(ui) * (double)elem<E>::re(ci) + (double)elem<E>::im(ui) * (double)elem<E>::im(ci);
@@ -1447,7 +1450,7 @@ __global__ __launch_bounds__(UPD_THREADS) void cg_update_kernel(E* __restrict__ 
     for (int64_t i = threadIdx.x; i < n; i += UPD_THREADS) {
       const E un = elem<E>::add(r[i], elem<E>::scale(beta, u[i]));
       u[i] = un;
-      if (B.panel) up.put(i, un);
+      if (B.ops.panel) up.put(i, un);
     }
   }
   if (threadIdx.x == 0) {
@@ -1725,31 +1728,11 @@ __global__ void admm_reset_kernel(admm_scalars* sc, int max_iter, float rho, flo
 }
 
 // ---- batched FISTA (shared A, matrix-core products) ----------------------------------------------
-static rls_skinny fista_skinny_desc(const rls_fista* s) {
-  rls_skinny K;
-  K.A = s->op->A;
-  K.lda = s->op->lda;
-  K.M = s->op->M;
-  K.N = s->op->N;
-  K.G = s->op->G;  // explicit AHA (src/CGNR.jl:49): every operator apply of the batched loop is ONE product over it
-  K.ldg = s->op->ldg;
-  K.nrhs = s->nrhs;
-  K.half = s->half;
-  K.ngroups = rls_skinny_groups(s->nrhs, s->half);
-  K.splits = s->splits;
-  K.X = K.R = K.P = K.V = nullptr;
-  K.ldv = s->ldv;
-  K.Ppack = s->Ypack;  // the T kernel's right operand: the extrapolated points
-  K.Tpack = s->Tpack;
-  K.Vpart = s->Vpart;
-  K.ldvp = s->op->N;
-  K.sc = nullptr;
-  return K;
-}
+static rls_skinny fista_skinny_desc(const rls_fista* s) { return s->ops.desc(s->op, s->nrhs, s->ldv); }
 
 template <typename E>
-static fista_batch<E> fista_batch_desc(const rls_fista* s) {
-  return fista_batch<E>{s->ldv, (const E*)s->Vpart, s->splits, rls_skinny_pad(s->nrhs, s->half), (E*)s->Ypack, s->half};
+static col_batch<E> fista_batch_desc(const rls_fista* s) {
+  return col_batch<E>{s->ldv, s->ops.view<E>(s->nrhs)};
 }
 
 static int32_t fista_enqueue_batched(rls_fista* s) {
@@ -1883,28 +1866,6 @@ static int32_t cg_solve_impl(rls_cg* s, void* x, const void* b, float rho, int32
 // {T = A U, V = A^H T, per-column CG update}, the FGP launch with one workgroup per column for a TV term, and the
 // per-column z / u / residual-norm / `done` kernel.  Columns retire independently (per-column device flags), exactly
 // as K independent solves do (src/MultiThreading.jl:60-78).
-static rls_skinny cg_skinny_desc(const rls_cg* s) {
-  rls_skinny K;
-  K.A = s->op->A;
-  K.lda = s->op->lda;
-  K.M = s->op->M;
-  K.N = s->op->N;
-  K.G = s->op->G;  // explicit AHA (src/CGNR.jl:49): every operator apply of the batched loop is ONE product over it
-  K.ldg = s->op->ldg;
-  K.nrhs = s->nrhs;
-  K.half = s->half;
-  K.ngroups = rls_skinny_groups(s->nrhs, s->half);
-  K.splits = s->splits;
-  K.X = K.R = K.P = K.V = nullptr;
-  K.ldv = s->ldv;
-  K.Ppack = s->Ppack;
-  K.Tpack = s->Tpack;
-  K.Vpart = s->Vpart;
-  K.ldvp = s->op->N;
-  K.sc = nullptr;
-  return K;
-}
-
 template <typename E>
 static int32_t admm_step_batched_typed(rls_admm* a, int32_t n_outer) {
   rls_cg* cg = a->cg;
@@ -1913,24 +1874,14 @@ static int32_t admm_step_batched_typed(rls_admm* a, int32_t n_outer) {
   const int32_t dtype = cg->op->dtype;
   const int64_t n = cg->op->N;
   const unsigned K = (unsigned)a->nrhs;
-  const rls_skinny SK = cg_skinny_desc(cg);
-  col_batch<E> B;
-  B.ldv = cg->ldv;
-  B.Vpart = (const E*)cg->Vpart;
-  B.S = cg->splits;
-  B.nrhs_pad = rls_skinny_pad(a->nrhs, cg->half);
-  B.panel = (E*)cg->Ppack;
-  B.half = cg->half;
-  B.skip_stride = (int)(sizeof(admm_scalars) / sizeof(int));
-  B.log_stride = (int64_t)ADMM_REC * a->log_cap;
-  col_batch<E> Bz = B;  // the z / u kernel reads no partial rows and writes no panel
-  Bz.Vpart = nullptr;
-  Bz.panel = nullptr;
+  const rls_skinny SK = cg->ops.desc(cg->op, cg->nrhs, cg->ldv);
+  const col_batch<E> B{cg->ldv, cg->ops.view<E>(a->nrhs), (int)(sizeof(admm_scalars) / sizeof(int)), (int64_t)ADMM_REC * a->log_cap};
+  const col_batch<E> Bz{B.ldv, operand_view<E>(), B.skip_stride, B.log_stride};  // the z / u kernel: no partial rows, no panel
   for (int k = 0; k < n_outer && a->enq < P.iterations; ++k, ++a->enq) {
     E* zcur = (E*)((a->enq & 1) ? P.z1 : P.z0);
     E* znew = (E*)((a->enq & 1) ? P.z0 : P.z1);
     hipLaunchKernelGGL(pack_panel_kernel<E>, dim3((unsigned)((n + 255) / 256 < 64 ? (n + 255) / 256 : 64), K), dim3(256), 0,
-                       ctx->stream, (const E*)P.x, cg->ldv, (E*)cg->Ppack, n, cg->half);
+                       ctx->stream, (const E*)P.x, cg->ldv, B.ops, n);
     RLS_TRY(rls_skinny_launch(ctx, dtype, SK, 1 | 2));  // AHA x of every column  (:244, warm start)
     admm_fuse<E> F;
     F.beta_y = (const E*)P.beta_y;
@@ -1991,7 +1942,7 @@ static bool cgnr_single(rls_cgnr* s) { return s->nrhs == 1; }
 static rls_operator* fista_op(rls_fista* s) { return s->op; }
 static bool fista_single(rls_fista* s) { return s->nrhs == 1; }
 static rls_operator* admm_op(rls_admm* a) { return a->cg->op; }
-static bool admm_single(rls_admm* a) { return a->nrhs == 1 && !a->cg->Vpart; }
+static bool admm_single(rls_admm* a) { return a->nrhs == 1 && !a->cg->ops.allocated(); }
 
 template <typename E>
 static void admm_local_start(rls_admm* a, const admm_fuse_v& F) {
@@ -2122,8 +2073,7 @@ static int32_t cgnr_create_impl(rls_operator* op, int32_t nrhs, void* x, void* r
   RLS_HIP(ctx, rls_enter(ctx));
   // the columns share solver.AHA (src/MultiThreading.jl:30-48): an explicit Gram matrix when the operator has one -- the
   // reference constructors' default for a dense matrix, src/CGNR.jl:49 --, otherwise the two products over A
-  const bool skinny = nrhs > 1 && ctx->tune.batched_mfma && rls_skinny_ok(op->dtype, op->M, op->N, op->A, op->lda) &&
-                      (!op->G || rls_skinny_ok(op->dtype, op->N, op->N, op->G, op->ldg));
+  const bool skinny = nrhs > 1 && ctx->tune.batched_mfma && shared_operands::supported(op);
   if (nrhs > 1 && !skinny)
     return rls_fail(ctx, RLS_E_UNSUPPORTED, "batched CGNR runs on the matrix cores: A (and AHA, when explicit) with M, N multiples "
                                             "of 16 and 16-byte aligned columns (other shapes: one plan per column)");
@@ -2188,13 +2138,8 @@ static int32_t cgnr_create_impl(rls_operator* op, int32_t nrhs, void* x, void* r
     }
   }
   if (!mem.error() && skinny) {
-    size_t pb, tb, vb;
-    rls_skinny_sizes(op->ctx, op->dtype, op->M, op->N, nrhs, &pb, &tb, &vb, &s->splits);
-    s->half = rls_skinny_half(op->ctx, op->dtype, nrhs);
-    mem.dev(&s->Ppack, pb, true);  // the padding columns of the last group stay zero
-    mem.dev(&s->Tpack, tb, false);
-    mem.dev(&s->Vpart, vb, false);
-    if (!mem.error() && op->G && s->half && rls_gramk_resident_ok(ctx, op->dtype, op->N, nrhs, op->G, op->ldg)) {
+    s->ops.alloc(mem, op, nrhs);
+    if (!mem.error() && op->G && s->ops.half && rls_gramk_resident_ok(ctx, op->dtype, op->N, nrhs, op->G, op->ldg)) {
       size_t xb, xxb, db;
       rls_gramk_sizes(op->N, &xb, &xxb, &db);
       s->resident.alloc(mem, ctx, op);
@@ -3324,7 +3269,7 @@ static int32_t fista_init_finish(rls_fista* s, float rho, float theta, float rel
     using E = typename decltype(t)::type;
     hipLaunchKernelGGL(fista_init_kernel<E>, dim3(1), dim3(UPD_THREADS), 0, ctx->stream, (E*)s->buf[0], (E*)s->buf[1], (E*)s->x0,
                        (E*)s->res, (E*)s->y, op->N, s->sc, rho, theta, rel_tol, iterations, restart_gradient, s->reg_kind,
-                       s->proj_kind, s->lambda, (long long)s->l21_slices, fista_batch<E>{0, nullptr, 1, 0, nullptr, 0},
+                       s->proj_kind, s->lambda, (long long)s->l21_slices, col_batch<E>(),
                        (unsigned*)s->resident.sync,
                        s->resident.sync ? (int)(rls_resident_sync_clear_bytes() / sizeof(unsigned)) : 0);
   });
@@ -3379,7 +3324,7 @@ int32_t rls_fista_step_local_b(rls_fista* s) {
   RLS_HIP(ctx, rls_enter(ctx));
   RLS_TRY(rls_with_elem(op->dtype, [&](auto t) {
     using E = typename decltype(t)::type;
-    return fista_launch_update<E>(s, 1, fista_batch<E>{0, nullptr, 1, 0, nullptr, 0});
+    return fista_launch_update<E>(s, 1, col_batch<E>());
   }));
   return launch_status(ctx);
 }
@@ -3392,8 +3337,7 @@ int32_t rls_fista_create_batched(rls_operator* op, int32_t nrhs, void* x, void* 
   rls_ctx* ctx = op->ctx;
   if (!x || !x0 || !xold || !res || !out || nrhs < 1 || ldv < op->N)
     return rls_fail(ctx, RLS_E_INVALID, "fista_create_batched: bad argument");
-  if (!op->A || !ctx->tune.batched_mfma || !rls_skinny_ok(op->dtype, op->M, op->N, op->A, op->lda) ||
-      (op->G && !rls_skinny_ok(op->dtype, op->N, op->N, op->G, op->ldg)))
+  if (!ctx->tune.batched_mfma || !shared_operands::supported(op))
     return rls_fail(ctx, RLS_E_UNSUPPORTED, "batched FISTA needs A (and AHA, when explicit) with 16-aligned M, N (matrix-core path)");
   RLS_HIP(ctx, rls_enter(ctx));
   *out = nullptr;
@@ -3410,18 +3354,13 @@ int32_t rls_fista_create_batched(rls_operator* op, int32_t nrhs, void* x, void* 
   s->res = res;
   s->nrhs = nrhs;
   s->ldv = ldv;
-  size_t pb, tb, vb;
-  rls_skinny_sizes(op->ctx, op->dtype, op->M, op->N, nrhs, &pb, &tb, &vb, &s->splits);
-  s->half = rls_skinny_half(op->ctx, op->dtype, nrhs);
   mem.dev(&s->y, (size_t)ldv * nrhs * rls_elem_size(op->dtype), false);
-  mem.dev(&s->Ypack, pb, true);  // the padding columns of the last group stay zero
-  mem.dev(&s->Tpack, tb, false);
-  mem.dev(&s->Vpart, vb, false);
+  s->ops.alloc(mem, op, nrhs);
   mem.dev(&s->sc, sizeof(fista_scalars) * nrhs, true);
   mem.pinned(&s->scb_h, sizeof(fista_scalars) * nrhs, false);
   mem.pinned(&s->sc_h, sizeof(fista_scalars), false);
   const bool vec16 = ldv % 2 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(xold) | reinterpret_cast<uintptr_t>(res)) & 15) == 0;
-  if (!mem.error() && op->G && s->half && vec16 && rls_fgramk_resident_ok(ctx, op->dtype, op->N, nrhs, op->G, op->ldg)) {
+  if (!mem.error() && op->G && s->ops.half && vec16 && rls_fgramk_resident_ok(ctx, op->dtype, op->N, nrhs, op->G, op->ldg)) {
     size_t yxb, xxb, db;
     rls_fgramk_sizes(op->N, &yxb, &xxb, &db);
     s->resident.alloc(mem, ctx, op);
@@ -3443,7 +3382,7 @@ int32_t rls_fista_init_batched(rls_fista* s, const void* B, int64_t ldb, float r
   if (!s) return RLS_E_INVALID;
   rls_operator* op = s->op;
   rls_ctx* ctx = op->ctx;
-  if (s->nrhs < 2 && !s->Ypack) return rls_fail(ctx, RLS_E_STATE, "fista_init_batched on a single-column plan");
+  if (s->nrhs < 2 && !s->ops.allocated()) return rls_fail(ctx, RLS_E_STATE, "fista_init_batched on a single-column plan");
   if (!B || ldb < op->M) return rls_fail(ctx, RLS_E_INVALID, "fista_init_batched: bad argument");
   RLS_HIP(ctx, rls_enter(ctx));
   RLS_TRY(rls_skinny_atb(ctx, op->dtype, fista_skinny_desc(s), B, ldb));  // partial rows of A^H B   (src/FISTA.jl:114)
@@ -3527,7 +3466,7 @@ static rls_fgramk fista_gramk_desc(const rls_fista* s) {
   D.Yx = s->fk_yx;
   D.Xx = s->fk_xx;
   D.dots = s->fk_dots;
-  D.Ypack = s->Ypack;
+  D.Ypack = s->ops.panel;
   return D;
 }
 
@@ -3776,8 +3715,7 @@ int32_t rls_cg_create_batched(rls_operator* op, int32_t nrhs, void* U, void* R, 
   if (!op) return RLS_E_INVALID;
   rls_ctx* ctx = op->ctx;
   if (!U || !R || !Cm || !out || nrhs < 1 || ldv < op->N) return rls_fail(ctx, RLS_E_INVALID, "cg_create_batched: bad argument");
-  if (!op->A || !rls_skinny_ok(op->dtype, op->M, op->N, op->A, op->lda) ||
-      (op->G && !rls_skinny_ok(op->dtype, op->N, op->N, op->G, op->ldg)))
+  if (!shared_operands::supported(op))
     return rls_fail(ctx, RLS_E_UNSUPPORTED, "cg_create_batched: needs A (and AHA, when explicit) with M, N multiples of 16");
   RLS_HIP(ctx, rls_enter(ctx));
   *out = nullptr;
@@ -3793,12 +3731,7 @@ int32_t rls_cg_create_batched(rls_operator* op, int32_t nrhs, void* U, void* R, 
   s->c = Cm;
   s->nrhs = nrhs;
   s->ldv = ldv;
-  size_t pb, tb, vb;
-  rls_skinny_sizes(op->ctx, op->dtype, op->M, op->N, nrhs, &pb, &tb, &vb, &s->splits);
-  s->half = rls_skinny_half(op->ctx, op->dtype, nrhs);
-  mem.dev(&s->Ppack, pb, true);  // the padding columns of the last group stay zero
-  mem.dev(&s->Tpack, tb, false);
-  mem.dev(&s->Vpart, vb, false);
+  s->ops.alloc(mem, op, nrhs);
   alloc_scalars(mem, &s->sc, &s->sc_h, nrhs);
   if (const int e = mem.error()) {
     rls_cg_destroy(s);
@@ -4028,35 +3961,13 @@ struct rls_pgm_batched {
   int device = 0;
   int kind = 0;  // 0 = OptISTA, 1 = POGM
   rls_pgmb D;
-  float *panel = nullptr, *Tpack = nullptr;
-  void* Vpart = nullptr;
-  int splits = 1, half = 0;
+  shared_operands ops;  // (the panel: the gradient points)
   pgmb_scalars *sc = nullptr, *sc_h = nullptr;  // [nrhs], pinned mirror
   step_graph graph;
   bool initialised = false;
 };
 
-static rls_skinny pgmb_skinny_desc(const rls_pgm_batched* s) {
-  rls_skinny K;
-  K.A = s->op->A;
-  K.lda = s->op->lda;
-  K.M = s->op->M;
-  K.N = s->op->N;
-  K.G = s->op->G;
-  K.ldg = s->op->ldg;
-  K.nrhs = s->D.nrhs;
-  K.half = s->half;
-  K.ngroups = rls_skinny_groups(s->D.nrhs, s->half);
-  K.splits = s->splits;
-  K.X = K.R = K.P = K.V = nullptr;
-  K.ldv = s->D.ldv;
-  K.Ppack = s->panel;  // the T kernel's right operand: the gradient points
-  K.Tpack = s->Tpack;
-  K.Vpart = s->Vpart;
-  K.ldvp = s->op->N;
-  K.sc = nullptr;
-  return K;
-}
+static rls_skinny pgmb_skinny_desc(const rls_pgm_batched* s) { return s->ops.desc(s->op, s->D.nrhs, s->D.ldv); }
 
 int32_t rls_pgm_create_batched(rls_operator* op, int32_t kind, int32_t nrhs, void* v0, void* v1, void* z, void* w, void* old,
                                void* res, void* x0, int64_t ldv, rls_pgm_batched** out) {
@@ -4065,8 +3976,7 @@ int32_t rls_pgm_create_batched(rls_operator* op, int32_t kind, int32_t nrhs, voi
   if ((kind != 0 && kind != 1) || !v0 || !v1 || !z || !old || !res || !x0 || !out || nrhs < 1 || ldv < op->N)
     return rls_fail(ctx, RLS_E_INVALID, "pgm_create_batched: bad argument");
   *out = nullptr;
-  if (!op->A || !ctx->tune.batched_mfma || !rls_skinny_ok(op->dtype, op->M, op->N, op->A, op->lda) ||
-      (op->G && !rls_skinny_ok(op->dtype, op->N, op->N, op->G, op->ldg)))
+  if (!ctx->tune.batched_mfma || !shared_operands::supported(op))
     return rls_fail(ctx, RLS_E_UNSUPPORTED, "batched OptISTA / POGM needs A (and AHA, when explicit) with 16-aligned M, N (matrix-core path)");
   RLS_HIP(ctx, rls_enter(ctx));
   rls_alloc_scope alloc_scope(ctx);
@@ -4076,12 +3986,7 @@ int32_t rls_pgm_create_batched(rls_operator* op, int32_t kind, int32_t nrhs, voi
   s->actx_id = ctx->id;
   s->device = ctx->device;
   s->kind = kind;
-  size_t pb, tb, vb;
-  rls_skinny_sizes(ctx, op->dtype, op->M, op->N, nrhs, &pb, &tb, &vb, &s->splits);
-  s->half = rls_skinny_half(ctx, op->dtype, nrhs);
-  s->mem.dev(&s->panel, pb, true);  // the padding columns of the last group stay zero
-  s->mem.dev(&s->Tpack, tb, false);
-  s->mem.dev(&s->Vpart, vb, false);
+  s->ops.alloc(s->mem, op, nrhs);
   s->mem.dev(&s->sc, sizeof(pgmb_scalars) * nrhs, true);
   s->mem.pinned(&s->sc_h, sizeof(pgmb_scalars) * nrhs, false);
   if (const int e = s->mem.error()) {
@@ -4102,11 +4007,7 @@ int32_t rls_pgm_create_batched(rls_operator* op, int32_t kind, int32_t nrhs, voi
   D.o0 = old;
   D.res = res;
   D.x0 = x0;
-  D.Vpart = s->Vpart;
-  D.S = s->splits;
-  D.nrhs_pad = rls_skinny_pad(nrhs, s->half);
-  D.panel = s->panel;
-  D.half = s->half;
+  D.ops = s->ops.erased(nrhs);
   D.sc = s->sc;
   D.table = nullptr;
   D.reg_kind = RLS_REG_L1;
@@ -4210,7 +4111,7 @@ int32_t rls_cg_path(rls_cg* s, int32_t* out) {
   if (!s || !out) return RLS_E_INVALID;
   const rls_ctx* ctx = s->op->ctx;
   const bool res = s->resident.usable(ctx);
-  if (s->nrhs > 1 || s->Vpart) *out = 3;
+  if (s->nrhs > 1 || s->ops.allocated()) *out = 3;
   else if (cg_use_gram_pipeline(s)) *out = (res && s->gram_resident) ? 5 : 2;
   else if (cg_use_pipeline(s)) *out = res ? 4 : 1;
   else *out = 0;
@@ -4367,7 +4268,7 @@ int32_t rls_admm_set_bregman(rls_admm* a, int32_t iterations_inner, void* Y, int
   if (!a) return RLS_E_INVALID;
   rls_ctx* ctx = a->cg->op->ctx;
   if (!a->ready || a->enq != 0) return rls_fail(ctx, RLS_E_STATE, "admm_set_bregman: call it right after admm_init");
-  if (!a->cg->Vpart) return rls_fail(ctx, RLS_E_UNSUPPORTED, "admm_set_bregman: batched plans only (rls_cg_create_batched)");
+  if (!a->cg->ops.allocated()) return rls_fail(ctx, RLS_E_UNSUPPORTED, "admm_set_bregman: batched plans only (rls_cg_create_batched)");
   if (a->P.reg_kind == RLS_REG_TV) return rls_fail(ctx, RLS_E_UNSUPPORTED, "admm_set_bregman: no TV term in Bregman mode");
   if (iterations_inner < 1 || !Y || ldy < a->cg->op->N) return rls_fail(ctx, RLS_E_INVALID, "admm_set_bregman: bad argument");
   a->breg_inner = iterations_inner;
@@ -4386,7 +4287,7 @@ int32_t rls_admm_step(rls_admm* a, int32_t n_outer) {
   const rls_admm_params& P = a->P;
   const int32_t dtype = cg->op->dtype;
   const int64_t n = cg->op->N;
-  if (a->nrhs > 1 || cg->Vpart) return admm_step_batched(a, n_outer);
+  if (a->nrhs > 1 || cg->ops.allocated()) return admm_step_batched(a, n_outer);
   a->requested = (int)std::min<long long>((long long)a->requested + n_outer, (long long)P.iterations);
   for (int k = 0; k < n_outer && a->enq < P.iterations; ++k, ++a->enq) {
     void* zcur = (a->enq & 1) ? P.z1 : P.z0;

@@ -428,3 +428,60 @@ def test_refused_shape_falls_back_to_per_column_plans(rls, ctx):
         O.solve(ref, B[:, j].astype(np.complex128))
         parity_check(f"skinny_refused_{M}x{N}_col{j}", xs[j].to_host(), ref.x,
                      lambda: O.solve(O.CGNR(A, reg=O.L2Regularization(1e-3), iterations=12, relTol=0.0), np.ascontiguousarray(B[:, j])))
+
+
+# ---- 10. every shared-A plan sums forced row splits -----------------------------------------------------------------------------
+# The per-column kernels of all four batched plans (CGNR; FISTA; cg! under ADMM and SplitBregman; OptISTA / POGM) take AHA u as S
+# partial rows per column and add them in one fixed order; the loop of that sum runs only when S > 1, which no shape this small
+# reaches on its own.  272 x 32 with S = 3 as in test_v_kernel_row_splits.  K = 3: complex the (8 re | 8 im) half layout (rows 8
+# columns apart), real one full group; K = 17: two groups (rows 32 columns apart), the second all padding but one column.
+# Gaussian A (condition number about 2), b = A x_true: on the CPU the Float32 oracle of every case below is within 6e-7 of the
+# float64 oracle, so the 1e-5 gate holds on its own and the Float32 fallback is not what a case passes by.
+SPLIT_FAMILIES = {
+    "CGNR": ("CGNR", "CgnrBatchedState", lambda R, lam, rho: dict(reg=R.L2Regularization(1e-2), iterations=5, relTol=0.0)),
+    "FISTA": ("FISTA", "FistaBatchedState", lambda R, lam, rho: dict(reg=R.L1Regularization(lam), rho=rho, iterations=5, relTol=0.0)),
+    "ADMM": ("ADMM", "AdmmBatchedState", lambda R, lam, rho: dict(reg=R.L1Regularization(0.05), rho=0.3, iterations=3, iterationsCG=4,
+                                                                  tolInner=1e-6, absTol=0.0, relTol=0.0)),
+    "SplitBregman": ("SplitBregman", "SplitBregmanBatchedState",
+                     lambda R, lam, rho: dict(reg=R.L1Regularization(0.05), rho=0.3, iterations=2, iterationsInner=2, iterationsCG=4,
+                                              tolInner=1e-6, absTol=0.0, relTol=0.0)),
+    "OptISTA": ("OptISTA", "PgmBatchedState", lambda R, lam, rho: dict(reg=R.L1Regularization(lam), rho=rho, iterations=5, relTol=0.0)),
+    "POGM": ("POGM", "PgmBatchedState", lambda R, lam, rho: dict(reg=R.L1Regularization(lam), rho=rho, iterations=5, relTol=0.0)),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def split_case(family, dtname, K):
+    """the problem, the solver's keywords (as a function of the module the regulariser comes from) and per column the float64 and
+    the working-precision oracle solutions: computed once per case, never written to"""
+    dt = np.dtype(dtname)
+    A, _, B = O.make_problem(272, 32, dt, 71, n_rhs=K)
+    B = np.asfortranarray(B)
+    A64 = A.astype(hi(dt))
+    lam = 0.02 * float(np.abs(A64.conj().T @ B[:, 0].astype(hi(dt))).max())
+    rho = float(0.9 / np.linalg.norm(A64, 2) ** 2)
+    cls, _, kw = SPLIT_FAMILIES[family]
+    x64 = [np.array(O.solve(getattr(O, cls)(A64, **kw(O, lam, rho)), B[:, j].astype(hi(dt)))) for j in range(K)]
+    x32 = [np.array(O.solve(getattr(O, cls)(A, **kw(O, lam, rho)), np.ascontiguousarray(B[:, j]))) for j in range(K)]
+    for a in [A, B] + x64 + x32:
+        a.setflags(write=False)
+    return A, B, (lambda R: kw(R, lam, rho)), x64, x32
+
+
+@pytest.mark.parametrize("K", [3, 17])
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("family", list(SPLIT_FAMILIES))
+def test_every_plan_sums_forced_row_splits(rls, ctx, family, dt, K):
+    A, B, kw, x64, x32 = split_case(family, np.dtype(dt).name, K)
+    cls, state, _ = SPLIT_FAMILIES[family]
+    with tuned(ctx, skinny_v_splits=3):  # read when the plan is created
+        S = rls.createLinearSolver(getattr(rls, cls), rls.DeviceMatrix.from_host(A, ctx), **kw(rls))
+        xs = rls.solve_(S, rls.DeviceMatrix.from_host(B, ctx), scheduler=rls.BatchedState)
+        assert type(S.state).__name__ == state, "the shape must take the shared-A plan"
+        got = [x.to_host() for x in xs]
+    tag = f"splits_{family}_{name(dt, 272, 32, K)}_S3"
+    errs = [rel(got[j], x64[j]) for j in range(K)]
+    worst = int(np.argmax(errs))
+    print(f"[skinny] {tag}: device {errs[worst]:.3e}  oracle-f32 {rel(x32[worst], x64[worst]):.3e}  (column {worst})")
+    for j in range(K):
+        parity_check(f"skinny_{tag}_col{j}", got[j], x64[j], x32[j], record=(j == worst))
