@@ -211,6 +211,28 @@ int32_t rls_prox_tv_fgp(rls_ctx* ctx, int32_t dtype, int32_t ndims, const int64_
  * with 1 / 2 / 4 / 8 pixels per thread.  Read-only: the launcher's own selector (csrc/tv.hip, fgp_variant).  < 0: RLS_E_*. */
 int32_t rls_tv_variant(rls_ctx* ctx, int32_t dtype, int32_t ndims, const int64_t* shape, int32_t ntv, const int32_t* dims);
 
+/* WaveletOp: orthogonal periodic wavelet transform of a signal or a column-major image.
+ * Real filter h of even length L, g[k] = (-1)^k h[L-1-k]; one analysis level on a line s of even length m gives [a | d] with
+ *   a[i] = sum_k h[k] s[(2i + k) mod m],  d[i] = sum_k g[k] s[(2i + k) mod m],  i = 0 .. m/2 - 1   (m < L: the taps wrap again);
+ * level j acts on the leading (n1 >> j) x (n2 >> j) block, along dimension 1 for every column, then along dimension 2 for every row
+ * (pyramid layout, approximation first).  The operator is orthogonal: adjoint = inverse.  Complex data: real and imaginary part alike.
+ *   rls_wavelet_create   dtype RLS_F32 / C32 / F64 / C64; shape[ndims]: extents of 1 are dropped, one or two may remain; levels < 0:
+ *                        the largest J with 2^J dividing every transformed extent.  RLS_E_INVALID: more than two extents, an extent
+ *                        not divisible by 2^levels, an unknown filter.  Owns one scratch image (nothing allocates per call).
+ *   rls_wavelet_apply    y = W x (adjoint 0) or y = W^T x (adjoint 1); y may be x (any other overlap is undefined).
+ *   rls_prox_wavelet_l1  x <- W^T soft(W x, lambda), the exact prox of lambda ||W x||_1, the soft threshold as rls_prox_l1 / _d has it.
+ * Images whose two copies fit one workgroup's LDS (2 N elements <= 159.5 KiB) run every level -- and for the prox the threshold and the
+ * way back -- in ONE single-workgroup launch; larger ones take one launch per level and dimension.  rls_tune_set("wavelet_fused", 0)
+ * forces the latter.  Both paths give the same bits.  Asynchronous on the context's stream. */
+typedef struct rls_wavelet rls_wavelet;
+enum { RLS_WT_HAAR = 0, RLS_WT_DB2 = 1 };
+int32_t rls_wavelet_create(rls_ctx* ctx, int32_t dtype, int32_t ndims, const int64_t* shape, int32_t filter_kind, int32_t levels,
+                           rls_wavelet** out);
+int32_t rls_wavelet_destroy(rls_wavelet* w);
+int32_t rls_wavelet_levels(rls_wavelet* w, int32_t* out);
+int32_t rls_wavelet_apply(rls_wavelet* w, int32_t adjoint, const void* x, void* y);
+int32_t rls_prox_wavelet_l1(rls_wavelet* w, void* x, double lambda);
+
 /* ---------------------------------------------------------------------------------------------
  * operator handle: the backend's operator type for A (SURVEY 3.1 "two operator modes").
  * A' * A on it yields the lazy normal operator (matrix-free, two GEMVs) unless a Gram matrix is set.
@@ -504,7 +526,7 @@ int32_t rls_cgnr_path(rls_cgnr* s, int32_t* out);
  * reg_kind selects the proximal map applied with rho*lambda (src/FISTA.jl:164); proj_kind the
  * projection applied every iteration (:166-168).
  * ------------------------------------------------------------------------------------------- */
-enum { RLS_REG_NONE = 0, RLS_REG_L1 = 1, RLS_REG_L2 = 2, RLS_REG_L21 = 3, RLS_REG_TV = 4 };
+enum { RLS_REG_NONE = 0, RLS_REG_L1 = 1, RLS_REG_L2 = 2, RLS_REG_L21 = 3, RLS_REG_TV = 4, RLS_REG_WAVELET = 5 };
 enum { RLS_PROJ_NONE = 0, RLS_PROJ_REAL = 1, RLS_PROJ_POSITIVE = 2 };
 
 typedef struct rls_fista_status {
@@ -548,6 +570,12 @@ int32_t rls_fista_set_reg(rls_fista* s, int32_t reg_kind, float lambda, int64_t 
  * launches behind their all-reduce.  proj_kind: the Positive / Real projection applied after the prox (:166-168). */
 int32_t rls_fista_set_reg_tv(rls_fista* s, float lambda, int32_t ndims, const int64_t* shape, int32_t ntv, const int32_t* dims,
                              int32_t iterations_tv, int32_t proj_kind);
+/* prox!(TransformedRegularization(L1Regularization(lambda), WaveletOp)) inside the plan: rls_prox_wavelet_l1's single-workgroup
+ * launch (threshold rho * lambda) between the two halves of the update, as the FGP launch of rls_fista_set_reg_tv.  `w` must be of the
+ * plan's context, element type and N, and outlive the plan's use of it.  RLS_E_UNSUPPORTED on a batched plan, or when the image does
+ * not take the single-workgroup kernel (too large for the LDS, or "wavelet_fused" = 0): the host then drives FISTA from the
+ * primitives.  rls_fista_set_reg with RLS_REG_WAVELET is RLS_E_INVALID: this is the way in. */
+int32_t rls_fista_set_reg_wavelet(rls_fista* s, rls_wavelet* w, float lambda, int32_t proj_kind);
 int32_t rls_fista_init(rls_fista* s, const void* b, float rho, float theta, float rel_tol, int32_t iterations,
                        int32_t restart_gradient);
 /* optional warm start x0 != 0 (init!(solver, b; x0), src/FISTA.jl:110,120): call right after init.  x_init: n = N

@@ -18,7 +18,7 @@ from .regularization import (AbstractParameterizedRegularization, AbstractProjec
                              AbstractNestedRegularization, AbstractScaledRegularization, AutoScaledRegularization,
                              ClampedScalingTransform, FixedParameterRegularization, FixedScaledRegularization,
                              IdentityTransform, MaskedRegularization, MinMaxTransform, PlugAndPlayRegularization,
-                             PnPRegularization, ProjectionRegularization, TransformedRegularization, ZTransform,
+                             PnPRegularization, ProjectionRegularization, TransformedRegularization, WaveletOp, ZTransform,
                              findfirst, findsink, findsinks, is_projection, sink, sinktype)
 from .solvers import (ADMM, CGNR, AbstractDirectSolver, DirectBatchedState, DirectSolver, DirectSolverState, PseudoInverse, PseudoInverseBatchedState, PseudoInverseState, DiagonalPreconditioner, FISTA, POGM, Kaczmarz, KaczmarzState, OptISTA, SplitBregman, AbstractKrylovSolver,
                       AbstractPrimalDualSolver, AbstractProximalGradientSolver, AbstractRowActionSolver,

@@ -16,6 +16,8 @@ F32, C32 = 0, 1
 F64, C64 = 2, 3   # the *_d entry points only: the L1 protocol with double scalars and the double-precision CGNR / FISTA plans
 OP_N, OP_T, OP_C = 0, 1, 2
 REG_NONE, REG_L1, REG_L2, REG_L21, REG_TV = 0, 1, 2, 3, 4
+REG_WAVELET = 5   # rls_fista_set_reg_wavelet only
+WT_HAAR, WT_DB2 = 0, 1
 PROJ_NONE, PROJ_REAL, PROJ_POSITIVE = 0, 1, 2
 
 
@@ -155,6 +157,13 @@ PROTOTYPES = {
     "rls_prox_tv_workspace_bytes": (_sz, [_i32, _i32, _pi64, _i32, _pi32]),
     "rls_prox_tv_fgp": (_i32, [_vp, _i32, _i32, _pi64, _i32, _pi32, _vp, _f, _i32, _vp, _sz]),
     "rls_tv_variant": (_i32, [_vp, _i32, _i32, _pi64, _i32, _pi32]),
+    # ---- WaveletOp and the prox of lambda ||W x||_1 (csrc/wavelet.hip) ----
+    "rls_wavelet_create": (_i32, [_vp, _i32, _i32, _pi64, _i32, _i32, _pvp]),
+    "rls_wavelet_destroy": (_i32, [_vp]),
+    "rls_wavelet_levels": (_i32, [_vp, _pi32]),
+    "rls_wavelet_apply": (_i32, [_vp, _i32, _vp, _vp]),
+    "rls_prox_wavelet_l1": (_i32, [_vp, _vp, _d]),
+    "rls_fista_set_reg_wavelet": (_i32, [_vp, _vp, _f, _i32]),
     "rls_operator_create": (_i32, [_vp, _i32, _i64, _i64, _vp, _i64, _pvp]),
     "rls_operator_set_gram": (_i32, [_vp, _vp, _i64]),
     "rls_operator_destroy": (_i32, [_vp]),

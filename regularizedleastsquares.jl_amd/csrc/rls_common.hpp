@@ -63,6 +63,8 @@ struct rls_tuning {
                                // solver bindings then run their host loop (a launch per sweep and per prox): measurement / escape hatch
   int pinv_block = -1;         // PseudoInverse, blocked sweeps ahead of the plain ones: -1 automatic, 0 plain only, 16 / 32 that width
   int pinv_block_tol = 0, pinv_block_cap = 0;  // measurement: tau_b = 10^-v and the cap of blocked sweeps (0: the constants)
+  int wavelet_fused = 1;       // wavelet.hip: 1 = images that fit one workgroup's LDS run all levels (and the L1 prox) in ONE launch;
+                               // 0: always one launch per level and dimension (and the FISTA plan refuses the wavelet term)
   int resident_spin = 100000;  // bound of every in-kernel wait, in polls (~1 us each: a wall-clock bound of ~0.1 s per
                                // wait); a launch that runs into it is a no-op and the host re-runs its iterations on the
                                // per-iteration pipeline (solvers.hip, *_recover)
@@ -1274,6 +1276,11 @@ bool rls_tv_single_ok(const rls_ctx* ctx, int32_t dtype, int32_t ndims, const in
 int32_t rls_tv_single_launch(rls_ctx* ctx, int32_t dtype, int32_t ndims, const int64_t* shape, int32_t ntv,
                              const int32_t* dims, const void* xin, const void* add, void* out, float lam, int iters,
                              const int* skip, int count = 1, int64_t ldv = 0, int skip_stride = 0);
+// wavelet.hip: out = W^T soft(W in, thr) as ONE single-workgroup launch (`skip` nullable; out may be in).  single_ok: `w` is a live
+// handle of this context, element type and length whose image takes that kernel under the context's current "wavelet_fused"
+bool rls_wavelet_single_ok(const rls_wavelet* w, const rls_ctx* ctx, int32_t dtype, int64_t n);
+uint64_t rls_wavelet_serial(const rls_wavelet* w);  // unique per handle ever created in this process (an address is not)
+int32_t rls_wavelet_prox_launch(rls_wavelet* w, const void* in, void* out, float thr, const int* skip);
 size_t rls_normal_fused_workspace(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* A, int64_t lda);
 int32_t rls_launch_normal_fused(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const void* A, int64_t lda,
                                 const void* p, void* v, void* slab, const int* skip);

@@ -752,7 +752,10 @@ struct rls_fista {
   int64_t tv_shape[4] = {1, 1, 1, 1};
   int32_t tv_dims[4] = {0, 0, 0, 0};
   void *tv_in = nullptr, *tv_out = nullptr;
-  float rho_h = 0.f;  // rho of the last init (the prox threshold rho * lambda is a launch argument of the FGP kernel)
+  rls_wavelet* wav = nullptr;  // RLS_REG_WAVELET (rls_fista_set_reg_wavelet): the caller's handle; its launch takes the FGP launch's place
+  uint64_t wav_serial = 0;     // ... and that handle's serial number: a cached graph has ITS filter, extents and depth as launch
+                               // arguments, and a handle created after another was destroyed may come back at the same address
+  float rho_h = 0.f;  // rho of the last init (the prox threshold rho * lambda is a launch argument of the FGP / wavelet kernel)
 };
 
 // Batched plans (shared A: rls_fista_create_batched, rls_cg_create_batched): the per-column kernels of FISTA, cg! and ADMM run
@@ -1021,13 +1024,16 @@ static int32_t fista_launch_update(rls_fista* s, unsigned nblocks, const col_bat
 #define RLS_FUPD_REG(EE)                                                                                            \
   hipLaunchKernelGGL((fista_update_reg_kernel<E, EE>), dim3(nblocks), dim3(UPD_THREADS), 0, op->ctx->stream,        \
                      (E*)s->buf[0], (E*)s->buf[1], (const E*)s->x0, (E*)s->res, (E*)s->y, n, s->sc, Bt)
-  if (s->reg_kind == RLS_REG_TV) {  // gradient step | FGP launch (its own workgroup, skipped once `done`) | projection, theta, y
+  if (s->reg_kind == RLS_REG_TV || s->reg_kind == RLS_REG_WAVELET) {  // gradient step | prox launch (its own workgroup, skipped once `done`) | projection, theta, y
     hipLaunchKernelGGL(fista_update_kernel<E>, dim3(1), dim3(UPD_THREADS), 0, op->ctx->stream, (E*)s->buf[0], (E*)s->buf[1],
                        (const E*)s->x0, (E*)s->res, (E*)s->y, n, s->sc, Bt, 1, (E*)s->tv_in, (const E*)s->tv_out);
     // (the threshold rho * lambda, the geometry and iterationsTV are kernel ARGUMENTS: a cached graph of this sequence is dropped
     //  whenever one of them changes -- fista_drop_graph in rls_fista_set_reg / _set_reg_tv / fista_init_finish)
-    tv_status = rls_tv_single_launch(op->ctx, op->dtype, s->tv_ndims, s->tv_shape, s->tv_ntv, s->tv_dims, s->tv_in, nullptr, s->tv_out,
-                                     s->rho_h * s->lambda, s->tv_iters, &s->sc->done, 1, 0, 0);
+    if (s->reg_kind == RLS_REG_WAVELET)  // W^T soft(W tv_in, rho lambda): analysis, threshold and synthesis in one workgroup's LDS
+      tv_status = rls_wavelet_prox_launch(s->wav, s->tv_in, s->tv_out, s->rho_h * s->lambda, &s->sc->done);
+    else
+      tv_status = rls_tv_single_launch(op->ctx, op->dtype, s->tv_ndims, s->tv_shape, s->tv_ntv, s->tv_dims, s->tv_in, nullptr, s->tv_out,
+                                       s->rho_h * s->lambda, s->tv_iters, &s->sc->done, 1, 0, 0);
     hipLaunchKernelGGL(fista_update_kernel<E>, dim3(1), dim3(UPD_THREADS), 0, op->ctx->stream, (E*)s->buf[0], (E*)s->buf[1],
                        (const E*)s->x0, (E*)s->res, (E*)s->y, n, s->sc, Bt, 2, (E*)s->tv_in, (const E*)s->tv_out);
   } else if (s->reg_kind != RLS_REG_L21 && n <= 4 * UPD_THREADS) {
@@ -3189,6 +3195,7 @@ int32_t rls_fista_set_reg(rls_fista* s, int32_t reg_kind, float lambda, int64_t 
   if (reg_kind == RLS_REG_L21 && (l21_slices <= 0 || s->op->N / l21_slices == 0))
     return rls_fail(ctx, RLS_E_INVALID, "fista_set_reg: slices must be in 1..N");
   if (s->reg_kind == RLS_REG_TV || reg_kind != s->reg_kind) s->graph.drop();  // another kernel sequence (or TV's baked arguments)
+  s->wav = nullptr;
   s->reg_kind = reg_kind;
   s->proj_kind = proj_kind;
   s->lambda = lambda;
@@ -3243,6 +3250,44 @@ int32_t rls_fista_set_reg_tv(rls_fista* s, float lambda, int32_t ndims, const in
   s->proj_kind = proj_kind;
   s->lambda = lambda;
   s->l21_slices = 1;
+  s->wav = nullptr;
+  return 0;
+}
+
+// FISTA with prox!(TransformedRegularization(L1Regularization, WaveletOp)): x <- W^T soft(W x, rho lambda) is the single-workgroup
+// launch of wavelet.hip between the two halves of the update, in the place and under the rules of the FGP launch above (single
+// right-hand side; the threshold is a launch argument, so a cached graph survives only an identical call).
+int32_t rls_fista_set_reg_wavelet(rls_fista* s, rls_wavelet* w, float lambda, int32_t proj_kind) {
+  if (!s) return RLS_E_INVALID;
+  rls_ctx* ctx = s->op->ctx;
+  if (!w || proj_kind < RLS_PROJ_NONE || proj_kind > RLS_PROJ_POSITIVE) return rls_fail(ctx, RLS_E_INVALID, "fista_set_reg_wavelet: bad argument");
+  if (s->nrhs != 1) return rls_fail(ctx, RLS_E_UNSUPPORTED, "fista_set_reg_wavelet: single right-hand side plans only");
+  if (!rls_wavelet_single_ok(w, ctx, s->op->dtype, s->op->N))
+    return rls_fail(ctx, RLS_E_UNSUPPORTED, "fista_set_reg_wavelet: the image does not take the single-workgroup wavelet kernel (or the handle is of another "
+                                            "context, element type or length); drive FISTA from the primitives");
+  RLS_HIP(ctx, rls_enter(ctx));
+  if (!s->tv_in) {  // both or neither (the blocks the TV launch uses)
+    rls_alloc_scope alloc_scope(ctx);
+    const size_t bytes = (size_t)s->op->N * rls_elem_size(s->op->dtype);
+    const plan_buffers::mark_t m = s->mem.mark();
+    s->mem.dev(&s->tv_in, bytes, false);
+    s->mem.dev(&s->tv_out, bytes, false);
+    if (const int e = s->mem.error()) {
+      s->mem.rollback(m);
+      return rls_fail(ctx, e, "fista_set_reg_wavelet: allocation failed");
+    }
+  }
+  // the handle's filter, extents and depth, lambda and rho are arguments of the captured launch: a cached graph survives only a call
+  // with the very same handle (by serial number: addresses are reused), lambda and projection
+  const uint64_t serial = rls_wavelet_serial(w);
+  if (!(s->reg_kind == RLS_REG_WAVELET && s->wav == w && s->wav_serial == serial && s->lambda == lambda && s->proj_kind == proj_kind))
+    s->graph.drop();
+  s->wav = w;
+  s->wav_serial = serial;
+  s->reg_kind = RLS_REG_WAVELET;
+  s->proj_kind = proj_kind;
+  s->lambda = lambda;
+  s->l21_slices = 1;
   return 0;
 }
 
@@ -3282,6 +3327,11 @@ static int32_t fista_init_finish(rls_fista* s, float rho, float theta, float rel
     // the single-workgroup FGP kernel was checked when the regulariser was set; its limits are context tunables that may have moved
     if (!rls_tv_single_ok(op->ctx, op->dtype, s->tv_ndims, s->tv_shape, s->tv_ntv, s->tv_dims))
       return rls_fail(ctx, RLS_E_UNSUPPORTED, "fista_init: the TV image no longer fits the single-workgroup FGP kernel");
+  }
+  if (s->reg_kind == RLS_REG_WAVELET) {  // the same two rules for the wavelet launch
+    if (rho != s->rho_h) s->graph.drop();
+    if (!rls_wavelet_single_ok(s->wav, op->ctx, op->dtype, op->N) || rls_wavelet_serial(s->wav) != s->wav_serial)
+      return rls_fail(ctx, RLS_E_UNSUPPORTED, "fista_init: the image no longer takes the single-workgroup wavelet kernel");
   }
   s->rho_h = rho;
   s->srv.off = false;  // (a new solve: the caller's pattern between iterates is judged afresh)

@@ -13,6 +13,7 @@ import ctypes as C
 import numpy as np
 from typing import Optional, Sequence, Tuple
 
+from . import _lib
 from ._lib import check
 from .arrays import DeviceVector
 
@@ -284,6 +285,95 @@ class GradientOp:
         return self.mul_(DeviceVector(self.n_out, x.dtype, x.ctx), x)
 
 
+class WaveletOp:
+    """LinearOperatorCollection.WaveletOp on device vectors (the reference's one documented trafo of TransformedRegularization,
+    docs/src/literate/explanations/regularization.jl:53-80): the orthogonal, periodic wavelet transform of a signal or of a
+    column-major image, `wt` = "db2" (the default, as upstream's wavelet(WT.db2)) or "haar", `levels` = None for the largest J with
+    2^J dividing every transformed extent.  Extents of 1 are dropped.  Orthogonal: mul_adj_ is the inverse.  The definition
+    (filters, periodisation, pyramid layout) is csrc/wavelet.hip's; one operator serves every context and element type (the
+    library handle is created on first use of each)."""
+
+    _FILTERS = {"haar": _lib.WT_HAAR, "db2": _lib.WT_DB2}
+
+    def __init__(self, shape, wt="db2", levels=None):
+        self.shape = tuple(int(s) for s in (shape if hasattr(shape, "__len__") else (shape,)))
+        if wt not in self._FILTERS:
+            raise ValueError(f"WaveletOp: unknown filter {wt!r} (one of {sorted(self._FILTERS)})")
+        self.wt = wt
+        if not self.shape or any(s < 1 for s in self.shape):
+            raise ValueError(f"WaveletOp: extents must be positive, got {self.shape}")
+        ext = [s for s in self.shape if s != 1]
+        if len(ext) > 2:
+            raise ValueError(f"WaveletOp: 1-D and 2-D shapes only, got {self.shape}")
+        full = 0
+        while ext and all(s % (2 << full) == 0 for s in ext):
+            full += 1
+        if levels is None:
+            levels = full
+        levels = int(levels)
+        if levels < 0:
+            raise ValueError(f"WaveletOp: levels must not be negative, got {levels}")
+        if levels > full:
+            raise ValueError(f"WaveletOp: an extent of {self.shape} is not divisible by 2^{levels}")
+        self.levels = levels
+        self.n_in = 1
+        for s in self.shape:
+            self.n_in *= s
+        self.n_out = self.n_in
+        self._cs = (C.c_int64 * len(self.shape))(*self.shape)
+        self._handles = {}   # (id(ctx), dtype code) -> (ctx, rls_wavelet*)
+
+    def size(self, i):
+        return (self.n_out, self.n_in)[i - 1]
+
+    def handle(self, ctx, code):
+        """the rls_wavelet of this operator on `ctx` for element type `code`, created on first use"""
+        key = (id(ctx), code)
+        if key not in self._handles:
+            w = C.c_void_p()
+            check(ctx.handle, ctx.lib.rls_wavelet_create(ctx.handle, code, len(self.shape), self._cs, self._FILTERS[self.wt], self.levels,
+                                                         C.byref(w)), "rls_wavelet_create")
+            self._handles[key] = (ctx, w)
+        return self._handles[key][1]
+
+    def _of(self, *vs):
+        for v in vs:
+            if v.n != self.n_in:
+                raise ValueError(f"WaveletOp: prod(shape)={self.n_in} does not match length(x)={v.n}")
+        if vs[0].ctx is not vs[-1].ctx or vs[0].code != vs[-1].code:
+            raise ValueError("WaveletOp: both vectors must be of one context and element type")
+        return self.handle(vs[0].ctx, vs[0].code)
+
+    def _apply(self, adjoint, y: DeviceVector, x: DeviceVector, alpha, beta):
+        if alpha != 1.0 or beta != 0.0:
+            raise ValueError("WaveletOp: only y = W x and x = W' y (alpha = 1, beta = 0)")
+        check(x.ctx.handle, x.ctx.lib.rls_wavelet_apply(self._of(x, y), adjoint, x.ptr, y.ptr), "rls_wavelet_apply")
+        return y
+
+    def mul_(self, z: DeviceVector, x: DeviceVector, alpha=1.0, beta=0.0):
+        return self._apply(0, z, x, alpha, beta)
+
+    def mul_adj_(self, x: DeviceVector, z: DeviceVector, alpha=1.0, beta=0.0):
+        return self._apply(1, x, z, alpha, beta)
+
+    def mul(self, x: DeviceVector) -> DeviceVector:
+        return self.mul_(DeviceVector(self.n_out, x.dtype, x.ctx), x)
+
+    def prox_l1_(self, x: DeviceVector, lam: float):
+        """x <- W' soft(W x, lam): one library call (one launch where the image fits a workgroup's LDS)"""
+        check(x.ctx.handle, x.ctx.lib.rls_prox_wavelet_l1(self._of(x), x.ptr, float(lam)), "rls_prox_wavelet_l1")
+        return x
+
+    def __del__(self):
+        for ctx, w in getattr(self, "_handles", {}).values():
+            try:
+                if w:   # (rls_wavelet_destroy checks for itself whether the context is still there)
+                    ctx.lib.rls_wavelet_destroy(w)
+            except Exception:
+                pass
+        self._handles = {}
+
+
 # ---- nested regularisation terms (src/Regularization/NestedRegularization.jl, ScaledRegularization.jl,
 # MaskedRegularization.jl, TransformedRegularization.jl), ProjectionRegularization (src/proximalMaps/ProxProj.jl)
 
@@ -385,7 +475,8 @@ class MaskedRegularization(AbstractNestedRegularization):
 
 class TransformedRegularization(AbstractNestedRegularization):
     """TransformedRegularization.jl:19-37: z = trafo * x ; prox!(reg, z) ; x = adjoint(trafo) * z.  `trafo` is a
-    DeviceMatrix, a GradientOp or any object with mul_(z, x) / mul_adj_(x, z) and size(1)."""
+    DeviceMatrix, a GradientOp, a WaveletOp or any object with mul_(z, x) / mul_adj_(x, z) and size(1).  A WaveletOp around a
+    plain L1 term is one library call (rls_prox_wavelet_l1: transform, threshold and inverse fused where the image allows)."""
 
     def __init__(self, reg, trafo):
         super().__init__(reg)
@@ -397,6 +488,8 @@ class TransformedRegularization(AbstractNestedRegularization):
         return t.mul_(DeviceVector(n_out, x.dtype, x.ctx), x)
 
     def prox_(self, x: DeviceVector, *args):
+        if isinstance(self.trafo, WaveletOp) and type(self.reg) is L1Regularization and len(args) == 1:
+            return self.trafo.prox_l1_(x, args[0])
         z = self._forward(x)
         self.reg.prox_(z, *args)
         self.trafo.mul_adj_(x, z)

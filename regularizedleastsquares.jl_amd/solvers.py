@@ -20,14 +20,15 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (PROJ_NONE, PROJ_POSITIVE, PROJ_REAL, REG_L1, REG_L2, REG_L21, REG_NONE, REG_TV, AdmmParams,
+from ._lib import (PROJ_NONE, PROJ_POSITIVE, PROJ_REAL, REG_L1, REG_L2, REG_L21, REG_NONE, REG_TV, REG_WAVELET, AdmmParams,
                    AdmmStatus, CgnrStatus, CgnrStatusD, CgStatus,
                    FistaStatus, FistaStatusD, PgmStatus, check)
 from .arrays import DeviceMatrix, DeviceVector, NormalOperator, OperatorHandle, is_double
 from .regularization import (AbstractParameterizedRegularization, AbstractProjectionRegularization, GradientOp,
                              L1Regularization, L2Regularization, findsink, findsinks, is_projection, sink,
                              L21Regularization, MeasurementBasedNormalization, NoNormalization, PositiveRegularization,
-                             RealRegularization, SystemMatrixBasedNormalization, TVRegularization, normalize)
+                             RealRegularization, SystemMatrixBasedNormalization, TVRegularization, normalize,
+                             TransformedRegularization, WaveletOp, _NormalizedNested)
 from .regularization import prox_ as _prox
 
 _EPS32 = float(np.finfo(np.float32).eps)
@@ -610,6 +611,9 @@ class FISTA(AbstractProximalGradientSolver):
     # and at most one projection); False = the reference's loop on the rls_*_d primitives, which TV, nested, transformed and
     # plug-and-play terms take in any case
     use_device_plan_f64 = True
+    # a wavelet-L1 term: True = the device plan (rls_fista_set_reg_wavelet) where the image takes its single-workgroup launch;
+    # False = the loop on the primitives (what any other transformed term runs), for comparisons
+    use_device_plan = True
 
     def __init__(self, A=None, *, AHA=None, reg=None, normalizeReg=None, iterations: int = 50, verbose: bool = False,
                  rho=None, theta=1, relTol=None, restart: str = "none"):
@@ -637,12 +641,24 @@ class FISTA(AbstractProximalGradientSolver):
             rho = 0.95 / power_iterations(_NormalApply(self._op), start)
         self.state = FISTAState(rho, theta, _eps_of(self._op, relTol))
 
+    def _wavelet_l1(self):
+        """the WaveletOp of TransformedRegularization(L1Regularization, WaveletOp) -- also under the wrapper normalisation puts around
+        a nested term -- else None.  lambda(self.reg) is the threshold's lambda either way."""
+        r = self.reg.reg if isinstance(self.reg, _NormalizedNested) else self.reg
+        if type(r) is TransformedRegularization and isinstance(r.trafo, WaveletOp) and type(r.reg) is L1Regularization:
+            return r.trafo
+        return None
+
     def _fused_kinds(self):
         """(reg_kind, lambda, slices, proj_kind) when the update is fusable, else None"""
         if self._op.double and (not self.use_device_plan_f64 or getattr(self, "_refused_f64", None) is self.reg):
             return None  # Float64 / ComplexF64 without a plan: the reference's loop on the primitives (rls_*_d)
         r = self.reg
-        if type(r) is L1Regularization:
+        if self._wavelet_l1() is not None:
+            if self._op.double or not self.use_device_plan:
+                return None  # (the wavelet launch of the plan is Float32 / ComplexF32 only)
+            kind, slices = REG_WAVELET, 1  # rls_prox_wavelet_l1's launch between the two halves of the plan's update
+        elif type(r) is L1Regularization:
             kind, slices = REG_L1, 1
         elif type(r) is L2Regularization and getattr(r, "lam_vector", None) is None:
             kind, slices = REG_L2, 1
@@ -671,7 +687,7 @@ class FISTA(AbstractProximalGradientSolver):
 
     def _init_batched(self, b, kw, previous):
         if not (type(self) is FISTA and isinstance(b, DeviceMatrix) and b.N > 1 and self.A is not None and not self._op.double
-                and (fused := self._fused_kinds()) is not None and fused[0] != REG_TV
+                and (fused := self._fused_kinds()) is not None and fused[0] not in (REG_TV, REG_WAVELET)
                 and not isinstance(self.normalizeReg, MeasurementBasedNormalization) and _cold_start_only(kw, "theta")):
             return None
         try:
@@ -730,10 +746,21 @@ class FISTA(AbstractProximalGradientSolver):
                 fused = None
             else:
                 check(h, st_tv, "rls_fista_set_reg_tv")
+        if fused is not None and fused[0] == REG_WAVELET:
+            wop = self._wavelet_l1()
+            if wop.n_in != N:
+                raise ValueError(f"WaveletOp: prod(shape)={wop.n_in} does not match the operator's N={N}")
+            st_w = lib.rls_fista_set_reg_wavelet(state._plan, wop.handle(b.ctx, b.code), fused[1], fused[3])
+            if st_w == -2:  # RLS_E_UNSUPPORTED: the image does not take the single-workgroup launch -- primitives
+                state._drop_plan(lib)
+                fused = None
+            else:
+                check(h, st_w, "rls_fista_set_reg_wavelet")
+                state._keep_wavelet = wop   # (the plan holds the operator's handle: it lives as long as the state uses it)
         if fused is not None:
             kind, lam_, slices, pk = fused
             e = state._entries[state._plan_d]
-            if not dbl and kind != REG_TV:   # (the Float64 plan and the TV launch have their regulariser set above)
+            if not dbl and kind not in (REG_TV, REG_WAVELET):   # (the Float64 plan, the TV and the wavelet launch have their regulariser set above)
                 check(h, lib.rls_fista_set_reg(state._plan, kind, lam_, slices, pk), "rls_fista_set_reg")
             check(h, getattr(lib, e.init)(state._plan, b.ptr, state.rho, float(theta), state.relTol, self.iterations,
                                           1 if self.restart == "gradient" else 0), e.init)
