@@ -334,7 +334,8 @@ def test_fallbacks(rls, ctx, dt):
 
 # shapes that select every instantiation of the two product kernels (plans_f64.hip: dp_gn_lanes, the CB choice of dp_gemv_t_v).
 # t = A p: G lanes along the rows, V elements per lane (V = 2: Float64 with even M and lda); G = 64 / 32 need >= 256 workgroups of
-# G V rows.  v = A^H t: CB columns per wave, 4 from N >= 8192, 2 from N >= 2048.
+# G V rows.  v = A^H t: CB columns per wave, 4 from N >= 8192, 2 from N >= 2048.  These shapes select the wide instantiations but
+# stay inside their tails (N = 8, M = 64): their unrolled main loops are reached in test_gpu_f64_plan_products.py, not here.
 VARIANTS = [("M=8192 (c128: G=32)", 8192, 8), ("M=16384 (c128: G=64; f64: V=2, G=32)", 16384, 8), ("M=32768 (f64: V=2, G=64)", 32768, 8),
             ("M=8193 (f64: V=1, G=32)", 8193, 8), ("M=16385 (f64: V=1, G=64)", 16385, 8), ("N=8192 (CB=4)", 64, 8192),
             ("N=8192, odd M (f64: V=1, CB=4)", 63, 8192), ("N=2048 (CB=2)", 64, 2048), ("N=2048, odd M (f64: V=1, CB=2)", 63, 2048)]
