@@ -233,6 +233,54 @@ int32_t rls_wavelet_levels(rls_wavelet* w, int32_t* out);
 int32_t rls_wavelet_apply(rls_wavelet* w, int32_t adjoint, const void* x, void* y);
 int32_t rls_prox_wavelet_l1(rls_wavelet* w, void* x, double lambda);
 
+/* Sparse system matrices: an operator handle for a SparseMatrixCSC, one set of entry points for
+ * RLS_F32 / C32 / F64 / C64.  Scalars cross as doubles and are narrowed to the element type's real type inside.
+ *   rls_sparse_csr_from_csc_host  pure host code, no context, no device call.  Validates a 0-based CSC triple -- colptr: int64[N + 1],
+ *                        colptr[0] = 0, non-decreasing, nnz = colptr[N]; rowval: int32 in [0, M), strictly increasing inside a
+ *                        column; 1 <= M, N < 2^31 -- and writes the CSR copy (rowptr_out: int64[M + 1], colval_out: int32[nnz],
+ *                        nzval_out: nnz elements) by a stable counting transpose: columns ascend inside every row.  With all
+ *                        three outputs null it only validates and writes nothing.  Anything else: RLS_E_INVALID (nothing is
+ *                        guaranteed about the outputs then).
+ *   rls_sparse_create    takes HOST arrays, validates them with the function above, builds the CSR copy on the host and uploads both
+ *                        layouts: A x gathers along CSR rows, A^T y / A^H y along CSC columns.  This is SETUP cost, paid once per
+ *                        matrix: O(nnz) host work, two copies of the matrix on the device, and the call waits for the upload (the
+ *                        host arrays are free on return).
+ *   rls_sparse_info      M, N, nnz (null pointers are skipped).
+ *   rls_sparse_to_host   the CSC triple back into host arrays (colptr_h: int64[N + 1], rowval_h: int32[nnz], nzval_h: nnz elements);
+ *                        waits for the copy.
+ *   rls_sparse_mul       the 5-argument mul!: y = alpha op(A) x + beta y, op = RLS_OP_N / T / C; x and y must not overlap.  Every
+ *                        output element is summed by one group of L lanes in a fixed order, without atomics: the same bits run to
+ *                        run.  beta = 0: y is not read.  L in {1, 4, 16, 64} is chosen per direction at creation from the mean
+ *                        non-zeros per output row (nnz / M for N, nnz / N for T and C); rls_tune_set("sparse_lanes", L) forces it
+ *                        (0: automatic; another value: RLS_E_INVALID).  Instantiations differ in the last bits, each reproducible.
+ *   rls_sparse_variant   the L a product in direction `op` would run with now.
+ *   rls_sparse_rownorm2  out_d[m] = rownorm²(A, m) (src/Utils.jl:26-33): device vector of M floats (F32 / C32) or doubles (F64 / C64).
+ *   rls_sparse_to_dense  A (M x N, column-major, leading dimension lda >= M) = the matrix: the M x N block is zeroed, then scattered.
+ *   rls_sparse_kaczmarz_sweep  the contract of rls_kaczmarz_sweep on the CSR rows: X (N x nrhs, ldx), U (M x nrhs, ldu), VL (M x nrhs,
+ *                        ldvl), one workgroup per column; rows_d[i], denom_d[i] (float for F32 / C32, double for F64 / C64), i < nused,
+ *                        rows distinct inside a sweep; n_sweeps repeats the order.  Per row step: tau = sum_k a_k x[col_k]
+ *                        (src/Utils.jl:89-100), alpha = denom[i] (u[row] - tau - eps_w vl[row]), x[col_k] += alpha conj(a_k)
+ *                        (src/Kaczmarz.jl:532-539), vl[row] += alpha eps_w.  x and vl are read inside the step that uses them (only
+ *                        matrix data is fetched ahead), so there is NO launch-splitting rule: nused = 1 with n_sweeps > 1 and
+ *                        consecutive rows that share columns are correct in one launch.  A row without non-zeros is a valid step
+ *                        (tau = 0).  x lives in the workgroup's LDS when N elements fit 159.5 KiB, else in global memory;
+ *                        rls_tune_set("sparse_kaczmarz_lds", 0) forces the latter.
+ * A null handle: RLS_E_INVALID.  All but create are asynchronous on the context's stream. */
+typedef struct rls_sparse rls_sparse;
+int32_t rls_sparse_csr_from_csc_host(int32_t dtype, int64_t M, int64_t N, const int64_t* colptr, const int32_t* rowval, const void* nzval,
+                                     int64_t* rowptr_out, int32_t* colval_out, void* nzval_out);
+int32_t rls_sparse_create(rls_ctx* ctx, int32_t dtype, int64_t M, int64_t N, const int64_t* colptr_h, const int32_t* rowval_h,
+                          const void* nzval_h, rls_sparse** out);
+int32_t rls_sparse_destroy(rls_sparse* sp);
+int32_t rls_sparse_info(rls_sparse* sp, int64_t* M, int64_t* N, int64_t* nnz);
+int32_t rls_sparse_to_host(rls_sparse* sp, int64_t* colptr_h, int32_t* rowval_h, void* nzval_h);
+int32_t rls_sparse_variant(rls_sparse* sp, int32_t op, int32_t* out);
+int32_t rls_sparse_mul(rls_sparse* sp, int32_t op, double alpha_re, double alpha_im, const void* x, double beta_re, double beta_im, void* y);
+int32_t rls_sparse_rownorm2(rls_sparse* sp, void* out_d);
+int32_t rls_sparse_to_dense(rls_sparse* sp, void* A, int64_t lda);
+int32_t rls_sparse_kaczmarz_sweep(rls_sparse* sp, int32_t nrhs, void* X, int64_t ldx, const void* U, int64_t ldu, void* VL, int64_t ldvl,
+                                  const int32_t* rows_d, const void* denom_d, int32_t nused, double eps_w, int32_t n_sweeps);
+
 /* ---------------------------------------------------------------------------------------------
  * operator handle: the backend's operator type for A (SURVEY 3.1 "two operator modes").
  * A' * A on it yields the lazy normal operator (matrix-free, two GEMVs) unless a Gram matrix is set.

@@ -164,6 +164,17 @@ PROTOTYPES = {
     "rls_wavelet_apply": (_i32, [_vp, _i32, _vp, _vp]),
     "rls_prox_wavelet_l1": (_i32, [_vp, _vp, _d]),
     "rls_fista_set_reg_wavelet": (_i32, [_vp, _vp, _f, _i32]),
+    # ---- sparse system matrices: CSC / CSR operator handle, products, rownorm², the sparse row sweep (csrc/sparse.hip) ----
+    "rls_sparse_csr_from_csc_host": (_i32, [_i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rls_sparse_create": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _pvp]),
+    "rls_sparse_destroy": (_i32, [_vp]),
+    "rls_sparse_info": (_i32, [_vp, _pi64, _pi64, _pi64]),
+    "rls_sparse_to_host": (_i32, [_vp, _vp, _vp, _vp]),
+    "rls_sparse_variant": (_i32, [_vp, _i32, _pi32]),
+    "rls_sparse_mul": (_i32, [_vp, _i32, _d, _d, _vp, _d, _d, _vp]),
+    "rls_sparse_rownorm2": (_i32, [_vp, _vp]),
+    "rls_sparse_to_dense": (_i32, [_vp, _vp, _i64]),
+    "rls_sparse_kaczmarz_sweep": (_i32, [_vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _d, _i32]),
     "rls_operator_create": (_i32, [_vp, _i32, _i64, _i64, _vp, _i64, _pvp]),
     "rls_operator_set_gram": (_i32, [_vp, _vp, _i64]),
     "rls_operator_destroy": (_i32, [_vp]),

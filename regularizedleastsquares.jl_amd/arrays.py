@@ -399,6 +399,161 @@ class DeviceMatrix:
         return NormalOperator(self)
 
 
+def _csc_from_host(S):
+    """(colptr int64[N + 1], rowval int32[nnz], nzval, (M, N)) -- contiguous, 0-based -- from that tuple or from a scipy.sparse
+    matrix (converted to CSC with sorted indices, duplicates summed).  scipy is imported only for the second form."""
+    if isinstance(S, (tuple, list)):
+        if len(S) != 4:
+            raise ValueError("DeviceSparseMatrix.from_host expects (colptr, rowval, nzval, (M, N)) or a scipy.sparse matrix")
+        colptr, rowval, nzval, shape = S
+    elif hasattr(S, "tocsc"):
+        S = S.tocsc(copy=True)
+        S.sum_duplicates()
+        S.sort_indices()
+        colptr, rowval, nzval, shape = S.indptr, S.indices, S.data, S.shape
+    else:
+        raise TypeError("DeviceSparseMatrix.from_host expects (colptr, rowval, nzval, (M, N)) or a scipy.sparse matrix")
+    M, N = (int(s) for s in shape)
+    nzval = np.ascontiguousarray(nzval)
+    dtype_code(nzval.dtype)   # (TypeError for an element type the backend does not compute in)
+    colptr, rowval = np.asarray(colptr), np.asarray(rowval)
+    if colptr.ndim != 1 or rowval.ndim != 1 or nzval.ndim != 1 or colptr.dtype.kind not in "iu" or rowval.dtype.kind not in "iu":
+        raise ValueError("colptr, rowval and nzval are 1-D arrays, colptr and rowval of integers")
+    if M < 1 or N < 1 or M >= 2 ** 31 or N >= 2 ** 31 or colptr.size != N + 1:
+        raise ValueError(f"a sparse {M} x {N} matrix needs 1 <= M, N < 2^31 and {N + 1} column pointers, got {colptr.size}")
+    if colptr[-1] != rowval.size or rowval.size != nzval.size:
+        raise ValueError(f"nnz = colptr[N] = {int(colptr[-1])}, but rowval has {rowval.size} and nzval {nzval.size} entries")
+    if rowval.size and (rowval.min() < 0 or rowval.max() >= 2 ** 31):
+        raise ValueError("row indices must lie in [0, M)")
+    return np.ascontiguousarray(colptr, dtype=np.int64), np.ascontiguousarray(rowval, dtype=np.int32), nzval, (M, N)
+
+
+class DeviceSparseMatrix:
+    """Sparse M x N operator in HBM (Julia `SparseMatrixCSC`): the CSC triple as given and a CSR copy, so that A x, A^T y and A^H y
+    are all gathers (rls_sparse, csrc/sparse.hip).  Served by CGNR, FISTA and Kaczmarz; `to_dense()` is the way to everything else."""
+
+    def __init__(self, csc, ctx: Optional[Context] = None):
+        colptr, rowval, nzval, (M, N) = csc
+        lib = _lib.load()
+        # validation runs on the host, ahead of any context: a malformed matrix is a ValueError on a machine without a device, too
+        # (no outputs: the checks alone; the one transpose of a construction is the one inside rls_sparse_create)
+        nnz = int(nzval.size)
+        if lib.rls_sparse_csr_from_csc_host(dtype_code(nzval.dtype), M, N, colptr.ctypes.data, rowval.ctypes.data, nzval.ctypes.data,
+                                            None, None, None) != 0:
+            raise ValueError("not a valid CSC matrix: colptr[0] = 0 and non-decreasing, row indices in [0, M) and strictly "
+                             "increasing inside a column (no duplicates)")
+        self.ctx = ctx or default_context()
+        self.M, self.N, self.nnz = M, N, nnz
+        self.dtype = np.dtype(nzval.dtype)
+        self.code = dtype_code(self.dtype)
+        self.double = is_double(self.code)
+        h = C.c_void_p()
+        check(self.ctx.handle, lib.rls_sparse_create(self.ctx.handle, self.code, M, N, colptr.ctypes.data, rowval.ctypes.data,
+                                                     nzval.ctypes.data, C.byref(h)), "rls_sparse_create")
+        self.handle = h
+
+    @classmethod
+    def from_host(cls, S, ctx: Optional[Context] = None) -> "DeviceSparseMatrix":
+        return cls(_csc_from_host(S), ctx)
+
+    def to_host(self):
+        """(colptr, rowval, nzval, (M, N)): the CSC triple, downloaded from the device (no host copy is kept)"""
+        colptr, rowval, nzval = np.empty(self.N + 1, np.int64), np.empty(self.nnz, np.int32), np.empty(self.nnz, self.dtype)
+        check(self.ctx.handle, self.ctx.lib.rls_sparse_to_host(self.handle, colptr.ctypes.data, rowval.ctypes.data if self.nnz else None,
+                                                               nzval.ctypes.data if self.nnz else None), "rls_sparse_to_host")
+        return colptr, rowval, nzval, (self.M, self.N)
+
+    @property
+    def shape(self):
+        return (self.M, self.N)
+
+    def size(self, i: int) -> int:  # 1-based like Julia's size(A, i)
+        return (self.M, self.N)[i - 1]
+
+    def variant(self, op: int) -> int:
+        """lanes per output row a product in direction `op` runs with (rls_sparse_variant)"""
+        v = C.c_int32()
+        check(self.ctx.handle, self.ctx.lib.rls_sparse_variant(self.handle, op, C.byref(v)), "rls_sparse_variant")
+        return v.value
+
+    def spmv_(self, op: int, x: DeviceVector, y: DeviceVector, alpha=1.0, beta=0.0):
+        """y = alpha * op(A) * x + beta * y     (5-arg mul!)"""
+        alpha, beta = complex(alpha), complex(beta)
+        nx, ny = (self.N, self.M) if op == OP_N else (self.M, self.N)
+        if x.n != nx or y.n != ny:
+            raise ValueError(f"mul: dimension mismatch: A is {self.M}x{self.N}, x {x.n}, y {y.n}, op {op}")
+        if x.dtype != self.dtype or y.dtype != self.dtype:
+            raise TypeError(f"mul: element types differ: A {self.dtype}, x {x.dtype}, y {y.dtype}")
+        check(self.ctx.handle, self.ctx.lib.rls_sparse_mul(self.handle, op, alpha.real, alpha.imag, x.ptr, beta.real, beta.imag, y.ptr),
+              "rls_sparse_mul")
+        return y
+
+    def mul_(self, y: DeviceVector, x: DeviceVector, alpha=1.0, beta=0.0):
+        return self.spmv_(OP_N, x, y, alpha, beta)
+
+    def mul_adj_(self, x: DeviceVector, y: DeviceVector, alpha=1.0, beta=0.0):
+        return self.spmv_(OP_C, y, x, alpha, beta)
+
+    def mul_transpose_(self, x: DeviceVector, y: DeviceVector, alpha=1.0, beta=0.0):
+        return self.spmv_(OP_T, y, x, alpha, beta)
+
+    def __matmul__(self, x: DeviceVector) -> DeviceVector:
+        return self.mul_(DeviceVector(self.M, self.dtype, self.ctx), x)
+
+    def rownorm2(self) -> "DeviceVector":
+        """rownorm²(A, m) for every row m (src/Utils.jl:26-33): vector of the element type's real type"""
+        out = DeviceVector(self.M, np.float64 if self.double else np.float32, self.ctx)
+        check(self.ctx.handle, self.ctx.lib.rls_sparse_rownorm2(self.handle, out.ptr), "rls_sparse_rownorm2")
+        return out
+
+    def to_dense(self) -> DeviceMatrix:
+        """Matrix(A): the way to Gram mode (`A.to_dense().gram()`) and to the solvers that take dense operators only"""
+        D = DeviceMatrix(self.M, self.N, self.dtype, self.ctx)
+        check(self.ctx.handle, self.ctx.lib.rls_sparse_to_dense(self.handle, D.ptr, D.lda), "rls_sparse_to_dense")
+        return D
+
+    def normal_operator(self) -> "SparseNormalOperator":
+        """A' * A, lazy: two sparse products per apply"""
+        return SparseNormalOperator(self)
+
+    def __del__(self):
+        try:
+            if self.handle and self.ctx.handle:
+                self.ctx.lib.rls_sparse_destroy(self.handle)
+        except Exception:
+            pass
+        self.handle = None
+
+
+class SparseNormalOperator:
+    """Lazy A^H A of a DeviceSparseMatrix: size N x N, eltype of A.  It is also the operator object the primitive loops of CGNR
+    and FISTA run on: M, N, code, double, mul_normal_, and no plan handle."""
+
+    handle = None   # no rls_operator: the device plans take dense operators only
+    sparse = True
+    gram = None
+
+    def __init__(self, A: DeviceSparseMatrix):
+        self.A = A
+        self.dtype, self.code, self.double = A.dtype, A.code, A.double
+        self.ctx = A.ctx
+        self.M, self.N = A.M, A.N
+        self.shape = (A.N, A.N)
+        self._t = None
+
+    def size(self, i: int) -> int:
+        return self.A.N
+
+    def mul_normal_(self, v: DeviceVector, p: DeviceVector):
+        if self._t is None:
+            self._t = DeviceVector(self.M, self.dtype, self.ctx)
+        self.A.mul_(self._t, p)
+        return self.A.mul_adj_(v, self._t)
+
+    def mul_(self, v: DeviceVector, p: DeviceVector):
+        return self.mul_normal_(v, p)
+
+
 class WeightingOp:
     """LinearOperatorCollection.WeightingOp(weights): diag(weights) (docs/src/literate/howto/normal_operator.jl:41)"""
 
@@ -413,6 +568,8 @@ def ProdOp(W: WeightingOp, A: DeviceMatrix) -> DeviceMatrix:
     instead of carrying a diagonal scale through every kernel."""
     if not isinstance(W, WeightingOp):
         raise TypeError("ProdOp: only ProdOp(WeightingOp(w), A) is supported")
+    if isinstance(A, DeviceSparseMatrix):
+        raise TypeError("ProdOp: a sparse A is not supported (ProdOp(WeightingOp(w), A.to_dense()) is the dense route)")
     w = W.weights
     if w.dtype != A.dtype:
         w = DeviceVector.from_host(w.to_host().astype(A.dtype), A.ctx)

@@ -30,7 +30,15 @@ import numpy as np
 
 from ._lib import (PROJ_NONE, PROJ_POSITIVE, PROJ_REAL, REG_L1, REG_L2, REG_L21, REG_NONE, REG_TV, AdmmStatus, CgnrStatus, CgStatus,
                    FistaStatus, check)
-from .arrays import Context
+from .arrays import Context, DeviceSparseMatrix
+
+
+def _dense_only(*operators):
+    """the multi-GPU classes shard and upload dense host arrays: a sparse operator is refused, not densified behind the caller's back"""
+    for A in operators:
+        if isinstance(A, DeviceSparseMatrix) or hasattr(A, "tocsc"):
+            raise TypeError("multigpu: sparse operators (DeviceSparseMatrix) are served by CGNR, FISTA and Kaczmarz; the multi-GPU "
+                            "solvers take dense host arrays")
 
 
 # --------------------------------------------------------------------------------------------
@@ -116,6 +124,7 @@ class ConcurrentSolves:
     def upload(self, matrices):
         """A_k -> DeviceMatrix on context k % n_streams (residency before a timed region)"""
         rls = self.rls
+        _dense_only(*matrices)
         return [rls.DeviceMatrix.from_host(A, self.ctxs[k % len(self.ctxs)]) for k, A in enumerate(matrices)]
 
     def solve(self, device_matrices, rhs, make_solver):
@@ -190,6 +199,7 @@ class HipLocalOps:
     stream, which orders the kernels and the collective without extra events."""
 
     def __init__(self, rls, A_local: np.ndarray, device: int):
+        _dense_only(A_local)
         import torch
 
         self.rls, self.torch = rls, torch
@@ -313,6 +323,7 @@ class CommRowShardedCGNR:
 
     def __init__(self, rls, shards, devices=None, transport=COMM_AUTO, lam=0.0, iterations=10,
                  relTol=float(np.finfo(np.float32).eps)):
+        _dense_only(*shards)
         self.rls = rls
         lib = rls.load()
         n = len(shards)
@@ -388,6 +399,7 @@ class _CommHost:
     and a set of named device vectors per rank"""
 
     def __init__(self, rls, shards, names, devices=None, transport=COMM_AUTO, threads=True):
+        _dense_only(*shards)
         self.rls = rls
         lib = rls.load()
         n = len(shards)
@@ -624,6 +636,7 @@ class HipFistaOps:
     """Rank-local half-steps of row-sharded FISTA on the GPU (rls_fista_init_local_a/b, rls_fista_step_local_a/b)."""
 
     def __init__(self, rls, A_local: np.ndarray, device: int, reg=None, proj=None):
+        _dense_only(A_local)
         import torch
 
         self.rls, self.torch = rls, torch
@@ -720,6 +733,7 @@ class HipAdmmOps:
     the distributed step."""
 
     def __init__(self, rls, A_local: np.ndarray, device: int, reg=None, proj=()):
+        _dense_only(A_local)
         import torch
 
         self.rls, self.torch = rls, torch

@@ -23,7 +23,8 @@ from . import _lib
 from ._lib import (PROJ_NONE, PROJ_POSITIVE, PROJ_REAL, REG_L1, REG_L2, REG_L21, REG_NONE, REG_TV, REG_WAVELET, AdmmParams,
                    AdmmStatus, CgnrStatus, CgnrStatusD, CgStatus,
                    FistaStatus, FistaStatusD, PgmStatus, check)
-from .arrays import DeviceMatrix, DeviceVector, NormalOperator, OperatorHandle, is_double
+from .arrays import (DeviceMatrix, DeviceSparseMatrix, DeviceVector, NormalOperator, OperatorHandle, SparseNormalOperator,
+                     is_double)
 from .regularization import (AbstractParameterizedRegularization, AbstractProjectionRegularization, GradientOp,
                              L1Regularization, L2Regularization, findsink, findsinks, is_projection, sink,
                              L21Regularization, MeasurementBasedNormalization, NoNormalization, PositiveRegularization,
@@ -55,9 +56,30 @@ def _as_list(reg):
     return list(reg) if isinstance(reg, (list, tuple)) else [reg]
 
 
-def _resolve_operator(A, AHA):
+_SPARSE_SERVED = "sparse operators (DeviceSparseMatrix) are served by CGNR, FISTA and Kaczmarz; A.to_dense() is the way to the others"
+
+
+def _resolve_sparse_operator(A, AHA):
+    """the sparse branch of _resolve_operator: (A, operator object).  AHA = None or A's own lazy normal operator: the primitive
+    loops on two sparse products per apply (SparseNormalOperator: no plan handle); a dense Gram matrix: the existing Gram path."""
+    if AHA is None or (isinstance(AHA, SparseNormalOperator) and AHA.A is A):
+        return A, AHA if AHA is not None else A.normal_operator()
+    if isinstance(AHA, DeviceMatrix):
+        if AHA.M != A.N or AHA.N != A.N or AHA.dtype != A.dtype:
+            raise ValueError(f"Gram matrix must be {A.N} x {A.N} {A.dtype}")
+        return A, OperatorHandle(None, AHA)   # Gram-only, as `AHA=` alone gives it
+    raise TypeError("with a sparse A, AHA must be None, A.normal_operator() or a dense Gram DeviceMatrix (e.g. A.to_dense().gram())")
+
+
+def _resolve_operator(A, AHA, sparse_ok=False):
     """Returns (A: DeviceMatrix|None, OperatorHandle).  AHA=None means the constructor default
     `A' * A`, which for this backend's operator type is the lazy normal operator (matrix-free)."""
+    if isinstance(A, DeviceSparseMatrix) or isinstance(AHA, SparseNormalOperator):
+        if not sparse_ok:
+            raise TypeError(_SPARSE_SERVED)
+        if A is None:
+            A = AHA.A
+        return _resolve_sparse_operator(A, AHA)
     if A is not None and not isinstance(A, DeviceMatrix):
         raise TypeError("A must be a DeviceMatrix (the backend is selected by the array type, as in the reference)")
     gram = None
@@ -73,6 +95,30 @@ def _resolve_operator(A, AHA):
         raise TypeError("AHA must be a DeviceMatrix (Gram matrix) or a NormalOperator")
     return A, OperatorHandle(A, gram)
 
+
+
+def _sparse_primitives(op) -> bool:
+    """the operator is a sparse A on its lazy normal operator: no device plan, CGNR and FISTA run their loops on the primitives"""
+    return getattr(op, "sparse", False)
+
+
+def _take_sparse_gram(solver):
+    """A sparse A with an explicit dense Gram matrix runs the Gram path as `AHA=` alone does: the solver's A becomes None (the
+    plans iterate on AHA) and init! forms A^H b with the sparse product first (_sparse_gram_rhs).  Returns the sparse A, or None."""
+    if isinstance(solver.A, DeviceSparseMatrix) and isinstance(solver._op, OperatorHandle):
+        A, solver.A = solver.A, None
+        return A
+    return None
+
+
+def _sparse_gram_rhs(solver, b):
+    """b, or A^H b where the solver holds a sparse A next to a dense Gram matrix"""
+    A = solver._sparse_A
+    if A is None:
+        return b
+    if b.n != A.M:
+        raise ValueError(f"DimensionMismatch: b has length {b.n}, expected {A.M}")
+    return A.mul_adj_(b.similar(A.N), b)
 
 
 def _scalar_state(solver):
@@ -242,9 +288,10 @@ class CGNR(AbstractKrylovSolver):
     use_device_plan_f64 = True
 
     def __init__(self, A=None, *, AHA=None, reg=None, normalizeReg=None, iterations: int = 10, relTol=None):
-        self.A, self._op = _resolve_operator(A, AHA)
+        self.A, self._op = _resolve_operator(A, AHA, sparse_ok=True)
         self.AHA = AHA if AHA is not None else self.A.normal_operator()
         regs = normalize(normalizeReg, _as_list(reg), self.A, None)
+        self._sparse_A = _take_sparse_gram(self)
         i2 = findsink(L2Regularization, regs)  # src/CGNR.jl:69 (sink type: nested / scaled L2 terms count)
         l2 = [] if i2 is None else [regs[i2]]
         self.L2 = l2[0] if l2 else L2Regularization(0.0)
@@ -263,6 +310,8 @@ class CGNR(AbstractKrylovSolver):
         if not (isinstance(b, DeviceMatrix) and b.N > 1 and not self.constr and _cold_start_only(kw)
                 and not isinstance(self.normalizeReg, MeasurementBasedNormalization)):  # per-column lambda: not batched
             return None
+        if _sparse_primitives(self._op) or self._sparse_A is not None:
+            return None  # a sparse operator: per-column solves
         try:
             st = CgnrBatchedState(self, b)
             st.init(b, _scalar_state(self))
@@ -276,9 +325,10 @@ class CGNR(AbstractKrylovSolver):
             # the reference's x0 != 0 branch reads a field that does not exist (src/CGNR.jl:119)
             raise NotImplementedError("CGNR: x0 != 0 is unsupported (it throws in the reference as well)")
         lib = b.ctx.lib
-        if self._op.double and not self.use_device_plan_f64:
+        if _sparse_primitives(self._op) or (self._op.double and not self.use_device_plan_f64):
             return self._init_from_primitives(state, b)
-        self._prepare(state, b)
+        b_in, b = b, _sparse_gram_rhs(self, b)   # (a sparse A next to a dense Gram matrix: the Gram path on A^H b)
+        self._prepare(state, b, b_in)
         init = state._entries[state._plan_d].init
         check(b.ctx.handle, getattr(lib, init)(state._plan, b.ptr, float(self.L2.lam), state.relTol, self.iterations), init)
         self._after_init(state)
@@ -342,11 +392,12 @@ class CGNR(AbstractKrylovSolver):
         state._residual = state.x0.norm()
         return state.x, state
 
-    def _prepare(self, state: CGNRState, b: DeviceVector):
-        """everything of init! ahead of the device work: the normalised L2 weight, the state vectors and the plan"""
+    def _prepare(self, state: CGNRState, b: DeviceVector, b_norm=None):
+        """everything of init! ahead of the device work: the normalised L2 weight, the state vectors and the plan
+        (b_norm: the right-hand side the normalisation sees, where it is not b)"""
         N = self._op.N
         lib = b.ctx.lib
-        self.L2 = normalize(self.normalizeReg, self.L2, self.A, b, in_solver=True)  # :129
+        self.L2 = normalize(self.normalizeReg, self.L2, self.A, b if b_norm is None else b_norm, in_solver=True)  # :129
         fresh = state.x is None or state.x.ctx is not b.ctx or state.x.dtype != b.dtype or state.x.n != N
         if fresh:
             state.x, state.x0, state.pl, state.vl = (b.similar(N) for _ in range(4))  # similar(b, ...) :92-95
@@ -380,7 +431,7 @@ class CGNR(AbstractKrylovSolver):
         """iterate(solver, state)  src/CGNR.jl:143-178; returns None when done.  One library call per iteration: the step
         and the status read-back (`done`, the convergence record) travel together (rls_cgnr_step_status)"""
         state = state or self.state
-        if self._op.double and not state._plan:
+        if (self._op.double or _sparse_primitives(self._op)) and not state._plan:
             return self._iterate_from_primitives(state)
         lib = state.x.ctx.lib
         if not getattr(state, "_status_valid", False):
@@ -396,7 +447,7 @@ class CGNR(AbstractKrylovSolver):
 
     def _run(self, state: CGNRState):
         """no callbacks: enqueue every remaining iteration (no-ops once done) and finalise"""
-        if self._op.double and not state._plan:
+        if (self._op.double or _sparse_primitives(self._op)) and not state._plan:
             while self.iterate(state) is not None:
                 pass
             return
@@ -617,7 +668,7 @@ class FISTA(AbstractProximalGradientSolver):
 
     def __init__(self, A=None, *, AHA=None, reg=None, normalizeReg=None, iterations: int = 50, verbose: bool = False,
                  rho=None, theta=1, relTol=None, restart: str = "none"):
-        self.A, self._op = _resolve_operator(A, AHA)
+        self.A, self._op = _resolve_operator(A, AHA, sparse_ok=True)
         self.AHA = AHA if AHA is not None else self.A.normal_operator()
         regs = _as_list(reg) or [L1Regularization(0.0)]
         self.proj = [r for r in regs if is_projection(r)]
@@ -625,6 +676,7 @@ class FISTA(AbstractProximalGradientSolver):
         if len(rest) != 1:
             raise ValueError(f"FISTA does not allow for more additional regularization terms, found {len(rest)}")
         self.reg = normalize(normalizeReg, rest, self.A, None)[0]
+        self._sparse_A = _take_sparse_gram(self)
         self.normalizeReg = normalizeReg or NoNormalization()
         self.verbose = bool(verbose)
         if restart not in ("none", "gradient"):
@@ -653,6 +705,8 @@ class FISTA(AbstractProximalGradientSolver):
         """(reg_kind, lambda, slices, proj_kind) when the update is fusable, else None"""
         if self._op.double and (not self.use_device_plan_f64 or getattr(self, "_refused_f64", None) is self.reg):
             return None  # Float64 / ComplexF64 without a plan: the reference's loop on the primitives (rls_*_d)
+        if _sparse_primitives(self._op):
+            return None  # a sparse A on its lazy normal operator: the generic branch, two sparse products per iteration
         r = self.reg
         if self._wavelet_l1() is not None:
             if self._op.double or not self.use_device_plan:
@@ -687,6 +741,7 @@ class FISTA(AbstractProximalGradientSolver):
 
     def _init_batched(self, b, kw, previous):
         if not (type(self) is FISTA and isinstance(b, DeviceMatrix) and b.N > 1 and self.A is not None and not self._op.double
+                and not _sparse_primitives(self._op)
                 and (fused := self._fused_kinds()) is not None and fused[0] not in (REG_TV, REG_WAVELET)
                 and not isinstance(self.normalizeReg, MeasurementBasedNormalization) and _cold_start_only(kw, "theta")):
             return None
@@ -701,6 +756,7 @@ class FISTA(AbstractProximalGradientSolver):
         """init!(solver, state, b; x0 = 0, theta = 1)   src/FISTA.jl:94-129"""
         N = self._op.N
         lib, h = b.ctx.lib, b.ctx.handle
+        b = _sparse_gram_rhs(self, b)   # (a sparse A next to a dense Gram matrix: the Gram path on A^H b)
         if isinstance(self.normalizeReg, MeasurementBasedNormalization):  # :128 normalises with x0 = A^H b
             x0n = b if self.A is None else self.A.mul_adj_(b.similar(N), b)
             self.reg = normalize(self.normalizeReg, self.reg, self.A, x0n, in_solver=True)
@@ -2087,6 +2143,17 @@ def _kaczmarz_launch_splits(rows, nused, n_sweeps):
     return [(c0, c1 - c0) for c0, c1 in zip(cuts[:-1], cuts[1:])]
 
 
+class _SparseRowAccess:
+    """what a Kaczmarz state asks of its row-access structure, for a sparse A: the handle's CSR rows are that structure, so
+    `mul_transpose_` -- A x through the stored transpose(A) in the dense solver -- is the forward product"""
+
+    def __init__(self, A):
+        self.A = A
+
+    def mul_transpose_(self, t, x):
+        return self.A.mul_(t, x)
+
+
 class KaczmarzState(AbstractSolverState):
     """src/Kaczmarz.jl:23-32.  nrhs > 1: the columns of a matrix right-hand side advance in ONE launch, one
     workgroup per column (backend scheduler, same per-column results as MultiThreadingState)."""
@@ -2139,8 +2206,9 @@ class Kaczmarz(AbstractRowActionSolver):
     def __init__(self, A=None, *, reg=None, normalizeReg=None, randomized: bool = False, subMatrixFraction=0.15,
                  shuffleRows: bool = False, seed: int = 1234, iterations: int = 10, greedy_randomized: bool = False,
                  theta=None):
-        if not isinstance(A, DeviceMatrix):
-            raise TypeError("A must be a DeviceMatrix (the backend is selected by the array type, as in the reference)")
+        if not isinstance(A, (DeviceMatrix, DeviceSparseMatrix)):
+            raise TypeError("A must be a DeviceMatrix or a DeviceSparseMatrix (the backend is selected by the array type, as in the reference)")
+        self._sparse = isinstance(A, DeviceSparseMatrix)
         if greedy_randomized:
             raise NotImplementedError("greedy randomized Kaczmarz is not defined for GPU arrays (test/testKaczmarz.jl:114)")
         self.A_in = A
@@ -2156,6 +2224,9 @@ class Kaczmarz(AbstractRowActionSolver):
         lam = self.L2.lam_vector if getattr(self.L2, "lam_vector", None) is not None else self.L2.lam
         if np.ndim(lam) == 1 and not isinstance(self.normalizeReg, (NoNormalization, SystemMatrixBasedNormalization)):
             raise ValueError("Tikhonov matrix for Kaczmarz is only valid with no or system matrix based normalization")
+        if np.ndim(lam) == 1 and self._sparse:
+            raise ValueError("Kaczmarz: a vector-valued lambda (Tikhonov matrix) with a sparse A is not supported; "
+                             "use A.to_dense() for it")
         self.randomized, self.shuffleRows, self.seed = bool(randomized), bool(shuffleRows), int(seed)
         self.iterations = int(iterations)
         self.subMatrixSize = int(round(subMatrixFraction * A.M))
@@ -2169,6 +2240,14 @@ class Kaczmarz(AbstractRowActionSolver):
         dbl = is_double(A.code)   # Float64 / ComplexF64: the same sweep on the double-precision entry points (rls_*_d)
         rt = np.float64 if dbl else np.float32
         self._rt = rt
+        if self._sparse:
+            # the CSR copy inside the handle IS the structure for row access: no transposed copy; the same row index and
+            # zero-energy-row rule as below
+            self.At = _SparseRowAccess(A)
+            self._lam_vec = None
+            self._lam_used = float(lam)
+            self._index_rows(A.rownorm2().to_host(), rt, lam)
+            return
         transpose = lib.rls_transpose_d if dbl else lib.rls_transpose
         scale_rows = lib.rls_scale_rows_d if dbl else lib.rls_scale_rows
         At = DeviceMatrix(A.N, A.M, A.dtype, ctx)
@@ -2186,7 +2265,10 @@ class Kaczmarz(AbstractRowActionSolver):
             Arow = A
         self.At = At
         self._lam_used = float(lam)
-        s2 = Arow.rownorm2().to_host()
+        self._index_rows(Arow.rownorm2().to_host(), rt, lam)
+
+    def _index_rows(self, s2, rt, lam):
+        """rowindex, denominators and sampling weights from the squared row norms (:372-383): rows without energy are skipped"""
         self._s2 = s2
         self.rowindex = np.nonzero(s2 > 0)[0].astype(np.int64)
         self.denom = (rt(1) / (s2[self.rowindex] + rt(lam))).astype(rt)
@@ -2198,8 +2280,8 @@ class Kaczmarz(AbstractRowActionSolver):
 
     def _init_batched(self, b, kw, previous):
         """all columns in one launch, one workgroup per column"""
-        if not isinstance(b, DeviceMatrix):
-            return None
+        if not isinstance(b, DeviceMatrix) or self._sparse:
+            return None   # (a sparse operator: per-column solves)
         self.state = st = KaczmarzState()  # (in place at once: the last solve's buffers go before this one's are allocated)
         self.init_(st, b, **kw)
         return st
@@ -2258,8 +2340,8 @@ class Kaczmarz(AbstractRowActionSolver):
     def _fused(self):
         """(proj_kind, reg_kind, lambda) of `reg` for rls_kaczmarz_solve, or None: the host loop (a term the kernel does not
         apply, or rls_tune_set "kaczmarz_fused" = 0 -- the context owns the switch, whoever set it)"""
-        if not self.A_in.ctx.tuned("kaczmarz_fused"):
-            return None
+        if self._sparse or not self.A_in.ctx.tuned("kaczmarz_fused"):
+            return None   # (no fused solve for sparse rows: the maps run between the sweeps, the "kaczmarz_fused" = 0 shape)
         return _kaczmarz_fused_kinds(self.reg)
 
     def _sweep(self, st, n_sweeps, fus=None, first=0, stride=0):
@@ -2271,6 +2353,10 @@ class Kaczmarz(AbstractRowActionSolver):
         ldvl = st.vl.lda if st.matrix else A.M
         dbl = is_double(A.code)
         nused = len(st.usedIndices)
+        if self._sparse:
+            check(ctx.handle, ctx.lib.rls_sparse_kaczmarz_sweep(A.handle, st.nrhs, st.x.ptr, ldx, st.u.ptr, ldu, st.vl.ptr, ldvl, st._rows.ptr,
+                                                                st._den.ptr, nused, float(st.eps_w), int(n_sweeps)), "rls_sparse_kaczmarz_sweep")
+            return
         head = (ctx.handle, A.code, A.M, A.N, self.At.ptr, self.At.lda, st.nrhs, st.x.ptr, ldx, st.u.ptr, ldu, st.vl.ptr, ldvl)
         if fus in (None, (PROJ_NONE, REG_NONE, 0.0)) and not stride:
             sweep = ctx.lib.rls_kaczmarz_sweep_d if dbl else ctx.lib.rls_kaczmarz_sweep
