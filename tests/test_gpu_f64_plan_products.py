@@ -37,8 +37,11 @@ from test_gpu_f64_plans import GRAM_TOL, ITER_TOL, SCALAR_TOL, _early_tols, clos
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -53
 GUARD = 5
-SENTINEL = {np.dtype(np.float64): np.float64(-1.2345e300), np.dtype(np.complex128): np.complex128(-1.2345e300 + 9.875e299j)}
-LD = {np.dtype(np.float64): np.longdouble, np.dtype(np.complex128): np.clongdouble}
+SENTINEL = {np.dtype(np.float64): np.float64(-1.2345e300), np.dtype(np.complex128): np.complex128(-1.2345e300 + 9.875e299j),
+            np.dtype(np.float32): np.float32(-1.2345e30), np.dtype(np.complex64): np.complex64(-1.2345e30 + 9.875e29j)}
+# (the reference type of each element type; the 4-byte types are judged in float64 / complex128: test_gpu_gemv_edges.py)
+LD = {np.dtype(np.float64): np.longdouble, np.dtype(np.complex128): np.clongdouble,
+      np.dtype(np.float32): np.float64, np.dtype(np.complex64): np.complex128}
 POOL = {np.dtype(np.float64): 5_400_000, np.dtype(np.complex128): 2_700_000}   # the largest operand of each type, in elements
 KINDS = [("f64-V1", np.float64, 1), ("f64-V2", np.float64, 2), ("c128-V1", np.complex128, 1)]
 WORST = {}   # group -> (largest error / bound, case)
@@ -126,11 +129,11 @@ def _report():
 
 
 class Guarded:
-    """a device vector of n + GUARD elements (+ `lead` in front), the excess prefilled with the sentinel"""
+    """a device vector of n + GUARD elements (+ `lead` in front), the excess prefilled with the sentinel (or with `fill`)"""
 
-    def __init__(self, rls, ctx, dt, n, body=None, lead=0):
+    def __init__(self, rls, ctx, dt, n, body=None, lead=0, fill=None):
         self.n, self.lead, self.dt = n, lead, np.dtype(dt)
-        self.host0 = np.full(lead + n + GUARD, SENTINEL[self.dt], dtype=self.dt)
+        self.host0 = np.full(lead + n + GUARD, SENTINEL[self.dt] if fill is None else fill, dtype=self.dt)
         if body is not None:
             self.host0[lead: lead + n] = body
         self.dev = rls.DeviceVector.from_host(self.host0, ctx)
