@@ -281,6 +281,44 @@ int32_t rls_sparse_to_dense(rls_sparse* sp, void* A, int64_t lda);
 int32_t rls_sparse_kaczmarz_sweep(rls_sparse* sp, int32_t nrhs, void* X, int64_t ldx, const void* U, int64_t ldu, void* VL, int64_t ldvl,
                                   const int32_t* rows_d, const void* denom_d, int32_t nused, double eps_w, int32_t n_sweeps);
 
+/* Matrix-free operators: SamplingOp, FFTOp and their product, the operator of the reference's compressed-sensing
+ * example.  Scalars cross as doubles.  A null handle: RLS_E_INVALID.  All but create are asynchronous on the context's stream.
+ *   rls_sampling_create  dtype RLS_F32 / C32 / F64 / C64; idx_host: m distinct 0-based int32 indices into [0, N), 1 <= m <= N < 2^31, a
+ *                        HOST array, validated on the host before anything is uploaded (an index out of range or repeated:
+ *                        RLS_E_INVALID).  Uploads the indices, builds the 0 / 1 mask on the device and waits for both.
+ *   rls_sampling_mul     the 5-argument mul!: op = RLS_OP_N: y[k] = alpha x[idx[k]] + beta y[k] (m outputs); RLS_OP_T / RLS_OP_C (one and the
+ *                        same for a real 0 / 1 matrix): y = beta y over all N elements, then y[idx[k]] += alpha x[k] -- a scatter
+ *                        without atomics, the indices being unique.  beta = 0: y is not read.  alpha = 1, beta = 0: plain copies.  x and y
+ *                        must not overlap.
+ *   rls_sampling_mul_normal  v = mask .* p (N elements; v may be p): exact products with 0 or 1 of the element's real type.
+ *   rls_fft_create       dtype RLS_C32 / C64 (else RLS_E_INVALID); shape[ndims]: extents of 1 are dropped, one or two may remain, each a
+ *                        power of two of at most 8192 (C32) / 4096 (C64) points -- anything else: RLS_E_UNSUPPORTED.  flags: RLS_FFT_SHIFT |
+ *                        RLS_FFT_UNITARY (LinearOperatorCollection's FFTOp(T; shape, shift = true, unitary = true)).  With the image
+ *                        column-major: F x = fftshift(fftn(ifftshift(x))) / sqrt(n); without RLS_FFT_SHIFT the two shifts go, without
+ *                        RLS_FFT_UNITARY the scale.  Owns the twiddle table (computed in double on the host) and one scratch image.
+ *   rls_fft_apply        y = F x (adjoint 0) or y = F^H x (adjoint 1), the conjugate transpose: fftshift(ifftn(ifftshift(x))) sqrt(n) when
+ *                        unitary, unscaled otherwise.  y may be x (any other overlap is undefined).
+ *   rls_fft_variant      1: a transform is ONE single-workgroup launch, the image in that workgroup's LDS; 0: one launch per dimension.
+ *                        rls_tune_set("fft_fused", v): 1 (default) the former for images of up to 1024 points, 2 for every image that
+ *                        fits the LDS (16384 C32 / 8192 C64 points), 0 never.  Both give the same bits.
+ *   rls_fft_sampled_mul  op = RLS_OP_N: y = S F x (m outputs); RLS_OP_C: y = F^H S^H x (N outputs); RLS_OP_T: RLS_E_UNSUPPORTED.  The two
+ *                        handles must share context, element type and N = prod(shape).  x and y must not overlap.
+ *   rls_fft_sampled_mul_normal  v = F^H diag(mask) F p, the bits of the three steps done one by one: ONE launch on the single-workgroup
+ *                        path, four on the other (the mask rides in the store of the last forward pass).  v may be p. */
+typedef struct rls_sampling rls_sampling;
+typedef struct rls_fft rls_fft;
+enum { RLS_FFT_SHIFT = 1, RLS_FFT_UNITARY = 2 };
+int32_t rls_sampling_create(rls_ctx* ctx, int32_t dtype, int64_t N, int64_t m, const int32_t* idx_host, rls_sampling** out);
+int32_t rls_sampling_destroy(rls_sampling* s);
+int32_t rls_sampling_mul(rls_sampling* s, int32_t op, double alpha_re, double alpha_im, const void* x, double beta_re, double beta_im, void* y);
+int32_t rls_sampling_mul_normal(rls_sampling* s, const void* p, void* v);
+int32_t rls_fft_create(rls_ctx* ctx, int32_t dtype, int32_t ndims, const int64_t* shape, int32_t flags, rls_fft** out);
+int32_t rls_fft_destroy(rls_fft* f);
+int32_t rls_fft_apply(rls_fft* f, int32_t adjoint, const void* x, void* y);
+int32_t rls_fft_variant(rls_fft* f, int32_t* out);
+int32_t rls_fft_sampled_mul(rls_fft* f, rls_sampling* s, int32_t op, const void* x, void* y);
+int32_t rls_fft_sampled_mul_normal(rls_fft* f, rls_sampling* s, const void* p, void* v);
+
 /* ---------------------------------------------------------------------------------------------
  * operator handle: the backend's operator type for A (SURVEY 3.1 "two operator modes").
  * A' * A on it yields the lazy normal operator (matrix-free, two GEMVs) unless a Gram matrix is set.

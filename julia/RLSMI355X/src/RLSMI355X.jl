@@ -688,4 +688,83 @@ pinv_solve!(p::PinvPlan, x::RLSVector, b::RLSVector, lambda::Real; proj::Integer
 pinv_solve!(p::PinvPlan, X::RLSMatrix, B::RLSMatrix, lambda::Real; proj::Integer = 0) =
   (pinv_solve!(p, X.ptr, X.lda, B.ptr, B.lda, B.N, lambda; proj); X)
 
+# ---- matrix-free operators: SamplingOp, FFTOp and their product (csrc/fft.hip) ---------------------------------------------------
+"SamplingOp(T; pattern, shape): y = x[pattern]; `pattern` holds 1-based indices into the column-major image, as in Julia"
+mutable struct RLSSamplingOp{T}
+  handle::Ptr{Cvoid}
+  M::Int
+  N::Int
+  ctx::Context
+end
+function RLSSamplingOp(::Type{T}; pattern::AbstractVector{<:Integer}, shape, ctx = context()) where {T}
+  idx = Int32.(pattern .- 1)
+  h = Ref{Ptr{Cvoid}}(C_NULL)
+  check(ctx, ccall((:rls_sampling_create, librls[]), Int32, (Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Int32}, Ref{Ptr{Cvoid}}),
+                   ctx.handle, dtypecode(T), prod(shape), length(idx), idx, h), "rls_sampling_create")
+  S = RLSSamplingOp{T}(h[], length(idx), prod(shape), ctx)
+  finalizer(s -> ccall((:rls_sampling_destroy, librls[]), Int32, (Ptr{Cvoid},), s.handle), S)
+end
+"FFTOp(T; shape, shift = true, unitary = true) on 1-D and 2-D power-of-two shapes"
+mutable struct RLSFFTOp{T}
+  handle::Ptr{Cvoid}
+  N::Int
+  ctx::Context
+end
+function RLSFFTOp(::Type{T}; shape, shift::Bool = true, unitary::Bool = true, ctx = context()) where {T<:Complex}
+  sh = Int64[shape...]
+  h = Ref{Ptr{Cvoid}}(C_NULL)
+  check(ctx, ccall((:rls_fft_create, librls[]), Int32, (Ptr{Cvoid}, Int32, Int32, Ptr{Int64}, Int32, Ref{Ptr{Cvoid}}),
+                   ctx.handle, dtypecode(T), length(sh), sh, Int32(shift) | (Int32(unitary) << 1), h), "rls_fft_create")
+  F = RLSFFTOp{T}(h[], prod(sh), ctx)
+  finalizer(f -> ccall((:rls_fft_destroy, librls[]), Int32, (Ptr{Cvoid},), f.handle), F)
+end
+"ProdOp(SamplingOp, FFTOp)"
+struct RLSSampledFFTOp{T}
+  S::RLSSamplingOp{T}
+  F::RLSFFTOp{T}
+end
+Base.size(S::RLSSamplingOp) = (S.M, S.N)
+Base.size(F::RLSFFTOp) = (F.N, F.N)
+Base.size(P::RLSSampledFFTOp) = (P.S.M, P.F.N)
+"1: a transform is one single-workgroup launch, 0: one launch per dimension"
+function fft_variant(F::RLSFFTOp)
+  v = Ref{Int32}(0)
+  check(F.ctx, ccall((:rls_fft_variant, librls[]), Int32, (Ptr{Cvoid}, Ref{Int32}), F.handle, v), "rls_fft_variant")
+  Int(v[])
+end
+function sampling_mul!(op::Int32, S::RLSSamplingOp{T}, x::RLSVector{T}, y::RLSVector{T}, alpha::Number, beta::Number) where {T}
+  a, b = ComplexF64(alpha), ComplexF64(beta)
+  check(S.ctx, ccall((:rls_sampling_mul, librls[]), Int32, (Ptr{Cvoid}, Int32, Float64, Float64, Ptr{Cvoid}, Float64, Float64, Ptr{Cvoid}),
+                     S.handle, op, real(a), imag(a), x.ptr, real(b), imag(b), y.ptr), "rls_sampling_mul")
+  y
+end
+LinearAlgebra.mul!(y::RLSVector{T}, S::RLSSamplingOp{T}, x::RLSVector{T}, alpha::Number = 1, beta::Number = 0) where {T} =
+  sampling_mul!(RLS_OP_N, S, x, y, alpha, beta)
+LinearAlgebra.mul!(y::RLSVector{T}, S::Adjoint{<:Any, RLSSamplingOp{T}}, x::RLSVector{T}, alpha::Number = 1, beta::Number = 0) where {T} =
+  sampling_mul!(RLS_OP_C, parent(S), x, y, alpha, beta)
+"v = mask .* p"
+function sampling_mul_normal!(v::RLSVector{T}, S::RLSSamplingOp{T}, p::RLSVector{T}) where {T}
+  check(S.ctx, ccall((:rls_sampling_mul_normal, librls[]), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), S.handle, p.ptr, v.ptr), "rls_sampling_mul_normal")
+  v
+end
+function fft_apply!(y::RLSVector{T}, F::RLSFFTOp{T}, x::RLSVector{T}, adjoint::Bool) where {T}
+  check(F.ctx, ccall((:rls_fft_apply, librls[]), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}), F.handle, Int32(adjoint), x.ptr, y.ptr), "rls_fft_apply")
+  y
+end
+LinearAlgebra.mul!(y::RLSVector{T}, F::RLSFFTOp{T}, x::RLSVector{T}) where {T} = fft_apply!(y, F, x, false)
+LinearAlgebra.mul!(y::RLSVector{T}, F::Adjoint{<:Any, RLSFFTOp{T}}, x::RLSVector{T}) where {T} = fft_apply!(y, parent(F), x, true)
+function sampled_fft_mul!(op::Int32, P::RLSSampledFFTOp{T}, x::RLSVector{T}, y::RLSVector{T}) where {T}
+  check(P.F.ctx, ccall((:rls_fft_sampled_mul, librls[]), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}),
+                       P.F.handle, P.S.handle, op, x.ptr, y.ptr), "rls_fft_sampled_mul")
+  y
+end
+LinearAlgebra.mul!(y::RLSVector{T}, P::RLSSampledFFTOp{T}, x::RLSVector{T}) where {T} = sampled_fft_mul!(RLS_OP_N, P, x, y)
+LinearAlgebra.mul!(y::RLSVector{T}, P::Adjoint{<:Any, RLSSampledFFTOp{T}}, x::RLSVector{T}) where {T} = sampled_fft_mul!(RLS_OP_C, parent(P), x, y)
+"v = F' * (mask .* (F * p)): one launch where the image fits a workgroup's LDS"
+function sampled_fft_mul_normal!(v::RLSVector{T}, P::RLSSampledFFTOp{T}, p::RLSVector{T}) where {T}
+  check(P.F.ctx, ccall((:rls_fft_sampled_mul_normal, librls[]), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                       P.F.handle, P.S.handle, p.ptr, v.ptr), "rls_fft_sampled_mul_normal")
+  v
+end
+
 end # module

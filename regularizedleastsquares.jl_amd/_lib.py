@@ -18,6 +18,7 @@ OP_N, OP_T, OP_C = 0, 1, 2
 REG_NONE, REG_L1, REG_L2, REG_L21, REG_TV = 0, 1, 2, 3, 4
 REG_WAVELET = 5   # rls_fista_set_reg_wavelet only
 WT_HAAR, WT_DB2 = 0, 1
+FFT_SHIFT, FFT_UNITARY = 1, 2   # rls_fft_create flags
 PROJ_NONE, PROJ_REAL, PROJ_POSITIVE = 0, 1, 2
 
 
@@ -175,6 +176,17 @@ PROTOTYPES = {
     "rls_sparse_rownorm2": (_i32, [_vp, _vp]),
     "rls_sparse_to_dense": (_i32, [_vp, _vp, _i64]),
     "rls_sparse_kaczmarz_sweep": (_i32, [_vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _d, _i32]),
+    # ---- matrix-free operators: SamplingOp, FFTOp and their product (csrc/fft.hip) ----
+    "rls_sampling_create": (_i32, [_vp, _i32, _i64, _i64, _vp, _pvp]),
+    "rls_sampling_destroy": (_i32, [_vp]),
+    "rls_sampling_mul": (_i32, [_vp, _i32, _d, _d, _vp, _d, _d, _vp]),
+    "rls_sampling_mul_normal": (_i32, [_vp, _vp, _vp]),
+    "rls_fft_create": (_i32, [_vp, _i32, _i32, _pi64, _i32, _pvp]),
+    "rls_fft_destroy": (_i32, [_vp]),
+    "rls_fft_apply": (_i32, [_vp, _i32, _vp, _vp]),
+    "rls_fft_variant": (_i32, [_vp, _pi32]),
+    "rls_fft_sampled_mul": (_i32, [_vp, _vp, _i32, _vp, _vp]),
+    "rls_fft_sampled_mul_normal": (_i32, [_vp, _vp, _vp, _vp]),
     "rls_operator_create": (_i32, [_vp, _i32, _i64, _i64, _vp, _i64, _pvp]),
     "rls_operator_set_gram": (_i32, [_vp, _vp, _i64]),
     "rls_operator_destroy": (_i32, [_vp]),

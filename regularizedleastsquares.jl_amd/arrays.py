@@ -5,6 +5,8 @@
   DeviceVector  the vector type of b and of every solver state vector (`similar(b, n)`)
   DeviceMatrix  the operator type of A: column-major dense matrix; `A.H @ A`-style normal operators
                 are lazy (`NormalOperator`) so the unchanged constructors land in matrix-free mode
+  SamplingOp, FFTOp, ProdOp(SamplingOp, FFTOp)
+                matrix-free operators (csrc/fft.hip): no stored matrix, served by CGNR and FISTA
 """
 from __future__ import annotations
 
@@ -531,6 +533,7 @@ class SparseNormalOperator:
 
     handle = None   # no rls_operator: the device plans take dense operators only
     sparse = True
+    primitives = True   # CGNR and FISTA run their loops on the primitives (solvers._sparse_primitives)
     gram = None
 
     def __init__(self, A: DeviceSparseMatrix):
@@ -554,6 +557,222 @@ class SparseNormalOperator:
         return self.mul_normal_(v, p)
 
 
+class _MatrixFreeOperator:
+    """What SamplingOp, FFTOp and their product share: the operator protocol (size, mul_, mul_adj_, normal_operator) and what the
+    primitive loops of CGNR and FISTA read from an operator object -- M, N, code, double, dtype, ctx, mul_normal_ -- with no plan
+    handle and no Gram matrix: the device plans take dense operators only."""
+
+    handle = None       # no rls_operator
+    gram = None
+    primitives = True   # CGNR and FISTA run their loops on the primitives (solvers._sparse_primitives)
+    matrix_free = True
+
+    @property
+    def shape(self):
+        return (self.M, self.N)
+
+    def size(self, i: int) -> int:  # 1-based like Julia's size(A, i)
+        return (self.M, self.N)[i - 1]
+
+    def _check(self, out: DeviceVector, n_out: int, inp: DeviceVector, n_in: int):
+        if inp.n != n_in or out.n != n_out:
+            raise ValueError(f"mul: dimension mismatch: the operator is {self.M}x{self.N}, input {inp.n}, output {out.n}")
+        if inp.dtype != self.dtype or out.dtype != self.dtype:
+            raise TypeError(f"mul: element types differ: operator {self.dtype}, input {inp.dtype}, output {out.dtype}")
+
+    def __matmul__(self, x: DeviceVector) -> DeviceVector:
+        return self.mul_(DeviceVector(self.M, self.dtype, self.ctx), x)
+
+    def normal_operator(self) -> "MatrixFreeNormalOperator":
+        """A' * A, lazy: one call of the operator's own normal product per apply"""
+        return MatrixFreeNormalOperator(self)
+
+
+def _sampling_pattern(pattern, n: int) -> np.ndarray:
+    """the 0-based sampling indices as a contiguous int32 array: every one inside [0, n), none twice (ValueError otherwise)"""
+    if isinstance(pattern, DeviceVector):
+        raise TypeError("SamplingOp: the pattern is a host array of integers (device vectors hold the four floating-point element types)")
+    idx = np.asarray(pattern)
+    if idx.ndim != 1 or idx.size < 1 or idx.dtype.kind not in "iu":
+        raise ValueError("SamplingOp: pattern is a non-empty 1-D array of 0-based integer indices")
+    if idx.min() < 0 or idx.max() >= n:
+        raise ValueError(f"SamplingOp: an index lies outside [0, {n})")
+    if np.unique(idx).size != idx.size:
+        raise ValueError("SamplingOp: an index is repeated")
+    return np.ascontiguousarray(idx, dtype=np.int32)
+
+
+class SamplingOp(_MatrixFreeOperator):
+    """LinearOperatorCollection.SamplingOp(T; pattern, shape) (docs/src/literate/examples/compressed_sensing.jl): y = x[pattern], size
+    (len(pattern), prod(shape)).  `pattern` holds 0-based indices into the column-major image."""
+
+    def __init__(self, dtype, pattern, shape, ctx: Optional[Context] = None):
+        self.dtype = np.dtype(dtype)
+        self.code = dtype_code(self.dtype)
+        self.double = is_double(self.code)
+        self.image_shape = tuple(int(s_) for s_ in np.atleast_1d(shape))
+        if not self.image_shape or min(self.image_shape) < 1:
+            raise ValueError("SamplingOp: shape must hold positive extents")
+        self.N = int(np.prod(self.image_shape))
+        if self.N >= 2 ** 31:
+            raise ValueError("SamplingOp: prod(shape) must be below 2^31")
+        idx = _sampling_pattern(pattern, self.N)   # (on the host, ahead of any context)
+        self.M = int(idx.size)
+        self.ctx = ctx or default_context()
+        h = C.c_void_p()
+        check(self.ctx.handle, self.ctx.lib.rls_sampling_create(self.ctx.handle, self.code, self.N, self.M, idx.ctypes.data, C.byref(h)),
+              "rls_sampling_create")
+        self._h = h
+
+    def _mul(self, op: int, x: DeviceVector, y: DeviceVector, alpha, beta):
+        alpha, beta = complex(alpha), complex(beta)
+        check(self.ctx.handle, self.ctx.lib.rls_sampling_mul(self._h, op, alpha.real, alpha.imag, x.ptr, beta.real, beta.imag, y.ptr),
+              "rls_sampling_mul")
+        return y
+
+    def mul_(self, y: DeviceVector, x: DeviceVector, alpha=1.0, beta=0.0):
+        self._check(y, self.M, x, self.N)
+        return self._mul(OP_N, x, y, alpha, beta)
+
+    def mul_adj_(self, x: DeviceVector, y: DeviceVector, alpha=1.0, beta=0.0):
+        self._check(x, self.N, y, self.M)
+        return self._mul(OP_C, y, x, alpha, beta)
+
+    def mul_transpose_(self, x: DeviceVector, y: DeviceVector, alpha=1.0, beta=0.0):
+        self._check(x, self.N, y, self.M)
+        return self._mul(OP_T, y, x, alpha, beta)
+
+    def mul_normal_(self, v: DeviceVector, p: DeviceVector):
+        """v = mask .* p"""
+        self._check(v, self.N, p, self.N)
+        check(self.ctx.handle, self.ctx.lib.rls_sampling_mul_normal(self._h, p.ptr, v.ptr), "rls_sampling_mul_normal")
+        return v
+
+    def __del__(self):
+        try:
+            if self._h and self.ctx.handle:
+                self.ctx.lib.rls_sampling_destroy(self._h)
+        except Exception:
+            pass
+        self._h = None
+
+
+class FFTOp(_MatrixFreeOperator):
+    """LinearOperatorCollection.FFTOp(T; shape, shift = true, unitary = true) on 1-D and 2-D power-of-two shapes: with the image
+    column-major, F x = fftshift(fftn(ifftshift(x))) / sqrt(n); `shift=False` drops the two shifts, `unitary=False` the scale.  The
+    adjoint is the conjugate transpose."""
+
+    def __init__(self, dtype, shape, shift: bool = True, unitary: bool = True, ctx: Optional[Context] = None):
+        self.dtype = np.dtype(dtype)
+        self.code = dtype_code(self.dtype)
+        if self.dtype.kind != "c":
+            raise TypeError(f"FFTOp: a complex element type is required, got {self.dtype}")
+        self.double = is_double(self.code)
+        self.image_shape = tuple(int(s_) for s_ in np.atleast_1d(shape))
+        if not self.image_shape or min(self.image_shape) < 1:
+            raise ValueError("FFTOp: shape must hold positive extents")
+        ext = [s_ for s_ in self.image_shape if s_ != 1]
+        if len(ext) > 2:
+            raise ValueError("FFTOp: 1-D and 2-D shapes only")
+        if any(s_ & (s_ - 1) for s_ in ext):
+            raise ValueError(f"FFTOp: extents must be powers of two, got {self.image_shape}")
+        self.shift, self.unitary = bool(shift), bool(unitary)
+        self.M = self.N = int(np.prod(self.image_shape))
+        self.ctx = ctx or default_context()
+        cs = (C.c_int64 * len(self.image_shape))(*self.image_shape)
+        h = C.c_void_p()
+        flags = (_lib.FFT_SHIFT if self.shift else 0) | (_lib.FFT_UNITARY if self.unitary else 0)
+        st = self.ctx.lib.rls_fft_create(self.ctx.handle, self.code, len(self.image_shape), cs, flags, C.byref(h))
+        if st == -2:   # RLS_E_UNSUPPORTED: a line longer than the kernels' LDS holds
+            raise ValueError(f"FFTOp: shape {self.image_shape} is not supported: " + (self.ctx.lib.rls_last_error_string(self.ctx.handle) or b"").decode())
+        check(self.ctx.handle, st, "rls_fft_create")
+        self._h = h
+        self._t = None
+
+    def variant(self) -> int:
+        """1: a transform is one single-workgroup launch, 0: one launch per dimension (rls_fft_variant)"""
+        v = C.c_int32()
+        check(self.ctx.handle, self.ctx.lib.rls_fft_variant(self._h, C.byref(v)), "rls_fft_variant")
+        return v.value
+
+    def mul_(self, y: DeviceVector, x: DeviceVector):
+        self._check(y, self.N, x, self.N)
+        check(self.ctx.handle, self.ctx.lib.rls_fft_apply(self._h, 0, x.ptr, y.ptr), "rls_fft_apply")
+        return y
+
+    def mul_adj_(self, x: DeviceVector, y: DeviceVector):
+        self._check(x, self.N, y, self.N)
+        check(self.ctx.handle, self.ctx.lib.rls_fft_apply(self._h, 1, y.ptr, x.ptr), "rls_fft_apply")
+        return x
+
+    def mul_normal_(self, v: DeviceVector, p: DeviceVector):
+        """v = F^H (F p): the forward into v, the adjoint in place"""
+        self.mul_(v, p)
+        return self.mul_adj_(v, v)
+
+    def __del__(self):
+        try:
+            if self._h and self.ctx.handle:
+                self.ctx.lib.rls_fft_destroy(self._h)
+        except Exception:
+            pass
+        self._h = None
+
+
+class SampledFFTOp(_MatrixFreeOperator):
+    """ProdOp(SamplingOp, FFTOp): y = S (F x), the operator of the reference's compressed-sensing example behind a Fourier transform
+    (rls_fft_sampled_mul); its normal operator F^H diag(mask) F is one launch where the image fits a workgroup's LDS."""
+
+    def __init__(self, S: SamplingOp, F: FFTOp):
+        if S.ctx is not F.ctx or S.dtype != F.dtype or S.N != F.N:
+            raise ValueError(f"ProdOp: SamplingOp ({S.M}x{S.N}, {S.dtype}) and FFTOp ({F.M}x{F.N}, {F.dtype}) must share context, element type "
+                             "and prod(shape)")
+        self.S, self.F = S, F
+        self.dtype, self.code, self.double, self.ctx = F.dtype, F.code, F.double, F.ctx
+        self.M, self.N = S.M, F.N
+        self.image_shape = F.image_shape
+
+    def mul_(self, y: DeviceVector, x: DeviceVector):
+        self._check(y, self.M, x, self.N)
+        check(self.ctx.handle, self.ctx.lib.rls_fft_sampled_mul(self.F._h, self.S._h, OP_N, x.ptr, y.ptr), "rls_fft_sampled_mul")
+        return y
+
+    def mul_adj_(self, x: DeviceVector, y: DeviceVector):
+        self._check(x, self.N, y, self.M)
+        check(self.ctx.handle, self.ctx.lib.rls_fft_sampled_mul(self.F._h, self.S._h, OP_C, y.ptr, x.ptr), "rls_fft_sampled_mul")
+        return x
+
+    def mul_normal_(self, v: DeviceVector, p: DeviceVector):
+        self._check(v, self.N, p, self.N)
+        check(self.ctx.handle, self.ctx.lib.rls_fft_sampled_mul_normal(self.F._h, self.S._h, p.ptr, v.ptr), "rls_fft_sampled_mul_normal")
+        return v
+
+
+class MatrixFreeNormalOperator:
+    """Lazy A^H A of a SamplingOp, an FFTOp or their product: size N x N, eltype of A; mul_ is the operator's own normal product.
+    Like SparseNormalOperator it is the operator object the primitive loops of CGNR and FISTA run on."""
+
+    handle = None
+    gram = None
+    primitives = True
+    matrix_free = True
+
+    def __init__(self, A: _MatrixFreeOperator):
+        self.A = A
+        self.dtype, self.code, self.double, self.ctx = A.dtype, A.code, A.double, A.ctx
+        self.M, self.N = A.M, A.N
+        self.shape = (A.N, A.N)
+
+    def size(self, i: int) -> int:
+        return self.A.N
+
+    def mul_normal_(self, v: DeviceVector, p: DeviceVector):
+        return self.A.mul_normal_(v, p)
+
+    def mul_(self, v: DeviceVector, p: DeviceVector):
+        return self.A.mul_normal_(v, p)
+
+
 class WeightingOp:
     """LinearOperatorCollection.WeightingOp(weights): diag(weights) (docs/src/literate/howto/normal_operator.jl:41)"""
 
@@ -561,13 +780,17 @@ class WeightingOp:
         self.weights = weights
 
 
-def ProdOp(W: WeightingOp, A: DeviceMatrix) -> DeviceMatrix:
-    """ProdOp(WeightingOp(w), A) (docs/src/literate/howto/normal_operator.jl:42, src/Utils.jl:23,102).  On a GPU with
+def ProdOp(W, A):
+    """ProdOp(SamplingOp, FFTOp): the matrix-free product S o F (SampledFFTOp).
+
+    ProdOp(WeightingOp(w), A) (docs/src/literate/howto/normal_operator.jl:42, src/Utils.jl:23,102).  On a GPU with
     288 GB the weighted operator is materialised once as diag(w) A: A, its adjoint and the normal operator
     A^H W^H W A (`normalOperator`) then run on the same one-pass / matrix-core kernels as any dense matrix,
     instead of carrying a diagonal scale through every kernel."""
-    if not isinstance(W, WeightingOp):
-        raise TypeError("ProdOp: only ProdOp(WeightingOp(w), A) is supported")
+    if isinstance(W, SamplingOp) and isinstance(A, FFTOp):
+        return SampledFFTOp(W, A)
+    if not isinstance(W, WeightingOp) or isinstance(A, _MatrixFreeOperator):
+        raise TypeError("ProdOp: only ProdOp(WeightingOp(w), A) with a dense A and ProdOp(SamplingOp, FFTOp) are supported")
     if isinstance(A, DeviceSparseMatrix):
         raise TypeError("ProdOp: a sparse A is not supported (ProdOp(WeightingOp(w), A.to_dense()) is the dense route)")
     w = W.weights

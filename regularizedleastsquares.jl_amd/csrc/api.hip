@@ -331,6 +331,7 @@ int32_t rls_tune_set(rls_ctx* ctx, const char* key, int32_t value) {
   else if (!strcmp(key, "pinv_block_tol")) ctx->tune.pinv_block_tol = value < 0 ? 0 : (value > 7 ? 7 : value);
   else if (!strcmp(key, "pinv_block_cap")) ctx->tune.pinv_block_cap = value < 0 ? 0 : (value > 40 ? 40 : value);
   else if (!strcmp(key, "wavelet_fused")) ctx->tune.wavelet_fused = value ? 1 : 0;
+  else if (!strcmp(key, "fft_fused")) ctx->tune.fft_fused = value < 0 ? 0 : (value > 2 ? 2 : value);
   else if (!strcmp(key, "sparse_lanes")) {
     if (value != 0 && value != 1 && value != 4 && value != 16 && value != 64)
       return rls_fail(ctx, RLS_E_INVALID, "tune_set: sparse_lanes is 0 (automatic), 1, 4, 16 or 64");

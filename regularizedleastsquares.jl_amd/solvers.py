@@ -23,8 +23,8 @@ from . import _lib
 from ._lib import (PROJ_NONE, PROJ_POSITIVE, PROJ_REAL, REG_L1, REG_L2, REG_L21, REG_NONE, REG_TV, REG_WAVELET, AdmmParams,
                    AdmmStatus, CgnrStatus, CgnrStatusD, CgStatus,
                    FistaStatus, FistaStatusD, PgmStatus, check)
-from .arrays import (DeviceMatrix, DeviceSparseMatrix, DeviceVector, NormalOperator, OperatorHandle, SparseNormalOperator,
-                     is_double)
+from .arrays import (DeviceMatrix, DeviceSparseMatrix, DeviceVector, MatrixFreeNormalOperator, NormalOperator, OperatorHandle,
+                     SparseNormalOperator, is_double)
 from .regularization import (AbstractParameterizedRegularization, AbstractProjectionRegularization, GradientOp,
                              L1Regularization, L2Regularization, findsink, findsinks, is_projection, sink,
                              L21Regularization, MeasurementBasedNormalization, NoNormalization, PositiveRegularization,
@@ -71,9 +71,30 @@ def _resolve_sparse_operator(A, AHA):
     raise TypeError("with a sparse A, AHA must be None, A.normal_operator() or a dense Gram DeviceMatrix (e.g. A.to_dense().gram())")
 
 
+_MATRIX_FREE_SERVED = ("matrix-free operators (SamplingOp, FFTOp, ProdOp(SamplingOp, FFTOp)) are served by CGNR and FISTA on their lazy "
+                       "normal operator; no other solver, no multi-GPU class and no explicit Gram matrix (AHA = DeviceMatrix) takes them")
+
+
+def _resolve_matrix_free_operator(A, AHA):
+    """the matrix-free branch of _resolve_operator: (A, A's lazy normal operator) -- the operator object of the primitive loops"""
+    if A is None:
+        A = AHA.A
+    if not getattr(A, "matrix_free", False):
+        raise TypeError("AHA is the normal operator of a matrix-free operator: A must be that operator (or None)")
+    if AHA is None:
+        return A, A.normal_operator()
+    if isinstance(AHA, MatrixFreeNormalOperator) and AHA.A is A:
+        return A, AHA
+    raise TypeError(_MATRIX_FREE_SERVED)
+
+
 def _resolve_operator(A, AHA, sparse_ok=False):
     """Returns (A: DeviceMatrix|None, OperatorHandle).  AHA=None means the constructor default
     `A' * A`, which for this backend's operator type is the lazy normal operator (matrix-free)."""
+    if getattr(A, "matrix_free", False) or isinstance(AHA, MatrixFreeNormalOperator):
+        if not sparse_ok:   # (the solvers that take sparse operators on the primitives take these: CGNR and FISTA)
+            raise TypeError(_MATRIX_FREE_SERVED)
+        return _resolve_matrix_free_operator(A, AHA)
     if isinstance(A, DeviceSparseMatrix) or isinstance(AHA, SparseNormalOperator):
         if not sparse_ok:
             raise TypeError(_SPARSE_SERVED)
@@ -98,8 +119,9 @@ def _resolve_operator(A, AHA, sparse_ok=False):
 
 
 def _sparse_primitives(op) -> bool:
-    """the operator is a sparse A on its lazy normal operator: no device plan, CGNR and FISTA run their loops on the primitives"""
-    return getattr(op, "sparse", False)
+    """the operator is a sparse or a matrix-free A on its lazy normal operator (SparseNormalOperator, MatrixFreeNormalOperator): no
+    device plan, CGNR and FISTA run their loops on the primitives"""
+    return getattr(op, "primitives", False)
 
 
 def _take_sparse_gram(solver):
@@ -2206,6 +2228,8 @@ class Kaczmarz(AbstractRowActionSolver):
     def __init__(self, A=None, *, reg=None, normalizeReg=None, randomized: bool = False, subMatrixFraction=0.15,
                  shuffleRows: bool = False, seed: int = 1234, iterations: int = 10, greedy_randomized: bool = False,
                  theta=None):
+        if getattr(A, "matrix_free", False):
+            raise TypeError(_MATRIX_FREE_SERVED)
         if not isinstance(A, (DeviceMatrix, DeviceSparseMatrix)):
             raise TypeError("A must be a DeviceMatrix or a DeviceSparseMatrix (the backend is selected by the array type, as in the reference)")
         self._sparse = isinstance(A, DeviceSparseMatrix)
