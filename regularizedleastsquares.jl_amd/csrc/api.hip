@@ -285,7 +285,7 @@ int32_t rls_tune_set(rls_ctx* ctx, const char* key, int32_t value) {
   else if (!strcmp(key, "pipe_hint_mode")) ctx->tune.pipe_hint_mode = value;
   else if (!strcmp(key, "resident")) {
     ctx->tune.resident = value;
-    ctx->resident_failures = 0;  // an explicit switch also forgets earlier timeouts (solvers.hip, resident_lost)
+    ctx->resident_failures = 0;  // an explicit switch also forgets earlier timeouts (plans.hpp, resident_slot::lost)
   }
   else if (!strcmp(key, "status_mailbox")) ctx->tune.status_mailbox = value;
   else if (!strcmp(key, "small")) ctx->tune.small = value;

@@ -2,7 +2,7 @@
 // -fsanitize=thread / -fsanitize=address (tests/host_concurrency.cpp, run by tests/test_host_concurrency.py):
 //   * the per-rank worker pool of the row-sharded solver loops and its sense-reversing spin barrier (comm.hip);
 //   * the process-wide free list of small pinned host blocks (api.hip);
-//   * the bookkeeping of the resident-launch chain (solvers.hip): which stream issued the last resident kernel of a device.
+//   * the bookkeeping of the resident-launch chain (operator.hip): which stream issued the last resident kernel of a device.
 // The device layer enters only through callables (what a phase enqueues, how a pinned block is obtained, what to do when
 // the chain changes streams).
 #pragma once
@@ -212,7 +212,7 @@ static inline void resident_chain_forget(std::mutex& mu, resident_chain_state& s
 }
 
 // ---- lost resident launches ------------------------------------------------------------------------------------------------------
-// What a plan (and its context) remembers about resident launches that gave up (solvers.hip, resident_slot): the plan stays off
+// What a plan (and its context) remembers about resident launches that gave up (plans.hpp, resident_slot): the plan stays off
 // the resident kernels from its first lost launch on, and a context that has met losses twice stops using them at all -- whatever
 // keeps a grid from being resident (another process on the device, a long kernel on another stream) would cost every later
 // attempt its full wait bound.

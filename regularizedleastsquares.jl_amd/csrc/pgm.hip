@@ -212,7 +212,7 @@ __global__ __launch_bounds__(PGM_THREADS) void pogm_auto_kernel(E* __restrict__ 
 
 // ---------------------------------------------------------------------------------------------
 // Batched OptISTA / POGM: K right-hand sides share one pass over A per product (skinny.hip); these kernels are the
-// per-column halves, workgroup b = column b (the plan: solvers.hip, rls_pgm_create_batched).  AHA x arrives as `S`
+// per-column halves, workgroup b = column b (the plan: plan_pgm.hip, rls_pgm_create_batched).  AHA x arrives as `S`
 // partial rows per column and is summed here in fixed order; the next gradient point also goes into the operand
 // panel.  Every column carries its own iteration count: the coefficient row and (POGM) the roles of the two x / y
 // buffers follow it, so columns that retire at different iterations need nothing from the host.

@@ -1,4 +1,4 @@
-// The one owner of a solver plan's device and pinned-host blocks (solvers.hip, plans_f64.hip).  Free of any device API, as
+// The one owner of a solver plan's device and pinned-host blocks (plans.hpp and the files that include it, plans_f64.hip).  Free of any device API, as
 // host_pool.hpp is, so that it also compiles with plain g++ under -fsanitize=address,undefined (tests/plan_buffers.cpp, run by
 // tests/test_plan_buffers.py): the device layer enters only through the five callables it is constructed with.
 //

@@ -140,7 +140,7 @@ __device__ static inline bool group_arrive_wait(unsigned* word, unsigned target,
 constexpr unsigned RLS_SRV_MAX_COMMANDS = 2048u;
 // the head of the control block {command sequence, n_steps, mailbox sequence, -} in ONE 16-byte read at system scope: the block lives
 // in pinned host memory, every read of it is a round trip over the link (1.5-2 us), and the three words used to be three dependent
-// reads.  The host writes the payload, a release fence, then the sequence word (server_command, solvers.hip): a read that shows the new
+// reads.  The host writes the payload, a release fence, then the sequence word (server_command, plans.hpp): a read that shows the new
 // sequence shows the payload of that command (the 16 bytes are one aligned piece of one cache line).
 struct srv_head {
   unsigned seq, n, mbseq, pad;

@@ -71,7 +71,7 @@ struct rls_tuning {
   int sparse_kaczmarz_lds = 1; // sparse.hip: 1 = the sparse row sweep keeps x in the workgroup's LDS where it fits; 0: always in global memory
   int resident_spin = 100000;  // bound of every in-kernel wait, in polls (~1 us each: a wall-clock bound of ~0.1 s per
                                // wait); a launch that runs into it is a no-op and the host re-runs its iterations on the
-                               // per-iteration pipeline (solvers.hip, *_recover)
+                               // per-iteration pipeline (plans.hpp, status_recover)
 };
 
 constexpr int RLS_FETCH_MAX = 24;  // blocks one publishing kernel moves (the statuses of a group of small problems: rls_cgnr_get_status_group)
@@ -90,7 +90,7 @@ struct rls_ctx {
   rls_tuning tune;
   uint64_t syncs = 0;         // host waits for the stream (rls_ctx_sync, rls_timer_stop_ms): queue mode starts on a plan's second
                               // resident step call between two of them (solvers.hip, cgnr_use_queue)
-  uint64_t tune_epoch = 0;    // bumped by every rls_tune_set: a cached hipGraph captured under other settings is dropped (solvers.hip, run_steps)
+  uint64_t tune_epoch = 0;    // bumped by every rls_tune_set: a cached hipGraph captured under other settings is dropped (plans.hpp, run_steps)
   int cus = 0;                // compute units of `device` (looked up once, by whoever asks first on this context)
   int resident_failures = 0;  // resident launches of this context that timed out; at 2 the context stops using them
   bool pools = false;         // device memory comes from the device's stream-ordered pool (rls_dev_alloc)
@@ -234,7 +234,7 @@ static inline hipError_t rls_event_wait(hipEvent_t ev) {
 // process is capturing, hipStreamWaitEvent from another thread on an event recorded outside that capture can fail
 // with hipErrorStreamCaptureIsolation (seen with one context capturing a FISTA graph while another chained a
 // resident launch: 1 run in 6); both sections are short and host-only, so serialising them costs nothing measurable.
-void rls_resident_forget(int device, hipStream_t stream);  // solvers.hip: a stream is going away (resident launch chain)
+void rls_resident_forget(int device, hipStream_t stream);  // operator.hip: a stream is going away (resident launch chain)
 inline std::mutex& rls_capture_mutex() {
   static std::mutex m;
   return m;
@@ -1023,7 +1023,7 @@ struct rls_operands {
   int half = 0;
 };
 
-// ---- batched OptISTA / POGM (K right-hand sides sharing A): kernels in pgm.hip, plan in solvers.hip ----------------------
+// ---- batched OptISTA / POGM (K right-hand sides sharing A): kernels in pgm.hip, plan in plan_pgm.hip ----------------------
 // one column's scalar record
 struct pgmb_scalars {
   double norm_x0;                          // ||A^H b||
@@ -1223,7 +1223,7 @@ void rls_fgramk_sizes(int64_t N, size_t* yx_bytes, size_t* xx_bytes, size_t* dot
 bool rls_fgramk_resident_ok(rls_ctx* ctx, int32_t dtype, int64_t N, int nrhs, const void* G, int64_t ldg);
 int32_t rls_fgramk_resident_launch(rls_ctx* ctx, const rls_fgramk& D, void* sync, int n_steps, unsigned spin_limit);
 
-// ---- DirectSolver (direct.hip): blocked Cholesky of G + lambda I and the triangular solves; plan in solvers.hip -------------
+// ---- DirectSolver (direct.hip): blocked Cholesky of G + lambda I and the triangular solves; plan in plan_direct.hip -------------
 // The factor is a padded square matrix of rls_direct_padded(N)^2 elements (64 x 64 blocks, identity in the padding) with the
 // factored diagonal blocks in NB tiles of 64 x 64 behind it (rls_direct_factor_elems(N) elements in all); `info` is
 // the plan's device word: 0, or the 1-based column of the first pivot that was not strictly positive and finite -- every
@@ -1236,7 +1236,7 @@ int32_t rls_direct_launch_factor(rls_ctx* ctx, int32_t dtype, int64_t N, const v
 int32_t rls_direct_launch_solve(rls_ctx* ctx, int32_t dtype, int64_t N, const void* W, int K, void* X, int64_t ldx, void* Y, int proj,
                                 const int* info);
 
-// ---- PseudoInverse (pinv.hip): one-sided Jacobi SVD A = W V^H and the two products of a solve; plan in solvers.hip ----------
+// ---- PseudoInverse (pinv.hip): one-sided Jacobi SVD A = W V^H and the two products of a solve; plan in plan_direct.hip ----------
 // W: rls_pinv_padded(dtype, M) x N, V: rls_pinv_padded(dtype, N) x N (leading dimensions padded to 16 bytes, padding rows zero);
 // stats: N + 1 floats, sigma_j^2 and behind them |A|_F^2; rotated: the plan's sweep word (a workgroup that rotated stores 1).
 int64_t rls_pinv_padded(int32_t dtype, int64_t n);
@@ -1259,7 +1259,7 @@ int32_t rls_pinv_launch_block_sweep(rls_ctx* ctx, int32_t dtype, int64_t M, int6
                                     void* scratch, int* rotated, int* rounds);
 
 // ---------------------------------------------------------------------------------------------
-// comm.hip internals used by the row-sharded solver loops (solvers.hip)
+// comm.hip internals used by the row-sharded solver loops (solvers.hip, plan_fista.hip)
 // ---------------------------------------------------------------------------------------------
 #include "host_pool.hpp"  // rls_comm_phase, the worker pool, the pinned cache, the resident-chain bookkeeping (device-free)
 int32_t rls_comm_run(rls_comm* c, const std::vector<rls_comm_phase>& phases, int reps);

@@ -274,7 +274,7 @@ struct rls_wavelet {
   int32_t J = 0, flen = 4;
   double h[4] = {0, 0, 0, 0}, g[4] = {0, 0, 0, 0};
   void* tmp = nullptr;  // the general path's scratch image
-  uint64_t serial = 0;  // unique per handle of this process: what a plan that caches launches of this handle compares (solvers.hip)
+  uint64_t serial = 0;  // unique per handle of this process: what a plan that caches launches of this handle compares (plan_fista.hip)
 };
 
 namespace {
@@ -364,7 +364,7 @@ static bool wv_live(const rls_wavelet* w) { return w && rls_ctx_alive(w->ctx, w-
 
 }  // namespace
 
-// ---- what the FISTA plan (solvers.hip) needs of a handle
+// ---- what the FISTA plan (plan_fista.hip) needs of a handle
 bool rls_wavelet_single_ok(const rls_wavelet* w, const rls_ctx* ctx, int32_t dtype, int64_t n) {
   return wv_live(w) && w->ctx == ctx && w->dtype == dtype && w->n1 * w->n2 == n && wv_use_fused(w);
 }
