@@ -250,14 +250,17 @@ __device__ static inline bool fft_neg(int k, int lgn, bool global_side) { return
 
 // ---- general path: one dimension of the image per launch.  DIM1 = false: bundles of 2^lgb contiguous lines along dimension 0;
 // DIM1 = true: bundles of 2^lgb neighbouring lines along dimension 1 (a strided load, 2^lgb consecutive elements per stride).
+// The shift signs of BOTH dimensions go into the load of the transform's `first` pass and into the store of its `last`, where the
+// single-workgroup kernel has them: a sign moved across a pass changes the sign of the exact zeros that cancellation leaves
+// (x - x = +0 whatever the sign in front), and the two paths are to give the same bits.
 // scale multiplies in the store when `last`; mask_at 1: the load is multiplied by the mask, 2: the store (behind the scale).
 template <typename E, bool INV, bool DIM1>
 __global__ __launch_bounds__(FFT_THREADS) void fft_pass_kernel(const E* src, E* dst, int lg1, int lg2, int lgb, const E* __restrict__ tw, int lgtw,
-                                                               int shift, int last, typename mfe<E>::R scale,
+                                                               int shift, int first, int last, typename mfe<E>::R scale,
                                                                const typename mfe<E>::R* __restrict__ mask, int mask_at) {
   extern __shared__ __align__(16) unsigned char fft_smem[];
   E* s = reinterpret_cast<E*>(fft_smem);
-  const int lgn = DIM1 ? lg2 : lg1, n = 1 << lgn, B = 1 << lgb;
+  const int lgn = DIM1 ? lg2 : lg1, lgo = DIM1 ? lg1 : lg2, n = 1 << lgn, B = 1 << lgb;
   const int nb = 1 << ((DIM1 ? lg1 : lg2) - lgb), cnt = 1 << (lgn + lgb);
   for (int bundle = blockIdx.x; bundle < nb; bundle += gridDim.x) {
     for (int idx = threadIdx.x; idx < cnt; idx += blockDim.x) {
@@ -274,7 +277,7 @@ __global__ __launch_bounds__(FFT_THREADS) void fft_pass_kernel(const E* src, E* 
       }
       E v = src[g];
       if (mask_at == 1) v = mfe<E>::rmul(v, mask[g]);
-      if (shift && fft_neg(k, lgn, INV)) v = mfe<E>::neg(v);
+      if (shift && first && (fft_neg(k, lgn, INV) != fft_neg(bundle * B + l, lgo, INV))) v = mfe<E>::neg(v);
       s[pos] = v;
     }
     __syncthreads();
@@ -292,7 +295,7 @@ __global__ __launch_bounds__(FFT_THREADS) void fft_pass_kernel(const E* src, E* 
         pos = (l << lgn) + (INV ? k : fft_rev(k, lgn));
       }
       E v = s[pos];
-      if (shift && fft_neg(k, lgn, !INV)) v = mfe<E>::neg(v);
+      if (shift && last && (fft_neg(k, lgn, !INV) != fft_neg(bundle * B + l, lgo, !INV))) v = mfe<E>::neg(v);
       if (last) v = mfe<E>::rmul(v, scale);
       if (mask_at == 2) v = mfe<E>::rmul(v, mask[g]);
       dst[g] = v;
@@ -406,7 +409,7 @@ static int32_t fft_fused_launch(rls_fft* f, const void* x, void* y, int mode, co
 }
 
 // one dimension on the general path
-static int32_t fft_pass(rls_fft* f, bool inv, bool dim1, const void* src, void* dst, bool last, const void* mask, int mask_at) {
+static int32_t fft_pass(rls_fft* f, bool inv, bool dim1, const void* src, void* dst, bool first, bool last, const void* mask, int mask_at) {
   rls_ctx* ctx = f->ctx;
   const int lgn = dim1 ? f->lg2 : f->lg1, lgo = dim1 ? f->lg1 : f->lg2;
   return fft_dispatch(f->dtype, [&](auto t) -> int32_t {
@@ -428,7 +431,7 @@ static int32_t fft_pass(rls_fft* f, bool inv, bool dim1, const void* src, void* 
         const hipError_t e = rls_allow_lds<fft_pass_kernel<E, INV, DIM1>>(ctx->device, FFT_LINE_LDS);
         if (e != hipSuccess) return rls_fail(ctx, (int32_t)e, "hipFuncSetAttribute (dynamic LDS) failed");
         hipLaunchKernelGGL((fft_pass_kernel<E, INV, DIM1>), dim3(grid), dim3(nt), cnt * sizeof(E), ctx->stream, (const E*)src, (E*)dst, f->lg1,
-                           f->lg2, lgb, (const E*)f->tw, f->lgmax - lgn, f->shift, last ? 1 : 0, (R)fft_scale(f), (const R*)mask, mask_at);
+                           f->lg2, lgb, (const E*)f->tw, f->lgmax - lgn, f->shift, first ? 1 : 0, last ? 1 : 0, (R)fft_scale(f), (const R*)mask, mask_at);
         return launch_status(ctx);
       });
     });
@@ -440,11 +443,11 @@ static int32_t fft_pass(rls_fft* f, bool inv, bool dim1, const void* src, void* 
 static int32_t fft_general(rls_fft* f, bool adjoint, const void* x, void* y, const void* mask) {
   const bool img = f->lg2 > 0;
   if (!adjoint) {
-    RLS_TRY(fft_pass(f, false, false, x, y, !img, img ? nullptr : mask, !img && mask ? 2 : 0));
-    if (img) RLS_TRY(fft_pass(f, false, true, y, y, true, mask, mask ? 2 : 0));
+    RLS_TRY(fft_pass(f, false, false, x, y, true, !img, img ? nullptr : mask, !img && mask ? 2 : 0));
+    if (img) RLS_TRY(fft_pass(f, false, true, y, y, false, true, mask, mask ? 2 : 0));
   } else {
-    if (img) RLS_TRY(fft_pass(f, true, true, x, y, false, mask, mask ? 1 : 0));
-    RLS_TRY(fft_pass(f, true, false, img ? y : x, y, true, img ? nullptr : mask, !img && mask ? 1 : 0));
+    if (img) RLS_TRY(fft_pass(f, true, true, x, y, true, false, mask, mask ? 1 : 0));
+    RLS_TRY(fft_pass(f, true, false, img ? y : x, y, !img, true, img ? nullptr : mask, !img && mask ? 1 : 0));
   }
   return 0;
 }
