@@ -319,6 +319,41 @@ int32_t rls_fft_variant(rls_fft* f, int32_t* out);
 int32_t rls_fft_sampled_mul(rls_fft* f, rls_sampling* s, int32_t op, const void* x, void* y);
 int32_t rls_fft_sampled_mul_normal(rls_fft* f, rls_sampling* s, const void* p, void* v);
 
+/* Matrix-free RadonOp: the operator of the reference's computed-tomography example, DEFINED as the exact
+ * parallel-beam line integral of a piecewise-constant image.  Image n1 x n2 column-major (pixel (i, j) = element i + n1 j, centre
+ * xr = i - (n1 - 1) / 2, yr = j - (n2 - 1) / 2); D detector bins per angle at t_k = k - (D - 1) / 2; sinogram D x n_angles, detector
+ * fastest; M = D n_angles, N = n1 n2.  A[k + D q, i + n1 j] = w(|t_k - (xr cos(angle_q) + yr sin(angle_q))|), the chord of the line
+ * through the unit pixel: with mx / mn the larger / smaller of |cos|, |sin| and hi = (|cos| + |sin|) / 2,
+ * w(d) = clamp((hi - d) / mn, 0, 1) / mx; for mn = 0 (an angle within 2^-40 of an axis is snapped onto it) w = 1 / mx for d < hi,
+ * 0.5 / mx for d == hi (a ray along a pixel edge), else 0.  The weights are real for every element type: A^H = A^T.  No circle
+ * mask, no attenuation.  Scalars cross as doubles.  A null handle: RLS_E_INVALID.  All but create are asynchronous on the context's stream.
+ *   rls_radon_create     dtype RLS_F32 / C32 / F64 / C64; angles_host: n_angles >= 1 finite doubles (radians), a HOST array; detectors: D,
+ *                        0 = the default 2 ceil(hypot(n1, n2) / 2) + 1 (every ray that meets the image).  Validated on the host before
+ *                        anything is uploaded: extents >= 1, M and N below 2^31 -- anything else RLS_E_INVALID.  Owns the per-angle table
+ *                        (computed in double on the host, stored in the element's real type) and a workspace of M elements; waits for
+ *                        the upload.
+ *   rls_radon_destroy
+ *   rls_radon_info       M, N, D (null pointers are skipped).
+ *   rls_radon_mul        the 5-argument mul!: op = RLS_OP_N: y = alpha A x + beta y (M outputs), a lane per ray marching along the major
+ *                        axis; RLS_OP_T / RLS_OP_C (one and the same): y = alpha A^T x + beta y (N outputs), L lanes per pixel, each
+ *                        walking its share of the angles in order, the L partials combined in a fixed order.  No atomics: the same
+ *                        bits run to run.  beta = 0: y is not read.  x and y must not overlap.  L in {1, 4, 16, 64} follows from N;
+ *                        rls_tune_set("radon_lanes", L) forces it (0: automatic; another value: RLS_E_INVALID).  Instantiations
+ *                        differ in the last bits, each reproducible.
+ *   rls_radon_mul_normal v = A^T A p: the forward into the handle's workspace, then the adjoint -- two launches, the bits of the two
+ *                        calls made one after the other.  v may be p.
+ *   rls_radon_to_dense   A (M x N, column-major, leading dimension lda >= M) = the matrix, every entry the bits the products use.
+ *   rls_radon_lanes      the L the adjoint would run with now. */
+typedef struct rls_radon rls_radon;
+int32_t rls_radon_create(rls_ctx* ctx, int32_t dtype, int64_t n1, int64_t n2, int64_t n_angles, const double* angles_host, int64_t detectors,
+                         rls_radon** out);
+int32_t rls_radon_destroy(rls_radon* r);
+int32_t rls_radon_info(rls_radon* r, int64_t* M, int64_t* N, int64_t* D);
+int32_t rls_radon_mul(rls_radon* r, int32_t op, double alpha_re, double alpha_im, const void* x, double beta_re, double beta_im, void* y);
+int32_t rls_radon_mul_normal(rls_radon* r, const void* p, void* v);
+int32_t rls_radon_to_dense(rls_radon* r, void* A, int64_t lda);
+int32_t rls_radon_lanes(rls_radon* r, int32_t* out);
+
 /* ---------------------------------------------------------------------------------------------
  * operator handle: the backend's operator type for A (SURVEY 3.1 "two operator modes").
  * A' * A on it yields the lazy normal operator (matrix-free, two GEMVs) unless a Gram matrix is set.

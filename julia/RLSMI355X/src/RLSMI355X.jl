@@ -767,4 +767,51 @@ function sampled_fft_mul_normal!(v::RLSVector{T}, P::RLSSampledFFTOp{T}, p::RLSV
   v
 end
 
+# ---- matrix-free RadonOp (csrc/radon.hip): thin wrappers of rls_radon_* ------------------------------------------------------------
+"RadonOp(T; angles, shape, detectors = 0): the exact parallel-beam line integral of a piecewise-constant image; `detectors = 0` is the default count"
+mutable struct RLSRadonOp{T}
+  handle::Ptr{Cvoid}
+  M::Int
+  N::Int
+  D::Int
+  ctx::Context
+end
+function RLSRadonOp(::Type{T}; angles::AbstractVector{<:Real}, shape, detectors::Integer = 0, ctx = context()) where {T}
+  ang = Float64.(angles)
+  h = Ref{Ptr{Cvoid}}(C_NULL)
+  check(ctx, ccall((:rls_radon_create, librls[]), Int32, (Ptr{Cvoid}, Int32, Int64, Int64, Int64, Ptr{Float64}, Int64, Ref{Ptr{Cvoid}}),
+                   ctx.handle, dtypecode(T), shape[1], shape[2], length(ang), ang, detectors, h), "rls_radon_create")
+  M, N, D = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+  check(ctx, ccall((:rls_radon_info, librls[]), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}), h[], M, N, D), "rls_radon_info")
+  R = RLSRadonOp{T}(h[], M[], N[], D[], ctx)
+  finalizer(r -> ccall((:rls_radon_destroy, librls[]), Int32, (Ptr{Cvoid},), r.handle), R)
+end
+Base.size(R::RLSRadonOp) = (R.M, R.N)
+function radon_mul!(op::Int32, R::RLSRadonOp{T}, x::RLSVector{T}, y::RLSVector{T}, alpha::Number, beta::Number) where {T}
+  a, b = ComplexF64(alpha), ComplexF64(beta)
+  check(R.ctx, ccall((:rls_radon_mul, librls[]), Int32, (Ptr{Cvoid}, Int32, Float64, Float64, Ptr{Cvoid}, Float64, Float64, Ptr{Cvoid}),
+                     R.handle, op, real(a), imag(a), x.ptr, real(b), imag(b), y.ptr), "rls_radon_mul")
+  y
+end
+LinearAlgebra.mul!(y::RLSVector{T}, R::RLSRadonOp{T}, x::RLSVector{T}, alpha::Number = 1, beta::Number = 0) where {T} =
+  radon_mul!(RLS_OP_N, R, x, y, alpha, beta)
+LinearAlgebra.mul!(y::RLSVector{T}, R::Adjoint{<:Any, RLSRadonOp{T}}, x::RLSVector{T}, alpha::Number = 1, beta::Number = 0) where {T} =
+  radon_mul!(RLS_OP_C, parent(R), x, y, alpha, beta)
+"v = A' * (A * p): two launches, the bits of the two calls"
+function radon_mul_normal!(v::RLSVector{T}, R::RLSRadonOp{T}, p::RLSVector{T}) where {T}
+  check(R.ctx, ccall((:rls_radon_mul_normal, librls[]), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), R.handle, p.ptr, v.ptr), "rls_radon_mul_normal")
+  v
+end
+"Matrix(A) into the M x N device matrix `A`"
+function radon_to_dense!(A::RLSMatrix{T}, R::RLSRadonOp{T}) where {T}
+  check(R.ctx, ccall((:rls_radon_to_dense, librls[]), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64), R.handle, A.ptr, A.lda), "rls_radon_to_dense")
+  A
+end
+"lanes per pixel the adjoint runs with now"
+function radon_lanes(R::RLSRadonOp)
+  v = Ref{Int32}(0)
+  check(R.ctx, ccall((:rls_radon_lanes, librls[]), Int32, (Ptr{Cvoid}, Ref{Int32}), R.handle, v), "rls_radon_lanes")
+  Int(v[])
+end
+
 end # module

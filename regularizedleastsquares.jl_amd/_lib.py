@@ -187,6 +187,14 @@ PROTOTYPES = {
     "rls_fft_variant": (_i32, [_vp, _pi32]),
     "rls_fft_sampled_mul": (_i32, [_vp, _vp, _i32, _vp, _vp]),
     "rls_fft_sampled_mul_normal": (_i32, [_vp, _vp, _vp, _vp]),
+    # ---- matrix-free RadonOp (csrc/radon.hip) ----
+    "rls_radon_create": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _pvp]),
+    "rls_radon_destroy": (_i32, [_vp]),
+    "rls_radon_info": (_i32, [_vp, _pi64, _pi64, _pi64]),
+    "rls_radon_mul": (_i32, [_vp, _i32, _d, _d, _vp, _d, _d, _vp]),
+    "rls_radon_mul_normal": (_i32, [_vp, _vp, _vp]),
+    "rls_radon_to_dense": (_i32, [_vp, _vp, _i64]),
+    "rls_radon_lanes": (_i32, [_vp, _pi32]),
     "rls_operator_create": (_i32, [_vp, _i32, _i64, _i64, _vp, _i64, _pvp]),
     "rls_operator_set_gram": (_i32, [_vp, _vp, _i64]),
     "rls_operator_destroy": (_i32, [_vp]),

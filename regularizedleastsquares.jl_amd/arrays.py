@@ -7,6 +7,7 @@
                 are lazy (`NormalOperator`) so the unchanged constructors land in matrix-free mode
   SamplingOp, FFTOp, ProdOp(SamplingOp, FFTOp)
                 matrix-free operators (csrc/fft.hip): no stored matrix, served by CGNR and FISTA
+  RadonOp       the matrix-free parallel-beam projector of the computed-tomography example (csrc/radon.hip), served likewise
 """
 from __future__ import annotations
 
@@ -746,6 +747,88 @@ class SampledFFTOp(_MatrixFreeOperator):
         self._check(v, self.N, p, self.N)
         check(self.ctx.handle, self.ctx.lib.rls_fft_sampled_mul_normal(self.F._h, self.S._h, p.ptr, v.ptr), "rls_fft_sampled_mul_normal")
         return v
+
+
+class RadonOp(_MatrixFreeOperator):
+    """RadonOp(T; angles, shape) of the reference's computed-tomography example (docs/src/literate/examples/computed_tomography.jl): the
+    exact parallel-beam line integral of a piecewise-constant image (csrc/radon.hip).  The image is column-major,
+    `angles` in radians; the sinogram is detectors x len(angles), detector fastest.  `detectors=None`: 2 ceil(hypot(shape) / 2) + 1
+    bins of unit spacing, every ray that meets the image.  Unlike RadonKA.jl: no inscribed-circle mask, no attenuation, and the default
+    detector count is not shape[0] - 1."""
+
+    def __init__(self, dtype, angles, shape, detectors=None, ctx: Optional[Context] = None):
+        self.dtype = np.dtype(dtype)
+        self.code = dtype_code(self.dtype)
+        self.double = is_double(self.code)
+        try:
+            self.image_shape = tuple(int(s_) for s_ in np.atleast_1d(shape))
+        except (TypeError, ValueError):
+            raise ValueError("RadonOp: shape must hold two positive extents") from None
+        if len(self.image_shape) != 2 or min(self.image_shape) < 1:
+            raise ValueError("RadonOp: shape must hold two positive extents")
+        try:
+            ang = np.ascontiguousarray(np.atleast_1d(np.asarray(angles, dtype=np.float64)))
+        except (TypeError, ValueError):
+            raise ValueError("RadonOp: angles is a non-empty 1-D array of finite angles in radians") from None
+        if ang.ndim != 1 or ang.size < 1 or not np.all(np.isfinite(ang)):
+            raise ValueError("RadonOp: angles is a non-empty 1-D array of finite angles in radians")
+        if detectors is None:
+            detectors = 2 * int(np.ceil(np.hypot(*self.image_shape) / 2)) + 1
+        if int(detectors) != detectors or detectors < 1:
+            raise ValueError("RadonOp: detectors must be a positive integer")
+        self.angles, self.detectors = ang, int(detectors)
+        self.M, self.N = self.detectors * int(ang.size), self.image_shape[0] * self.image_shape[1]
+        if self.M >= 2 ** 31 or self.N >= 2 ** 31:
+            raise ValueError("RadonOp: detectors * len(angles) and prod(shape) must be below 2^31")
+        self.ctx = ctx or default_context()   # (every refusal above is raised ahead of any context)
+        h = C.c_void_p()
+        check(self.ctx.handle, self.ctx.lib.rls_radon_create(self.ctx.handle, self.code, self.image_shape[0], self.image_shape[1], ang.size,
+                                                             ang.ctypes.data, self.detectors, C.byref(h)), "rls_radon_create")
+        self._h = h
+
+    def _mul(self, op: int, x: DeviceVector, y: DeviceVector, alpha, beta):
+        alpha, beta = complex(alpha), complex(beta)
+        check(self.ctx.handle, self.ctx.lib.rls_radon_mul(self._h, op, alpha.real, alpha.imag, x.ptr, beta.real, beta.imag, y.ptr),
+              "rls_radon_mul")
+        return y
+
+    def mul_(self, y: DeviceVector, x: DeviceVector, alpha=1.0, beta=0.0):
+        self._check(y, self.M, x, self.N)
+        return self._mul(OP_N, x, y, alpha, beta)
+
+    def mul_adj_(self, x: DeviceVector, y: DeviceVector, alpha=1.0, beta=0.0):
+        self._check(x, self.N, y, self.M)
+        return self._mul(OP_C, y, x, alpha, beta)
+
+    def mul_transpose_(self, x: DeviceVector, y: DeviceVector, alpha=1.0, beta=0.0):
+        self._check(x, self.N, y, self.M)
+        return self._mul(OP_T, y, x, alpha, beta)
+
+    def mul_normal_(self, v: DeviceVector, p: DeviceVector):
+        """v = A^T (A p): the forward into the handle's workspace, then the adjoint"""
+        self._check(v, self.N, p, self.N)
+        check(self.ctx.handle, self.ctx.lib.rls_radon_mul_normal(self._h, p.ptr, v.ptr), "rls_radon_mul_normal")
+        return v
+
+    def to_dense(self) -> DeviceMatrix:
+        """Matrix(A), every entry the bits the products use: for small operators and tests (M x N elements)"""
+        A = DeviceMatrix(self.M, self.N, self.dtype, self.ctx)
+        check(self.ctx.handle, self.ctx.lib.rls_radon_to_dense(self._h, A.ptr, A.lda), "rls_radon_to_dense")
+        return A
+
+    def lanes(self) -> int:
+        """lanes per pixel the adjoint runs with under the context's current tune (rls_radon_lanes)"""
+        v = C.c_int32()
+        check(self.ctx.handle, self.ctx.lib.rls_radon_lanes(self._h, C.byref(v)), "rls_radon_lanes")
+        return v.value
+
+    def __del__(self):
+        try:
+            if self._h and self.ctx.handle:
+                self.ctx.lib.rls_radon_destroy(self._h)
+        except Exception:
+            pass
+        self._h = None
 
 
 class MatrixFreeNormalOperator:

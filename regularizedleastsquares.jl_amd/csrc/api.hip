@@ -338,6 +338,11 @@ int32_t rls_tune_set(rls_ctx* ctx, const char* key, int32_t value) {
     ctx->tune.sparse_lanes = value;
   }
   else if (!strcmp(key, "sparse_kaczmarz_lds")) ctx->tune.sparse_kaczmarz_lds = value ? 1 : 0;
+  else if (!strcmp(key, "radon_lanes")) {
+    if (value != 0 && value != 1 && value != 4 && value != 16 && value != 64)
+      return rls_fail(ctx, RLS_E_INVALID, "tune_set: radon_lanes is 0 (automatic), 1, 4, 16 or 64");
+    ctx->tune.radon_lanes = value;
+  }
   else return rls_fail(ctx, RLS_E_INVALID, "tune_set: unknown key");
   return 0;
 }

@@ -67,6 +67,7 @@ struct rls_tuning {
                                // 0: always one launch per level and dimension (and the FISTA plan refuses the wavelet term)
   int fft_fused = 1;           // fft.hip: 1 = small images run both dimensions (and the normal operator of S o F) in ONE single-workgroup
                                // launch; 2: every image that fits one workgroup's LDS; 0: always one launch per dimension
+  int radon_lanes = 0;         // radon.hip: lanes per pixel of the adjoint (1, 4, 16, 64); 0 = from the pixel count
   int sparse_lanes = 0;        // sparse.hip: lanes per output row of rls_sparse_mul (1, 4, 16, 64); 0 = from the mean non-zeros per row
   int sparse_kaczmarz_lds = 1; // sparse.hip: 1 = the sparse row sweep keeps x in the workgroup's LDS where it fits; 0: always in global memory
   int resident_spin = 100000;  // bound of every in-kernel wait, in polls (~1 us each: a wall-clock bound of ~0.1 s per
