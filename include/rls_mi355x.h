@@ -354,6 +354,35 @@ int32_t rls_radon_mul_normal(rls_radon* r, const void* p, void* v);
 int32_t rls_radon_to_dense(rls_radon* r, void* A, int64_t lda);
 int32_t rls_radon_lanes(rls_radon* r, int32_t* out);
 
+/* Matrix-free NFFTOp: non-uniform Fourier sampling, DEFINED as y_j = sum_k x_k exp(-2 pi i k . nu_j) over
+ * k_d in {-floor(N_d / 2), ..., ceil(N_d / 2) - 1}, no scale factor, the image column-major; M = J, N = prod(shape).  Computed on a grid
+ * of n_d = the smallest power of two >= 2 N_d points with the Kaiser-Bessel window of NFFT3 at 2 m taps per dimension (periodic),
+ * deapodised by phihat(k) = I0(m sqrt(b^2 - (2 pi k / n)^2)), b = pi (2 - N_d / n_d).  A null handle: RLS_E_INVALID.  All but create are
+ * asynchronous on the context's stream.
+ *   rls_nfft_create      dtype RLS_C32 / C64 (else RLS_E_INVALID); shape[ndims]: extents of 1 are dropped, one or two may remain (none: a
+ *                        signal of one point), need not be powers of two; nodes_host: d x J doubles, a HOST array, coordinate d of node
+ *                        j at nodes_host[d J + j], every one in [-0.5, 0.5); m: 1 ... 8.  Validated on the host before anything is
+ *                        uploaded: a node out of range or NaN, J < 1, J >= 2^31, an extent < 1: RLS_E_INVALID; m out of range, a third
+ *                        extent, a grid line 2 N_d beyond the FFT's 8192 (C32) / 4096 (C64) points: RLS_E_UNSUPPORTED; a grid that does
+ *                        not fit: RLS_E_WORKSPACE.  Owns an rls_fft of the grid (RLS_FFT_SHIFT only), the two phihat tables and the
+ *                        J d 2m tap weights (computed in double on the host, rounded once), the cell -> node lists of the adjoint,
+ *                        the grid and a workspace of J elements; waits for the upload.
+ *   rls_nfft_destroy
+ *   rls_nfft_info        M = J, N, and the grid's point count n_1 n_2 (null pointers are skipped).
+ *   rls_nfft_mul         op = RLS_OP_N: y = A x (J outputs): embed and deapodise, the unscaled shifted FFT, a lane per node summing its
+ *                        (2 m)^d taps in one fixed order.  RLS_OP_C: y = A^H x (N outputs), the exact conjugate transpose of what
+ *                        RLS_OP_N computes: an OUTPUT-driven spread (a lane per grid point walks the cells it can depend on, cells
+ *                        ascending, nodes in input order; no atomics: the same bits run to run), the adjoint FFT, crop and deapodise.
+ *                        RLS_OP_T: RLS_E_UNSUPPORTED, nothing written.  x and y must not overlap.
+ *   rls_nfft_mul_normal  v = A^H A p: the two chains back to back through the handle's workspace, the bits of the two calls.  v may be p. */
+typedef struct rls_nfft rls_nfft;
+int32_t rls_nfft_create(rls_ctx* ctx, int32_t dtype, int32_t ndims, const int64_t* shape, int64_t J, const double* nodes_host, int32_t m,
+                        rls_nfft** out);
+int32_t rls_nfft_destroy(rls_nfft* h);
+int32_t rls_nfft_info(rls_nfft* h, int64_t* M, int64_t* N, int64_t* grid_points);
+int32_t rls_nfft_mul(rls_nfft* h, int32_t op, const void* x, void* y);
+int32_t rls_nfft_mul_normal(rls_nfft* h, const void* p, void* v);
+
 /* ---------------------------------------------------------------------------------------------
  * operator handle: the backend's operator type for A (SURVEY 3.1 "two operator modes").
  * A' * A on it yields the lazy normal operator (matrix-free, two GEMVs) unless a Gram matrix is set.

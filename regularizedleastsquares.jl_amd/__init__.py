@@ -8,7 +8,7 @@ The directory name contains a dot, so it cannot be imported with a plain `import
 use the `rls_amd` shim at the repository root (`import rls_amd`).
 """
 from ._lib import LIB_PATH, RLSError, load  # noqa: F401
-from .arrays import (Context, DeviceMatrix, DeviceSparseMatrix, DeviceVector, FFTOp, MatrixFreeNormalOperator, NormalOperator,  # noqa: F401
+from .arrays import (Context, DeviceMatrix, DeviceSparseMatrix, DeviceVector, FFTOp, MatrixFreeNormalOperator, NFFTOp, NormalOperator,  # noqa: F401
                      OperatorHandle, ProdOp, RadonOp, SampledFFTOp, SamplingOp, SparseNormalOperator, WeightingOp, default_context, normalOperator)
 from .regularization import (AbstractParameterizedRegularization, AbstractProjectionRegularization,  # noqa: F401
                              AbstractRegularization, GradientOp, L1Regularization, L2Regularization,

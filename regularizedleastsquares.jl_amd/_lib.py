@@ -195,6 +195,12 @@ PROTOTYPES = {
     "rls_radon_mul_normal": (_i32, [_vp, _vp, _vp]),
     "rls_radon_to_dense": (_i32, [_vp, _vp, _i64]),
     "rls_radon_lanes": (_i32, [_vp, _pi32]),
+    # ---- matrix-free NFFTOp (csrc/nfft.hip) ----
+    "rls_nfft_create": (_i32, [_vp, _i32, _i32, _pi64, _i64, _vp, _i32, _pvp]),
+    "rls_nfft_destroy": (_i32, [_vp]),
+    "rls_nfft_info": (_i32, [_vp, _pi64, _pi64, _pi64]),
+    "rls_nfft_mul": (_i32, [_vp, _i32, _vp, _vp]),
+    "rls_nfft_mul_normal": (_i32, [_vp, _vp, _vp]),
     "rls_operator_create": (_i32, [_vp, _i32, _i64, _i64, _vp, _i64, _pvp]),
     "rls_operator_set_gram": (_i32, [_vp, _vp, _i64]),
     "rls_operator_destroy": (_i32, [_vp]),

@@ -8,6 +8,7 @@
   SamplingOp, FFTOp, ProdOp(SamplingOp, FFTOp)
                 matrix-free operators (csrc/fft.hip): no stored matrix, served by CGNR and FISTA
   RadonOp       the matrix-free parallel-beam projector of the computed-tomography example (csrc/radon.hip), served likewise
+  NFFTOp        matrix-free non-uniform Fourier sampling (csrc/nfft.hip), served likewise
 """
 from __future__ import annotations
 
@@ -826,6 +827,107 @@ class RadonOp(_MatrixFreeOperator):
         try:
             if self._h and self.ctx.handle:
                 self.ctx.lib.rls_radon_destroy(self._h)
+        except Exception:
+            pass
+        self._h = None
+
+
+class NFFTOp(_MatrixFreeOperator):
+    """NFFTOp(T; nodes, shape): non-uniform Fourier sampling without a stored matrix (csrc/nfft.hip),
+    y_j = sum_k x_k exp(-2 pi i k . nodes[:, j]) over k_d in {-floor(N_d / 2), ..., ceil(N_d / 2) - 1}, no scale factor.  The image is
+    column-major with one or two extents (unit extents are dropped; they need not be powers of two); `nodes` is a host array d x J
+    (a 1-D array of J nodes for a signal) with every entry in [-0.5, 0.5); `m` in 1 ... 8 is the half-width of the Kaiser-Bessel
+    window, 2 m taps per dimension on a grid of the smallest power of two >= 2 N_d points.  The adjoint is the exact conjugate
+    transpose of what the forward computes.  Unlike NFFT.jl: the oversampling is not a parameter, the window is fixed, nodes at 0.5
+    are refused rather than wrapped, and there is no density compensation (ProdOp(WeightingOp, NFFTOp) stays refused) and no
+    Toeplitz form of the normal operator."""
+
+    MAX_EXTENT = {8: 4096, 16: 2048}   # by element size: the grid line 2 N_d must fit the FFT's 8192 / 4096 points
+
+    def __init__(self, dtype, nodes, shape, m=4, ctx: Optional[Context] = None):
+        self.dtype = np.dtype(dtype)
+        self.code = dtype_code(self.dtype)
+        if self.dtype.kind != "c":
+            raise TypeError(f"NFFTOp: a complex element type is required, got {self.dtype}")
+        self.double = is_double(self.code)
+        try:
+            self.image_shape = tuple(int(s_) for s_ in np.atleast_1d(shape))
+        except (TypeError, ValueError):
+            raise ValueError("NFFTOp: shape must hold one or two positive extents") from None
+        if not self.image_shape or min(self.image_shape) < 1:
+            raise ValueError("NFFTOp: shape must hold one or two positive extents")
+        ext = [s_ for s_ in self.image_shape if s_ != 1] or [1]
+        if len(ext) > 2:
+            raise ValueError("NFFTOp: 1-D and 2-D shapes only")
+        if max(ext) > self.MAX_EXTENT[self.dtype.itemsize]:
+            raise ValueError(f"NFFTOp: an extent of {max(ext)} needs a grid line beyond the FFT's "
+                             f"{2 * self.MAX_EXTENT[self.dtype.itemsize]} points for {self.dtype}")
+        try:
+            nu = np.asarray(nodes, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("NFFTOp: nodes is a d x J array of numbers in [-0.5, 0.5)") from None
+        if nu.ndim == 1 and len(ext) == 1:
+            nu = nu[None, :]
+        if nu.ndim != 2 or nu.shape[0] != len(ext) or nu.shape[1] < 1:
+            raise ValueError(f"NFFTOp: nodes must be {len(ext)} x J with J >= 1, got shape {nu.shape}")
+        if nu.shape[1] >= 2 ** 31:
+            raise ValueError("NFFTOp: the number of nodes must be below 2^31")
+        if not np.all((nu >= -0.5) & (nu < 0.5)):   # (a NaN fails both)
+            raise ValueError("NFFTOp: every node coordinate must lie in [-0.5, 0.5)")
+        if isinstance(m, bool) or int(m) != m or not 1 <= m <= 8:
+            raise ValueError("NFFTOp: m must be an integer in 1 ... 8")
+        self.nodes, self.m = np.ascontiguousarray(nu), int(m)
+        self.M, self.N = int(nu.shape[1]), int(np.prod(self.image_shape))
+        self.ctx = ctx or default_context()   # (every refusal above is raised ahead of any context)
+        cs = (C.c_int64 * len(self.image_shape))(*self.image_shape)
+        h = C.c_void_p()
+        st = self.ctx.lib.rls_nfft_create(self.ctx.handle, self.code, len(self.image_shape), cs, self.M, self.nodes.ctypes.data, self.m, C.byref(h))
+        if st == -2:   # RLS_E_UNSUPPORTED
+            raise ValueError(f"NFFTOp: shape {self.image_shape}, m = {self.m} is not supported: "
+                             + (self.ctx.lib.rls_last_error_string(self.ctx.handle) or b"").decode())
+        check(self.ctx.handle, st, "rls_nfft_create")
+        self._h = h
+        n = C.c_int64()
+        check(self.ctx.handle, self.ctx.lib.rls_nfft_info(self._h, None, None, C.byref(n)), "rls_nfft_info")
+        self.grid_points = n.value
+
+    def _mul(self, op: int, x: DeviceVector, y: DeviceVector):
+        check(self.ctx.handle, self.ctx.lib.rls_nfft_mul(self._h, op, x.ptr, y.ptr), "rls_nfft_mul")
+        return y
+
+    def mul_(self, y: DeviceVector, x: DeviceVector):
+        self._check(y, self.M, x, self.N)
+        return self._mul(OP_N, x, y)
+
+    def mul_adj_(self, x: DeviceVector, y: DeviceVector):
+        self._check(x, self.N, y, self.M)
+        return self._mul(OP_C, y, x)
+
+    def mul_transpose_(self, x: DeviceVector, y: DeviceVector):
+        """refused (RLS_E_UNSUPPORTED): the operator is complex, its transpose is not its adjoint and nothing needs it"""
+        self._check(x, self.N, y, self.M)
+        return self._mul(OP_T, y, x)
+
+    def mul_normal_(self, v: DeviceVector, p: DeviceVector):
+        """v = A^H (A p): the forward into the handle's workspace, then the adjoint; the bits of the two calls.  v may be p"""
+        self._check(v, self.N, p, self.N)
+        check(self.ctx.handle, self.ctx.lib.rls_nfft_mul_normal(self._h, p.ptr, v.ptr), "rls_nfft_mul_normal")
+        return v
+
+    def to_dense(self) -> DeviceMatrix:
+        """Matrix(A) by N forward applications to unit vectors, every entry the bits the product gives: for small operators and tests"""
+        A = np.empty((self.M, self.N), self.dtype, order="F")
+        y = DeviceVector(self.M, self.dtype, self.ctx)
+        for k in range(self.N):
+            e = np.zeros(self.N, self.dtype)
+            e[k] = 1
+            A[:, k] = self.mul_(y, DeviceVector.from_host(e, self.ctx)).to_host()
+        return DeviceMatrix.from_host(A, self.ctx)
+
+    def __del__(self):
+        try:
+            if self._h and self.ctx.handle:
+                self.ctx.lib.rls_nfft_destroy(self._h)
         except Exception:
             pass
         self._h = None

@@ -37,7 +37,7 @@ def _dense_only(*operators):
     """the multi-GPU classes shard and upload dense host arrays: a sparse operator is refused, not densified behind the caller's back"""
     for A in operators:
         if getattr(A, "matrix_free", False):
-            raise TypeError("multigpu: matrix-free operators (SamplingOp, FFTOp, ProdOp(SamplingOp, FFTOp), RadonOp) are served by CGNR and FISTA; "
+            raise TypeError("multigpu: matrix-free operators (SamplingOp, FFTOp, ProdOp(SamplingOp, FFTOp), RadonOp, NFFTOp) are served by CGNR and FISTA; "
                             "the multi-GPU solvers take dense host arrays")
         if isinstance(A, DeviceSparseMatrix) or hasattr(A, "tocsc"):
             raise TypeError("multigpu: sparse operators (DeviceSparseMatrix) are served by CGNR, FISTA and Kaczmarz; the multi-GPU "

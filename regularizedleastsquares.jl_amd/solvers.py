@@ -71,7 +71,7 @@ def _resolve_sparse_operator(A, AHA):
     raise TypeError("with a sparse A, AHA must be None, A.normal_operator() or a dense Gram DeviceMatrix (e.g. A.to_dense().gram())")
 
 
-_MATRIX_FREE_SERVED = ("matrix-free operators (SamplingOp, FFTOp, ProdOp(SamplingOp, FFTOp), RadonOp) are served by CGNR and FISTA on their lazy "
+_MATRIX_FREE_SERVED = ("matrix-free operators (SamplingOp, FFTOp, ProdOp(SamplingOp, FFTOp), RadonOp, NFFTOp) are served by CGNR and FISTA on their lazy "
                        "normal operator; no other solver, no multi-GPU class and no explicit Gram matrix (AHA = DeviceMatrix) takes them")
 
 
