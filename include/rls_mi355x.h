@@ -902,11 +902,19 @@ int32_t rls_admm_set_bregman(rls_admm* a, int32_t iterations_inner, void* Y, int
  *   rls_direct_solve       for the K columns of B (M x K, columns ldb apart; for an operator without A: N x K, taken as A^H b):
  *                          X = A^H B, L Y = X, L^H X = Y, then the projection proj_kind (RLS_PROJ_*).  X: N x K, columns ldx apart.
  *                          1 <= K <= 16 * 65535.  K + 2 ceil(N / 64) launches: A^H b is one product per column.
+ *                          (An operator without A: one copy kernel X = B instead, none where B == X with ldb == ldx.)
+ *                          For such an operator B and X are either the same block (B == X, ldb == ldx: solved in place) or
+ *                          do not overlap; anything else is RLS_E_INVALID.
  *   rls_direct_get_status  synchronises.  info = 0, or the 1-based column of the first pivot that was not strictly positive
  *                          and finite (G + lambda I is not positive definite: use lambda > 0).  The factorisation records
  *                          it in a device word; every later kernel of that factorisation and of the solves reads the word
  *                          and does nothing, so X is then NOT written.  A failed factor is never reused: the next
  *                          rls_direct_factor runs again, whatever its lambda and whether or not the status was read.
+ *   rls_direct_get_factor  a read-only view of the factor, valid while the plan lives: W, the device pointer of the padded square
+ *                          (ld x ld elements, column-major, ld = 64 ceil(N / 64)), whose strict lower-triangle 64 x 64 tiles hold
+ *                          L and whose diagonal tiles hold the unfactored Schur complements; Ldiag, the ceil(N / 64) factored
+ *                          diagonal tiles (64 x 64, column-major, one after the other) behind it.  Rows and columns >= N carry the
+ *                          identity.  Launches nothing and does not synchronise: read behind rls_direct_get_status.
  * All asynchronous on the context's stream but the status.  Null arguments: RLS_E_INVALID.
  * ------------------------------------------------------------------------------------------- */
 typedef struct rls_direct rls_direct;
@@ -919,6 +927,7 @@ int32_t rls_direct_create(rls_operator* op, rls_direct** out);
 int32_t rls_direct_factor(rls_direct* s, float lambda);
 int32_t rls_direct_solve(rls_direct* s, int64_t K, const void* B, int64_t ldb, void* X, int64_t ldx, int32_t proj_kind);
 int32_t rls_direct_get_status(rls_direct* s, rls_direct_status* out);
+int32_t rls_direct_get_factor(rls_direct* s, void** W, int64_t* ld, void** Ldiag);
 int32_t rls_direct_destroy(rls_direct* s);
 
 /* ---------------------------------------------------------------------------------------------

@@ -341,6 +341,7 @@ PROTOTYPES = {
     "rls_direct_factor": (_i32, [_vp, _f]),
     "rls_direct_solve": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32]),
     "rls_direct_get_status": (_i32, [_vp, C.POINTER(DirectStatus)]),
+    "rls_direct_get_factor": (_i32, [_vp, _pvp, _pi64, _pvp]),
     "rls_direct_destroy": (_i32, [_vp]),
     # ---- PseudoInverse: one-sided Jacobi SVD of A (csrc/pinv.hip) ----
     "rls_pinv_create": (_i32, [_vp, _pvp]),

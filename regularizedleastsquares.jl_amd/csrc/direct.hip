@@ -25,7 +25,8 @@
 //                       contribution from ITS row block below (forward, L Y = X) or above (backward, L^H X = Y).
 // The forward pass reads X and writes the solved blocks to the plan's workspace, the backward pass goes the other way, so no
 // workgroup reads a block another one of the same launch writes.  The projection (RLS_PROJ_*) rides on the backward pass's
-// store.  2 NB launches per solve, behind the K products A^H b.
+// store.  2 NB launches per solve, behind the K products A^H b (a Gram-only
+// operator: behind chol_copy_kernel, X = B).
 //
 // Every sum runs in a fixed order: two runs give the same bits.  No atomics, no grid-wide synchronisation.
 #include "rls_common.hpp"
@@ -231,6 +232,16 @@ __global__ __launch_bounds__(DTHREADS) void chol_trsm_kernel(const E* __restrict
   }
 }
 
+// X = B, one workgroup per column: the right-hand sides of a Gram-only operator (B is A^H b already).  A kernel and not a copy of
+// the runtime's, so that it reads the pivot word like every other one: after a failed factorisation X is not written.
+template <typename E>
+__global__ __launch_bounds__(DTHREADS) void chol_copy_kernel(const E* B, int64_t ldb, E* X, int64_t ldx, int64_t N, const int* info) {
+  if (*info != 0) return;
+  const E* b = B + (int64_t)blockIdx.x * ldb;
+  E* x = X + (int64_t)blockIdx.x * ldx;
+  for (int64_t i = threadIdx.x; i < N; i += DTHREADS) x[i] = b[i];
+}
+
 int64_t rls_direct_padded(int64_t N) { return (N + DB - 1) / DB * DB; }
 // elements of the factor's allocation: the padded square and, behind it, the NB factored diagonal tiles
 size_t rls_direct_factor_elems(int64_t N) {
@@ -251,6 +262,13 @@ int32_t rls_direct_launch_factor(rls_ctx* ctx, int32_t dtype, int64_t N, const v
       if (m > 0) RLS_TRY(rls_launch<chol_trail_kernel<E>>(ctx, dim3(m, m), dim3(DTHREADS), 0, (E*)W, ld, j, (const int*)info));
     }
     return 0;
+  });
+}
+
+int32_t rls_direct_launch_copy(rls_ctx* ctx, int32_t dtype, int64_t N, int K, const void* B, int64_t ldb, void* X, int64_t ldx, const int* info) {
+  return rls_with_elem(dtype, [&](auto t) -> int32_t {
+    using E = typename decltype(t)::type;
+    return rls_launch<chol_copy_kernel<E>>(ctx, dim3((unsigned)K), dim3(DTHREADS), 0, (const E*)B, ldb, (E*)X, ldx, N, info);
   });
 }
 

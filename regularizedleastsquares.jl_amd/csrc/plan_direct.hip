@@ -160,8 +160,14 @@ int32_t rls_direct_solve(rls_direct* s, int64_t K, const void* B, int64_t ldb, v
   if (K < 1 || K > RLS_DIRECT_MAX_RHS || ldb < rows || ldx < op->N || proj_kind < RLS_PROJ_NONE || proj_kind > RLS_PROJ_POSITIVE)
     return rls_fail(ctx, RLS_E_INVALID, "direct_solve: bad argument");
   if (!s->factored) return rls_fail(ctx, RLS_E_STATE, "direct_solve: rls_direct_factor has not run");
-  RLS_HIP(ctx, rls_enter(ctx));
   const size_t es = rls_elem_size(op->dtype);
+  if (!op->A && !(B == X && ldb == ldx)) {  // the copy X = B runs all columns at once: the two must be the same block or apart
+    const char *b0 = (const char*)B, *x0 = (const char*)X;
+    const char* b1 = b0 + ((size_t)(K - 1) * (size_t)ldb + (size_t)op->N) * es;
+    const char* x1 = x0 + ((size_t)(K - 1) * (size_t)ldx + (size_t)op->N) * es;
+    if (b0 < x1 && x0 < b1) return rls_fail(ctx, RLS_E_INVALID, "direct_solve: B and X overlap (pass B == X with ldb == ldx, or disjoint blocks)");
+  }
+  RLS_HIP(ctx, rls_enter(ctx));
   if (K > s->ycols) {  // the workspace grows with the widest solve seen (stream-ordered: earlier solves still own the old block)
     rls_alloc_scope alloc_scope(ctx);
     s->mem.rollback(s->ymark);
@@ -174,13 +180,13 @@ int32_t rls_direct_solve(rls_direct* s, int64_t K, const void* B, int64_t ldb, v
     }
     s->ycols = K;
   }
-  // X = A^H B, column by column (each a no-op once the pivot word is set)
-  for (int64_t k = 0; k < K; ++k) {
+  // X = A^H B, column by column (each a no-op once the pivot word is set); a Gram-only operator's B is A^H B already: one guarded copy
+  for (int64_t k = 0; op->A && k < K; ++k) {
     const char* b = (const char*)B + (size_t)k * (size_t)ldb * es;
     char* x = (char*)X + (size_t)k * (size_t)ldx * es;
-    if (op->A) RLS_TRY(rls_launch_gemv(ctx, op->dtype, RLS_OP_C, op->M, op->N, 1.f, 0.f, op->A, op->lda, b, 0.f, 0.f, x, s->info));
-    else if (b != x) RLS_HIP(ctx, hipMemcpyAsync(x, b, (size_t)op->N * es, hipMemcpyDeviceToDevice, ctx->stream));
+    RLS_TRY(rls_launch_gemv(ctx, op->dtype, RLS_OP_C, op->M, op->N, 1.f, 0.f, op->A, op->lda, b, 0.f, 0.f, x, s->info));
   }
+  if (!op->A && !(B == X && ldb == ldx)) RLS_TRY(rls_direct_launch_copy(ctx, op->dtype, op->N, (int)K, B, ldb, X, ldx, s->info));
   return rls_direct_launch_solve(ctx, op->dtype, op->N, s->L, (int)K, X, ldx, s->Y, proj_kind, s->info);
 }
 
@@ -195,6 +201,15 @@ int32_t rls_direct_get_status(rls_direct* s, rls_direct_status* out) {
   out->factorizations = s->factorizations;
   out->info = *s->info_h;
   s->known_good = s->factored && out->info == 0;  // (the stream has been waited for: the word belongs to the last factorisation)
+  return 0;
+}
+
+int32_t rls_direct_get_factor(rls_direct* s, void** W, int64_t* ld, void** Ldiag) {
+  if (!s || !W || !ld || !Ldiag) return RLS_E_INVALID;
+  const int64_t np = rls_direct_padded(s->op->N);
+  *W = s->L;
+  *ld = np;
+  *Ldiag = (char*)s->L + (size_t)np * (size_t)np * rls_elem_size(s->op->dtype);
   return 0;
 }
 

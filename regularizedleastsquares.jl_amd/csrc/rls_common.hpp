@@ -1233,6 +1233,8 @@ int64_t rls_direct_padded(int64_t N);
 size_t rls_direct_factor_elems(int64_t N);
 constexpr int64_t RLS_DIRECT_MAX_RHS = 16 * 65535;  // 16 columns per workgroup, the chunks in gridDim.y
 int32_t rls_direct_launch_factor(rls_ctx* ctx, int32_t dtype, int64_t N, const void* G, int64_t ldg, float lambda, void* W, int* info);
+// X = B (N x K, columns ldb / ldx apart): the right-hand sides of a Gram-only operator; a no-op once `info` is set, like every kernel
+int32_t rls_direct_launch_copy(rls_ctx* ctx, int32_t dtype, int64_t N, int K, const void* B, int64_t ldb, void* X, int64_t ldx, const int* info);
 // X (N x K, columns ldx apart): A^H B in, the solutions out (through the projection); Y: rls_direct_padded(N) x K workspace
 int32_t rls_direct_launch_solve(rls_ctx* ctx, int32_t dtype, int64_t N, const void* W, int K, void* X, int64_t ldx, void* Y, int proj,
                                 const int* info);

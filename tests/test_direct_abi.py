@@ -10,7 +10,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "rls_mi355x.h")
-ENTRY_POINTS = ("rls_direct_create", "rls_direct_factor", "rls_direct_solve", "rls_direct_get_status", "rls_direct_destroy")
+ENTRY_POINTS = ("rls_direct_create", "rls_direct_factor", "rls_direct_solve", "rls_direct_get_status", "rls_direct_destroy",
+                "rls_direct_get_factor")
 
 
 def test_entry_points_declared_exported_and_bound(rls):
@@ -39,7 +40,12 @@ def test_null_arguments_are_errors_not_crashes(rls):
     assert lib.rls_direct_solve(None, 1, p, 16, p, 16, 0) == -1
     assert lib.rls_direct_get_status(None, C.byref(st)) == -1
     assert lib.rls_direct_destroy(None) == -1
-    assert not out.value
+    ld = C.c_int64(-7)
+    assert lib.rls_direct_get_factor(None, C.byref(out), C.byref(ld), C.byref(out)) == -1
+    assert lib.rls_direct_get_factor(p, None, C.byref(ld), C.byref(out)) == -1      # (refused before the plan is looked at)
+    assert lib.rls_direct_get_factor(p, C.byref(out), None, C.byref(out)) == -1
+    assert lib.rls_direct_get_factor(p, C.byref(out), C.byref(ld), None) == -1
+    assert not out.value and ld.value == -7
 
 
 def test_classes_are_public(rls):
